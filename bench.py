@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Forward spectra/sec of the MI355X radiative-transfer engine.
 
-    python bench.py --gpus N --steps K --warmup W [--walkers B]
+    python bench.py --gpus N --steps K --warmup W [--walkers B] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path (profile prep + RT kernel; for N > 1 also
 the RCCL all-gather that reassembles each spectrum) over one batch of B*N
@@ -19,10 +19,18 @@ child's output and exits with its code.
 The contract's figure (`value`, `ms_per_step`) is the FIRST timed window: exactly K
 steps between barriers, on SURVEY 8d's opacities to the letter (exp(N(-25,3)) cm2/g: every
 layer of every column is walked, no credit from the `toomuch` cut), every step launching its
-own prep_profiles kernel -- the form an MCMC step takes.  The line
-certifies itself: `parity` = the spectra of the LAST step of that window against the CPU
-oracle on the same walkers (whole spectra; the run fails above 1e-9) and, bit for bit,
-against a fresh plain launch.  Around the window the default run adds, outside it:
+own prep_profiles kernel -- the form an MCMC step takes.  A plain run
+does only that: set-up, spin-up, W warm-up steps, the K timed steps, the line.
+--dump-outputs DIR writes the spectra of the last timed step to DIR/spectra.npy (float64,
+[walker][wavenumber]; the walkers and tables are seeded, so the same arguments give the same
+inputs on every run and two builds can be compared output for output).
+
+--full adds the record around the window.  Its window brackets every --event-stride-th RT
+launch with HIP events (the per-kernel figures of `roofline`), and the line certifies itself:
+`parity` = the spectra of the LAST step of that window against the CPU oracle on the same
+walkers (whole spectra; the run fails above 1e-9) and, bit for bit, against a fresh plain
+launch.  Outside the window it adds:
+  * `roofline`: bytes per launch from untimed passes over the run's batches, profiler records of this build;
   * `windows`: --repeats further windows of K steps (median / min / max);
   * `roofline.cold`: launches after a 1 GiB scratch sweep (nothing in L2 / Infinity Cache);
   * `integ_sweep` / `cut_sweep`: the integration rules and the two `toomuch` cuts at 10 and 256 walkers;
@@ -31,7 +39,8 @@ against a fresh plain launch.  Around the window the default run adds, outside i
   * `configs`: BASELINE.json configs 2, 4 (per-GPU work), transit geometry, 5, MC3-style worker processes;
   * `cpu_baseline` (the oracle on the timed run's own walkers); for N > 1 `scaling_diag` and a
     `replicas` comparison.
---no-extras keeps only the contract's window (what the profiling scripts run).
+Everything goes to the detail file (--detail).  --full --no-extras keeps the contract's window,
+`parity` and `roofline` (what the profiling scripts run); --full --no-cpu drops `cpu_baseline`.
 
 --dry-gloo replaces the GPU engine by a stub (spectra = a known function of the
 profile and the sample index) on CPU tensors with the gloo backend: it exercises
@@ -39,8 +48,8 @@ the launch path, the sharded step loop, the bucketed all-gather and the
 one-JSON-line contract where there is no GPU (tests/test_bench_launch.py).  Its
 line carries "dry": true and measures nothing.
 
-Prints ONE JSON line on rank 0 (contract: see the task statement; `roofline`
-and `cpu_baseline` objects included).
+Prints ONE JSON line on rank 0 (contract: see the task statement; with --full the `roofline`,
+`cpu_baseline` and `parity` objects filled in).
 """
 from __future__ import annotations
 
@@ -332,17 +341,33 @@ def contract_line(res, detail_name="bench_detail.json"):
 
 
 def emit(res, detail_path=DETAIL_FILE):
-    """Everything to the detail file (and to stderr), the contract's line -- alone -- to stdout."""
+    """Everything to the detail file (and to stderr) if there is one (--full), the contract's line -- alone -- to
+    stdout."""
     name = None
-    try:
-        with open(detail_path, "w") as f:
-            json.dump(res, f, indent=1)
-            f.write("\n")
-        name = os.path.relpath(detail_path, ROOT)
-    except OSError as e:       # a read-only checkout must not cost the line
-        print("bench.py: detail file not written: %r" % (e,), file=sys.stderr)
-    print("bench.py detail: " + json.dumps(res), file=sys.stderr, flush=True)
+    if detail_path:
+        try:
+            with open(detail_path, "w") as f:
+                json.dump(res, f, indent=1)
+                f.write("\n")
+            name = os.path.relpath(detail_path, ROOT)
+        except OSError as e:       # a read-only checkout must not cost the line
+            print("bench.py: detail file not written: %r" % (e,), file=sys.stderr)
+        print("bench.py detail: " + json.dumps(res), file=sys.stderr, flush=True)
     print(contract_line(res, name), flush=True)
+
+
+DUMP_LIMIT = 64 << 20    # bytes --dump-outputs may write
+
+
+def dump_outputs(outdir, spectra):
+    """--dump-outputs: the spectra [walker][wavenumber] of the last timed step, float64 as the engine returns them, to
+    outdir/spectra.npy.  Above DUMP_LIMIT bytes only evenly spaced walkers (rows), the same ones on every run."""
+    s = spectra.detach().cpu().numpy().astype(np.float64, copy=False)
+    if s.nbytes > DUMP_LIMIT:
+        keep = max(1, DUMP_LIMIT // (s.shape[1] * 8))
+        s = s[np.unique(np.linspace(0, s.shape[0] - 1, keep).round().astype(int))]
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "spectra.npy"), s)
 
 
 def self_launch(ngpus, argv, port=0):
@@ -433,13 +458,19 @@ def main():
     ap.add_argument("--integ", type=int, default=None, choices=[0, 1, 2],
                     help="integration rule of the headline run (default: the engine's, integ 1 = App. A-4)")
     ap.add_argument("--repeats", type=int, default=15,
-                    help="further timed windows of --steps steps after the contract's (spread of the figure)")
+                    help="--full: further timed windows of --steps steps after the contract's (spread of the figure)")
     ap.add_argument("--sweep", default="64,256,1024",
-                    help="extra batch sizes reported under batch_sweep (N=1 only; '' = none)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+                    help="--full: extra batch sizes reported under batch_sweep (N=1 only; '' = none)")
+    ap.add_argument("--full", action="store_true",
+                    help="the whole record around the contract's window: kernel events, roofline, parity against "
+                         "the CPU oracle, repeats, cold pass, sweeps, other opacity model, configs, cpu_baseline, "
+                         "replicas comparison; everything in the detail file (a plain run times the window only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the spectra of the last timed step to DIR/spectra.npy (float64 [walker][wavenumber])")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the contract's window and its roofline record: no repeats, cold pass, sweeps, "
-                         "survey8d leg, configs, replicas comparison (what the profiling scripts run)")
+                    help="with --full: only the contract's window, its parity and its roofline record: no repeats, "
+                         "cold pass, sweeps, survey8d leg, configs, replicas comparison (what the profiling scripts run)")
     ap.add_argument("--event-stride", type=int, default=3,
                     help="HIP events bracket every n-th RT launch of the timed windows (a pair of event records "
                          "costs the stream about 5 us, 7 %% of a ten-walker step; 1 = every launch).  Coprime with "
@@ -481,8 +512,8 @@ def main():
     ap.add_argument("--dry-gloo", action="store_true",
                     help="no GPU: stub engine, CPU tensors, gloo backend (launch-path check, not a measurement)")
     ap.add_argument("--detail", default=DETAIL_FILE,
-                    help="where the full record goes (windows, sweeps, side legs, notes); stdout carries the contract's "
-                         "line only, at most %d bytes" % LINE_LIMIT)
+                    help="--full: where the full record goes (windows, sweeps, side legs, notes); stdout carries the "
+                         "contract's line only, at most %d bytes" % LINE_LIMIT)
     ap.add_argument("--master-port", type=int, default=0,
                     help="rendezvous port of the self-launched N > 1 run (0: pick a free one)")
     a = ap.parse_args()
@@ -680,7 +711,7 @@ def main():
         dt_local, drain_s, out = window(steps)
         # the contract's window has ended: its LAST step's spectra, set aside for the parity record
         last_set = (steps - 1) % nsets
-        out_first = out.clone() if (out is not None and not dry) else out
+        out_first = out.clone() if out is not None else None
         wins = [dt_local]
         for _ in range(repeats):
             wins.append(window(steps)[0])
@@ -723,7 +754,7 @@ def main():
     # wavenumber block; replicas: every rank evaluates its own B walkers on the whole grid.
     nwalk = a.walkers * world if (sharded or world == 1) else a.walkers
     nspectra_per_step = a.walkers * world
-    extras = not a.no_extras and not dry
+    extras = a.full and not a.no_extras and not dry
     models, kname_box = [], [""]
 
     def byte_model_passes(profs_h, d_prof):
@@ -740,15 +771,17 @@ def main():
             walked, wpc, kname_box[0] = engine.walked_end()
             models.append(launch_byte_model(case, profs_h[sset], walked, wpc, h0 - l0, spline=conv["cia_interp"] == "spline"))
 
-    main_run = timed(nwalk, a.steps, a.warmup, True, repeats=a.repeats if extras else 0,
-                     before=byte_model_passes if (rank == 0 and not dry) else None)
+    main_run = timed(nwalk, a.steps, a.warmup, a.full, repeats=a.repeats if extras else 0,
+                     before=byte_model_passes if (a.full and rank == 0 and not dry) else None)
     dt, kern_ms, nlaunch, ok, profs_all = (main_run[k] for k in ("dt", "kern_ms", "nlaunch", "ok", "profs"))
     profs0 = profs_all[0]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, main_run["last_out"])
 
     # ---- the line certifies its own output: the LAST step of the contract's window against the CPU oracle on
     # the same walkers (whole spectra), and bit for bit against a fresh launch of that batch with nothing prefetched
     parity = None
-    if rank == 0 and not dry:
+    if a.full and rank == 0 and not dry:
         lset = main_run["last_set"]
         got = main_run["last_out"]                       # [nwalk][whole grid if gathered, else this rank's block]
         plain = torch.empty((nwalk, hi - lo), dtype=torch.float64, device=dev)
@@ -810,85 +843,86 @@ def main():
                        "walkers_per_step": nspectra_per_step, "nlayers": a.nlayers, "nwave": a.nwave,
                        "parallelism": ("wavenumber-block shard x%d + all-gather" if a.mode == "shard"
                                        else "replicas x%d, no collective") % world},
-            "scaling_diag": main_run["diag"],
-            "roofline": None, "cpu_baseline": None}, detail_path=a.detail)
+            "scaling_diag": main_run["diag"] if a.full else None,
+            "roofline": None, "cpu_baseline": None}, detail_path=a.detail if a.full else None)
     elif rank == 0:
         assert ok
         value = nspectra_per_step * a.steps / dt
-        # SURVEY 8d's bytes per RT launch on this GPU, to the letter: two T planes x M molecules + two planes of ONE
-        # CIA table per file + profile in + spectrum out (the engine's own count, bartrt_algorithmic_bytes, follows
-        # its table slots: two per file under `cia_interp spline`)
-        alg = nwalk * (2.0 * a.nlayers * (hi - lo) * len(case.opmol) * 8 + 2.0 * a.nlayers * (hi - lo) * len(case.cia) * 8
-                       + (len(case.species) + 1) * a.nlayers * 8 + (hi - lo) * 8)
-        per_launch_s = kern_ms / 1e3 / max(nlaunch, 1)
         nsets = profs_all.shape[0]
-        kname = kname_box[0]
-        d_out = torch.empty((nwalk, hi - lo), dtype=torch.float64, device=dev)
-        mean = lambda key: float(np.mean([m[key] for m in models]))
-        uniq, eff, wfrac = mean("unique_bytes"), mean("effective_bytes"), mean("layers_walked_frac")
-        # ---- cold launches: a 1 GiB scratch sweep in front of each (L2 and the 256 MiB Infinity
-        # Cache hold nothing of the tables: every compulsory byte comes from HBM)
-        cold = None
-
-        def cold_pass():
-            scratch = torch.zeros(1 << 27, dtype=torch.float64, device=dev)
-            cms = []
-            for j in range(12):
-                scratch.add_(1.0)
-                torch.cuda.synchronize()
-                engine.timing_begin(1)
-                engine.run_batch_dev(main_run["d_prof"][j % nsets], d_out)
-                torch.cuda.synchronize()
-                ms, n = engine.timing_end()
-                cms.append(ms / max(n, 1))
-            del scratch
-            cmed = float(np.median(cms))
-            return {"launch_ms": _stats(cms), "achieved_GBps": uniq / (cmed / 1e3) / 1e9,
-                    "frac": uniq / (cmed / 1e3) / 1e9 / PEAK_HBM_GBS,
-                    "note": "RT kernel after a 1 GiB read-modify-write of a scratch buffer (4x the Infinity Cache): "
-                            "the launch's compulsory bytes all come from HBM; the warm figure above is taken in "
-                            "the timed loop, where consecutive batches share most table planes through the "
-                            "256 MiB Infinity Cache, and is an upper bound on DRAM utilisation"}
-        if extras and world == 1:
-            cold = guarded("cold", cold_pass)
-        # ---- committed profiler figures of THIS build (tools/profile_round.sh), if any
         sid = source_id()
-        same = lambda j: (j.get("source_id") == sid and j.get("walkers") == nwalk and j.get("nwave") == a.nwave
-                          and j.get("nlayers") == a.nlayers and j.get("integ", 0) == integ and world == 1
-                          and j.get("kappa", "forest") == a.kappa and j.get("cut", "vertical") == conv["cut"]
-                          and bool(j.get("prefetch", True)) == bool(a.prefetch))
-        traffic = traffic_src = None
-        try:
-            j = json.load(open(os.path.join(ROOT, "profiles", "pmc_latest.json")))
-            if same(j):
-                traffic, traffic_src = j["traffic_bytes_per_launch"], "profiles/%s_pmc.json" % j.get("tag", "?")
-        except Exception:
-            pass
-        fp64 = None
-        try:
-            j = json.load(open(os.path.join(ROOT, "profiles", "isa_latest.json")))
-            if j.get("source_id") == sid and j["kernel_family"] in kname:
-                flop = mean("layer_wavenumbers_walked") * (2 * j["fp64_fma_per_layer"] + j["fp64_other_per_layer"])
-                fp64 = {"flop_per_launch": flop, "achieved": flop / per_launch_s / 1e12, "peak": PEAK_FP64_TFLOPS,
-                        "unit": "TFLOP/s", "frac": flop / per_launch_s / 1e12 / PEAK_FP64_TFLOPS,
-                        "note": "fp64 VALU operations the kernel's layer loop issues per (layer, wavenumber) "
-                                "(FMA = 2) x (layer, wavenumber) pairs walked; vector fp64 peak, no MFMA on this path",
-                        "source": "profiles/%s" % j.get("file", "isa_latest.json")}
-        except Exception:
-            pass
-        bound_measured = None
-        try:
-            j = json.load(open(os.path.join(ROOT, "profiles", "sq_latest.json")))
-            if j.get("source_id") == sid:
-                bound_measured = {"source": "profiles/%s" % j.get("file", "sq_latest.json")}
-                for k_, v in j.get("batches", {}).items():
-                    busy = v["fp64_pipe_busy_fraction"]
-                    bound_measured[k_] = {
-                        "bound": "fp64_valu" if busy >= 0.75 else "issue/latency",
-                        "fp64_pipe_busy_fraction": busy, "resident_waves_per_simd": v["resident_waves_per_simd"],
-                        "wave_time": v["wave_time"]}
-        except Exception:
-            pass
+        if a.full:
+            # SURVEY 8d's bytes per RT launch on this GPU, to the letter: two T planes x M molecules + two planes of ONE
+            # CIA table per file + profile in + spectrum out (the engine's own count, bartrt_algorithmic_bytes, follows
+            # its table slots: two per file under `cia_interp spline`)
+            alg = nwalk * (2.0 * a.nlayers * (hi - lo) * len(case.opmol) * 8 + 2.0 * a.nlayers * (hi - lo) * len(case.cia) * 8
+                           + (len(case.species) + 1) * a.nlayers * 8 + (hi - lo) * 8)
+            per_launch_s = kern_ms / 1e3 / max(nlaunch, 1)
+            kname = kname_box[0]
+            d_out = torch.empty((nwalk, hi - lo), dtype=torch.float64, device=dev)
+            mean = lambda key: float(np.mean([m[key] for m in models]))
+            uniq, eff, wfrac = mean("unique_bytes"), mean("effective_bytes"), mean("layers_walked_frac")
+            # ---- cold launches: a 1 GiB scratch sweep in front of each (L2 and the 256 MiB Infinity
+            # Cache hold nothing of the tables: every compulsory byte comes from HBM)
+            cold = None
+
+            def cold_pass():
+                scratch = torch.zeros(1 << 27, dtype=torch.float64, device=dev)
+                cms = []
+                for j in range(12):
+                    scratch.add_(1.0)
+                    torch.cuda.synchronize()
+                    engine.timing_begin(1)
+                    engine.run_batch_dev(main_run["d_prof"][j % nsets], d_out)
+                    torch.cuda.synchronize()
+                    ms, n = engine.timing_end()
+                    cms.append(ms / max(n, 1))
+                del scratch
+                cmed = float(np.median(cms))
+                return {"launch_ms": _stats(cms), "achieved_GBps": uniq / (cmed / 1e3) / 1e9,
+                        "frac": uniq / (cmed / 1e3) / 1e9 / PEAK_HBM_GBS,
+                        "note": "RT kernel after a 1 GiB read-modify-write of a scratch buffer (4x the Infinity Cache): "
+                                "the launch's compulsory bytes all come from HBM; the warm figure above is taken in "
+                                "the timed loop, where consecutive batches share most table planes through the "
+                                "256 MiB Infinity Cache, and is an upper bound on DRAM utilisation"}
+            if extras and world == 1:
+                cold = guarded("cold", cold_pass)
+            # ---- committed profiler figures of THIS build (tools/profile_round.sh), if any
+            same = lambda j: (j.get("source_id") == sid and j.get("walkers") == nwalk and j.get("nwave") == a.nwave
+                              and j.get("nlayers") == a.nlayers and j.get("integ", 0) == integ and world == 1
+                              and j.get("kappa", "forest") == a.kappa and j.get("cut", "vertical") == conv["cut"]
+                              and bool(j.get("prefetch", True)) == bool(a.prefetch))
+            traffic = traffic_src = None
+            try:
+                j = json.load(open(os.path.join(ROOT, "profiles", "pmc_latest.json")))
+                if same(j):
+                    traffic, traffic_src = j["traffic_bytes_per_launch"], "profiles/%s_pmc.json" % j.get("tag", "?")
+            except Exception:
+                pass
+            fp64 = None
+            try:
+                j = json.load(open(os.path.join(ROOT, "profiles", "isa_latest.json")))
+                if j.get("source_id") == sid and j["kernel_family"] in kname:
+                    flop = mean("layer_wavenumbers_walked") * (2 * j["fp64_fma_per_layer"] + j["fp64_other_per_layer"])
+                    fp64 = {"flop_per_launch": flop, "achieved": flop / per_launch_s / 1e12, "peak": PEAK_FP64_TFLOPS,
+                            "unit": "TFLOP/s", "frac": flop / per_launch_s / 1e12 / PEAK_FP64_TFLOPS,
+                            "note": "fp64 VALU operations the kernel's layer loop issues per (layer, wavenumber) "
+                                    "(FMA = 2) x (layer, wavenumber) pairs walked; vector fp64 peak, no MFMA on this path",
+                            "source": "profiles/%s" % j.get("file", "isa_latest.json")}
+            except Exception:
+                pass
+            bound_measured = None
+            try:
+                j = json.load(open(os.path.join(ROOT, "profiles", "sq_latest.json")))
+                if j.get("source_id") == sid:
+                    bound_measured = {"source": "profiles/%s" % j.get("file", "sq_latest.json")}
+                    for k_, v in j.get("batches", {}).items():
+                        busy = v["fp64_pipe_busy_fraction"]
+                        bound_measured[k_] = {
+                            "bound": "fp64_valu" if busy >= 0.75 else "issue/latency",
+                            "fp64_pipe_busy_fraction": busy, "resident_waves_per_simd": v["resident_waves_per_simd"],
+                            "wave_time": v["wave_time"]}
+            except Exception:
+                pass
         wms = main_run["windows_ms"]
         res = {
             "metric": "forward spectra/sec (100 layers x 1e4 wavenumbers)",
@@ -930,61 +964,64 @@ def main():
                 "parallelism": ("wavenumber-block shard x%d + all-gather" % world if sharded else
                                 "replicas x%d, no collective" % world) if world > 1 else "single GPU",
             },
-            "windows": {
-                "value_is": "the FIRST window: exactly --steps steps between barriers, as the contract times them; "
-                            "the other %d windows ran right after it, same length" % (len(wms) - 1),
-                "ms_per_step": _stats(wms), "spectra_per_s_median": nspectra_per_step / (np.median(wms) / 1e3),
-            } if len(wms) > 1 else None,
-            "parity": parity,
-            "roofline": {
-                "bound": "hbm", "achieved": uniq / per_launch_s / 1e9, "peak": PEAK_HBM_GBS,
-                "unit": "GB/s", "frac": uniq / per_launch_s / 1e9 / PEAK_HBM_GBS,
-                "traffic": traffic, "traffic_source": traffic_src,
-                "traffic_GBps": traffic / per_launch_s / 1e9 if traffic else None,
-                # the three fractions side by side; each is one division of figures in this object
-                "fractions": {
-                    "frac_survey8d_letter": alg / per_launch_s / 1e9 / PEAK_HBM_GBS,
-                    "frac_survey8d_letter_note": "SURVEY 8d's bytes per spectrum (80.09 MB, no credit for table planes "
-                                                 "shared between the walkers of a launch) x walkers / avg launch time / "
-                                                 "peak.  NOT bounded by HBM: walkers whose temperatures fall in the "
-                                                 "same bracket read the same planes, which L2 serves -- above 1 it "
-                                                 "says so, not that work is skipped (see `parity`)",
-                    "frac_unique_bytes": uniq / per_launch_s / 1e9 / PEAK_HBM_GBS,
-                    "frac_unique_bytes_note": "= `frac`: the launch's compulsory bytes (every table row counted once per "
-                                              "launch, down to where its wave stopped) / avg launch time / peak",
-                    "frac_counter": traffic / per_launch_s / 1e9 / PEAK_HBM_GBS if traffic else None,
-                    "frac_counter_note": "`traffic` (FETCH_SIZE x calibration + WRITE_SIZE of the committed rocprofv3 "
-                                         "--pmc passes of this build and workload) / avg launch time / peak.  FETCH_SIZE "
-                                         "counts requests that leave L2, INCLUDING those the 256 MiB Infinity Cache (MALL) "
-                                         "serves: in the timed loop consecutive batches share most planes through it, so "
-                                         "this is an upper bound on DRAM utilisation; `frac_cold` is the lower one",
-                    "frac_cold": (cold or {}).get("frac"),
-                    "frac_cold_note": "unique bytes / median launch time after a 1 GiB scratch sweep / peak: nothing "
-                                      "in L2 or the Infinity Cache, every compulsory byte from DRAM",
-                },
-                "bound_measured": bound_measured,
-                "cold": cold,
-                "bytes_model": "achieved = unique_bytes_per_launch / avg launch time: every (layer, T plane, "
-                               "molecule, 64-wavenumber column) row the launch's walkers read down to the layer "
-                               "where their wave stopped, counted once per launch (walkers share planes; a row "
-                               "has to come from HBM once per launch whatever the implementation), + CIA rows, "
-                               "layer records in, spectra out.  Computed from the launch's own profiles and the "
-                               "kernels' walked-layer record (bartrt_walked_*), averaged over the cycled batches",
-                "unique_bytes_per_launch": uniq,
-                "effective_bytes_per_launch": eff,
-                "layers_walked_frac": wfrac,
-                "kernel": kname, "launches": nlaunch, "event_stride": a.event_stride,
-                "sets_sampled": int(min(nsets, nlaunch)) if np.gcd(a.event_stride, nsets) == 1 else None,
-                "avg_launch_ms": per_launch_s * 1e3,
-                # SURVEY 8d's per-spectrum figure x walkers: no credit for rows shared between the
-                # walkers of a launch or for layers below the cut, so it is NOT bounded by the HBM
-                # peak (the shared rows are served by L2) -- kept as a labelled throughput figure
-                "survey8d_algorithmic_bytes_per_launch": alg,
-                "survey8d_algorithmic_GBps": alg / per_launch_s / 1e9,
-                "fp64": fp64,
-            },
             "source_id": sid,
         }
+        if a.full:
+            res.update({
+                "windows": {
+                    "value_is": "the FIRST window: exactly --steps steps between barriers, as the contract times them; "
+                                "the other %d windows ran right after it, same length" % (len(wms) - 1),
+                    "ms_per_step": _stats(wms), "spectra_per_s_median": nspectra_per_step / (np.median(wms) / 1e3),
+                } if len(wms) > 1 else None,
+                "parity": parity,
+                "roofline": {
+                    "bound": "hbm", "achieved": uniq / per_launch_s / 1e9, "peak": PEAK_HBM_GBS,
+                    "unit": "GB/s", "frac": uniq / per_launch_s / 1e9 / PEAK_HBM_GBS,
+                    "traffic": traffic, "traffic_source": traffic_src,
+                    "traffic_GBps": traffic / per_launch_s / 1e9 if traffic else None,
+                    # the three fractions side by side; each is one division of figures in this object
+                    "fractions": {
+                        "frac_survey8d_letter": alg / per_launch_s / 1e9 / PEAK_HBM_GBS,
+                        "frac_survey8d_letter_note": "SURVEY 8d's bytes per spectrum (80.09 MB, no credit for table planes "
+                                                     "shared between the walkers of a launch) x walkers / avg launch time / "
+                                                     "peak.  NOT bounded by HBM: walkers whose temperatures fall in the "
+                                                     "same bracket read the same planes, which L2 serves -- above 1 it "
+                                                     "says so, not that work is skipped (see `parity`)",
+                        "frac_unique_bytes": uniq / per_launch_s / 1e9 / PEAK_HBM_GBS,
+                        "frac_unique_bytes_note": "= `frac`: the launch's compulsory bytes (every table row counted once per "
+                                                  "launch, down to where its wave stopped) / avg launch time / peak",
+                        "frac_counter": traffic / per_launch_s / 1e9 / PEAK_HBM_GBS if traffic else None,
+                        "frac_counter_note": "`traffic` (FETCH_SIZE x calibration + WRITE_SIZE of the committed rocprofv3 "
+                                             "--pmc passes of this build and workload) / avg launch time / peak.  FETCH_SIZE "
+                                             "counts requests that leave L2, INCLUDING those the 256 MiB Infinity Cache (MALL) "
+                                             "serves: in the timed loop consecutive batches share most planes through it, so "
+                                             "this is an upper bound on DRAM utilisation; `frac_cold` is the lower one",
+                        "frac_cold": (cold or {}).get("frac"),
+                        "frac_cold_note": "unique bytes / median launch time after a 1 GiB scratch sweep / peak: nothing "
+                                          "in L2 or the Infinity Cache, every compulsory byte from DRAM",
+                    },
+                    "bound_measured": bound_measured,
+                    "cold": cold,
+                    "bytes_model": "achieved = unique_bytes_per_launch / avg launch time: every (layer, T plane, "
+                                   "molecule, 64-wavenumber column) row the launch's walkers read down to the layer "
+                                   "where their wave stopped, counted once per launch (walkers share planes; a row "
+                                   "has to come from HBM once per launch whatever the implementation), + CIA rows, "
+                                   "layer records in, spectra out.  Computed from the launch's own profiles and the "
+                                   "kernels' walked-layer record (bartrt_walked_*), averaged over the cycled batches",
+                    "unique_bytes_per_launch": uniq,
+                    "effective_bytes_per_launch": eff,
+                    "layers_walked_frac": wfrac,
+                    "kernel": kname, "launches": nlaunch, "event_stride": a.event_stride,
+                    "sets_sampled": int(min(nsets, nlaunch)) if np.gcd(a.event_stride, nsets) == 1 else None,
+                    "avg_launch_ms": per_launch_s * 1e3,
+                    # SURVEY 8d's per-spectrum figure x walkers: no credit for rows shared between the
+                    # walkers of a launch or for layers below the cut, so it is NOT bounded by the HBM
+                    # peak (the shared rows are served by L2) -- kept as a labelled throughput figure
+                    "survey8d_algorithmic_bytes_per_launch": alg,
+                    "survey8d_algorithmic_GBps": alg / per_launch_s / 1e9,
+                    "fp64": fp64,
+                },
+            })
         if extras and world == 1 and not a.prefetch:
             def prefetched():
                 r = timed(nwalk, a.steps, a.warmup, True, repeats=4, prefetch=True)
@@ -996,7 +1033,7 @@ def main():
                     "spectra_per_s_median": nspectra_per_step / (np.median(r["windows_ms"]) / 1e3),
                     "rt_kernel_ms": r["kern_ms"] / max(r["nlaunch"], 1)}
             res["with_prefetch"] = guarded("with_prefetch", prefetched)
-        if main_run["diag"]:
+        if a.full and main_run["diag"]:
             res["scaling_diag"] = main_run["diag"]
         if replicas:
             res["replicas"] = replicas
@@ -1048,12 +1085,12 @@ def main():
             res[other + "_workload"] = guarded(other, lambda: bench_configs.kappa_leg(
                 a, wd, conv, other, make_profiles, launch_byte_model, PEAK_HBM_GBS))
             res["configs"] = guarded("configs", lambda: bench_configs.run_all(integ, headline_dir=wd, kappa=a.kappa))
-        if world == 1 and not a.no_cpu:
+        if a.full and world == 1 and not a.no_cpu:
             res["cpu_baseline"] = guarded("cpu_baseline", lambda: cpu_baseline(
                 case, conv, profs_all.reshape(-1, profs_all.shape[-1])))
         else:
             res["cpu_baseline"] = None
-        emit(res, detail_path=a.detail)
+        emit(res, detail_path=a.detail if a.full else None)
     if in_group:
         dist.barrier()
         dist.destroy_process_group()

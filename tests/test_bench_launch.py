@@ -9,6 +9,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -20,7 +22,7 @@ def _bench(*args, env=None):
 
 
 def test_gpus2_self_launch_one_json_line():
-    r = _bench("--gpus", "2", "--dry-gloo", "--steps", "11", "--warmup", "3", "--walkers", "3",
+    r = _bench("--gpus", "2", "--full", "--dry-gloo", "--steps", "11", "--warmup", "3", "--walkers", "3",
                "--nwave", "2501", "--gather-steps", "4", "--sweep", "")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -44,7 +46,7 @@ def test_gpus8_uneven_grid_dry_run():
     """A node's worth of ranks on a grid that does not divide (2 501 samples over 8): the blocks' padding in the
     bucketed all-gather, the reassembly checked sample for sample inside bench.py, and the keys the first real
     8-GPU record will be read by (what an N = 8 line should look like)."""
-    r = _bench("--gpus", "8", "--dry-gloo", "--steps", "9", "--warmup", "2", "--walkers", "2",
+    r = _bench("--gpus", "8", "--full", "--dry-gloo", "--steps", "9", "--warmup", "2", "--walkers", "2",
                "--nwave", "2501", "--gather-steps", "4", "--sweep", "")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -63,7 +65,7 @@ def test_gpus8_uneven_grid_dry_run():
 
 def test_gpus2_replicas_mode_has_no_collective():
     """--mode replicas: SURVEY 8e's baseline -- every rank the whole grid and its own walkers."""
-    r = _bench("--gpus", "2", "--dry-gloo", "--mode", "replicas", "--steps", "5", "--warmup", "1", "--walkers", "3",
+    r = _bench("--gpus", "2", "--full", "--dry-gloo", "--mode", "replicas", "--steps", "5", "--warmup", "1", "--walkers", "3",
                "--nwave", "700", "--sweep", "")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -182,9 +184,9 @@ def test_contract_line_is_short_and_complete():
 
 
 def test_detail_file_carries_the_rest(tmp_path):
-    """The dry run writes the full record where --detail says and names it in the line."""
+    """The dry --full run writes the full record where --detail says and names it in the line."""
     detail = tmp_path / "detail.json"
-    r = _bench("--gpus", "2", "--dry-gloo", "--steps", "5", "--warmup", "1", "--walkers", "2", "--nwave", "700",
+    r = _bench("--gpus", "2", "--full", "--dry-gloo", "--steps", "5", "--warmup", "1", "--walkers", "2", "--nwave", "700",
                "--sweep", "", "--detail", str(detail))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -192,3 +194,84 @@ def test_detail_file_carries_the_rest(tmp_path):
     full = json.load(open(detail))
     assert "exposed_gather_note" in full["scaling_diag"]         # the notes are there, not in the line
     assert json.loads(lines[0])["scaling_diag"]["mode"] == "shard"
+
+
+def _dry_last_step(nwalk, nwave, steps, world):
+    """The stub spectra of the last timed step of a dry run: batch (steps - 1) mod nsets of the seeded walkers,
+    every rank's block reassembled."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from bart_amd import synth
+    case = synth.make_case("unused", nlayers=100, nwave=nwave, kappa_model="survey8d", write=False)
+    nsets = max(1, min(16, 4096 // nwalk))
+    profs = bench.make_profiles(case, nwalk * nsets, seed=20260103).reshape(nsets, nwalk, -1)
+    return bench.StubEngine.expected(torch.from_numpy(profs[(steps - 1) % nsets]), 0, nwave).numpy()
+
+
+def test_plain_run_times_the_window_and_dumps_its_last_step(tmp_path):
+    """A plain run (no --full) prints the contract's line and nothing of the full record: no detail file, no
+    scaling_diag.  --dump-outputs writes the spectra of the last timed step, the same on every run."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        detail, out = tmp_path / ("detail%d.json" % k), tmp_path / ("out%d" % k)
+        r = _bench("--gpus", "2", "--dry-gloo", "--steps", "7", "--warmup", "2", "--walkers", "3", "--nwave", "701",
+                   "--detail", str(detail), "--dump-outputs", str(out))
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout
+        j = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in j, key
+        assert j["steps"] == 7 and j["warmup"] == 2 and j["ms_per_step"] > 0 and j["detail"] is None
+        assert "scaling_diag" not in j and "parity" not in j and not detail.exists()
+        assert sorted(os.listdir(out)) == ["spectra.npy"]
+        dumps.append(np.load(out / "spectra.npy"))
+    assert dumps[0].dtype == np.float64 and dumps[0].shape == (6, 701)
+    assert np.array_equal(dumps[0], dumps[1])
+    assert np.array_equal(dumps[0], _dry_last_step(6, 701, 7, 2))
+
+
+def test_dump_outputs_samples_rows_above_the_limit(tmp_path, monkeypatch):
+    """Above the size limit --dump-outputs keeps evenly spaced walkers, the same ones on every run."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    spec = torch.arange(50 * 40, dtype=torch.float64).reshape(50, 40)
+    bench.dump_outputs(str(tmp_path / "all"), spec)
+    assert np.array_equal(np.load(tmp_path / "all" / "spectra.npy"), spec.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 10 * 40 * 8)
+    bench.dump_outputs(str(tmp_path / "some"), spec)
+    got = np.load(tmp_path / "some" / "spectra.npy")
+    assert got.nbytes <= 10 * 40 * 8 and got.shape == (10, 40)
+    assert np.array_equal(got, spec.numpy()[np.linspace(0, 49, 10).round().astype(int)])
+
+
+@pytest.mark.gpu
+def test_plain_gpu_run_dumps_the_last_timed_step(tmp_path):
+    """A plain run on the GPU: the contract's line without the --full record, and DIR/spectra.npy = the spectra of
+    the last timed step, held to the CPU oracle on the same walkers as the --full line's `parity` holds them."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from bart_amd import synth
+    steps = 7
+    r = _bench("--steps", str(steps), "--warmup", "2", "--nwave", "2501", "--workdir", str(tmp_path / "w"),
+               "--detail", str(tmp_path / "detail.json"), "--dump-outputs", str(tmp_path / "out"))
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    j = json.loads(lines[0])
+    assert j["steps"] == steps and j["value"] > 0 and j["ms_per_step"] > 0 and j["n_gpus"] == 1
+    assert j["roofline"] is None and j["cpu_baseline"] is None and "parity" not in j
+    assert not (tmp_path / "detail.json").exists()
+    spec = np.load(tmp_path / "out" / "spectra.npy")
+    assert spec.dtype == np.float64 and spec.shape == (10, 2501)
+    case = synth.make_case(str(tmp_path / "w_survey8d"), nlayers=100, nwave=2501, kappa_model="survey8d", write=False)
+    profs = bench.make_profiles(case, 10 * 16, seed=20260103).reshape(16, 10, -1)[(steps - 1) % 16]
+    conv = {k: j["config"][k] for k in ("integ", "cut", "cia_interp")}
+    rec = bench.parity_record(case, conv, profs, spec, True, "the dumped last step")
+    assert rec["ok"], rec

@@ -37,7 +37,7 @@ def test_bench_collective_path_under_torchrun_world1(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--force-collective", "--force-replicas-leg", "--steps", "8", "--warmup", "2",
-           "--no-extras", "--no-cpu", "--nwave", "2501", "--workdir", str(tmp_path / "w"), "--detail", str(tmp_path / "detail.json")]
+           "--full", "--no-extras", "--no-cpu", "--nwave", "2501", "--workdir", str(tmp_path / "w"), "--detail", str(tmp_path / "detail.json")]
     r = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -9,7 +9,7 @@ the bound that applies to it:
   transit_10 / _256   transit geometry on the bench grid (rt_transit_mfma)
   lbl_wnosamp1 / 2160 BASELINE config 5: on-the-fly Voigt line-by-line, 1e6 lines x 1e5 points
 
-Imported by bench.py (N = 1, default run); `python tools/bench_configs.py` prints the
+Imported by bench.py (N = 1, --full run); `python tools/bench_configs.py` prints the
 object on its own."""
 import json
 import os

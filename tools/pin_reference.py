@@ -295,7 +295,9 @@ def main(argv=None):
     ap.add_argument("--json", default=None, help="also write the full report here")
     a = ap.parse_args(argv)
     import fuzz_readers
-    exe = os.path.join(tempfile.gettempdir(), "bartrt_validate_inputs")
+    work = tempfile.mkdtemp(prefix="bartrt_pin_")
+    exe = os.path.join(work, "bartrt_validate_inputs")      # (a private directory: a fixed name in the shared temp
+                                                            # directory may be another user's file)
     subprocess.check_call(["g++", "-O2", "-std=c++17", os.path.join(ROOT, "tools", "fuzz_readers.cpp"),
                            os.path.join(ROOT, "bart_amd", "csrc", "io.cpp"), "-o", exe])
     del fuzz_readers
@@ -303,7 +305,6 @@ def main(argv=None):
     if not cfgs:
         print("no *.cfg in %s" % a.refdir)
         return 2
-    work = tempfile.mkdtemp(prefix="bartrt_pin_")
     reports = []
     for cfg in cfgs:
         rep = pin_one(cfg, exe, a.tol, work)

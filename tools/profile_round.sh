@@ -8,23 +8,23 @@ root=$(pwd)
 out=$root/gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
-B="--steps 200 --warmup 20 --no-cpu --no-extras"
+B="--steps 200 --warmup 20 --full --no-cpu --no-extras"
 cd /tmp
 rocprofv3 --kernel-trace --stats -d "$out/stats_w10" --output-format csv -- python3 "$root/bench.py" $B > "$out/stats_w10.log" 2>&1
 # the integration rules side by side: rule 0 and rule 1 (the default) at 10 and 256 walkers
 rocprofv3 --kernel-trace --stats -d "$out/stats_w10_i0" --output-format csv -- python3 "$root/bench.py" $B --integ 0 > "$out/stats_w10_i0.log" 2>&1
 rocprofv3 --kernel-trace --stats -d "$out/stats_w10_i1" --output-format csv -- python3 "$root/bench.py" $B --integ 1 > "$out/stats_w10_i1.log" 2>&1
-rocprofv3 --kernel-trace --stats -d "$out/stats_w256_i0" --output-format csv -- python3 "$root/bench.py" --steps 20 --warmup 5 --no-cpu --no-extras --walkers 256 --integ 0 > "$out/stats_w256_i0.log" 2>&1
-rocprofv3 --kernel-trace --stats -d "$out/stats_w256_i1" --output-format csv -- python3 "$root/bench.py" --steps 20 --warmup 5 --no-cpu --no-extras --walkers 256 --integ 1 > "$out/stats_w256_i1.log" 2>&1
+rocprofv3 --kernel-trace --stats -d "$out/stats_w256_i0" --output-format csv -- python3 "$root/bench.py" --steps 20 --warmup 5 --full --no-cpu --no-extras --walkers 256 --integ 0 > "$out/stats_w256_i0.log" 2>&1
+rocprofv3 --kernel-trace --stats -d "$out/stats_w256_i1" --output-format csv -- python3 "$root/bench.py" --steps 20 --warmup 5 --full --no-cpu --no-extras --walkers 256 --integ 1 > "$out/stats_w256_i1.log" 2>&1
 # the two cuts side by side and the prefetched form
 rocprofv3 --kernel-trace --stats -d "$out/stats_w10_vert" --output-format csv -- python3 "$root/bench.py" $B --cut vertical > "$out/stats_w10_vert.log" 2>&1
-rocprofv3 --kernel-trace --stats -d "$out/stats_w256_vert" --output-format csv -- python3 "$root/bench.py" --steps 20 --warmup 5 --no-cpu --no-extras --walkers 256 --cut vertical > "$out/stats_w256_vert.log" 2>&1
+rocprofv3 --kernel-trace --stats -d "$out/stats_w256_vert" --output-format csv -- python3 "$root/bench.py" --steps 20 --warmup 5 --full --no-cpu --no-extras --walkers 256 --cut vertical > "$out/stats_w256_vert.log" 2>&1
 rocprofv3 --kernel-trace --stats -d "$out/stats_w10_pf" --output-format csv -- python3 "$root/bench.py" $B --prefetch > "$out/stats_w10_pf.log" 2>&1
 rocprofv3 --kernel-trace --stats -d "$out/stats_w10_forest" --output-format csv -- python3 "$root/bench.py" $B --kappa forest > "$out/stats_w10_forest.log" 2>&1
 rocprofv3 --kernel-trace --stats -d "$out/stats_w1" --output-format csv -- python3 "$root/bench.py" $B --walkers 1 > "$out/stats_w1.log" 2>&1
-rocprofv3 --kernel-trace --stats -d "$out/stats_w256" --output-format csv -- python3 "$root/bench.py" --steps 20 --warmup 5 --no-cpu --no-extras --walkers 256 > "$out/stats_w256.log" 2>&1
-rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$out/pmc_fetch" --output-format csv -- python3 "$root/bench.py" --steps 50 --warmup 10 --no-cpu --no-extras > "$out/pmc_fetch.log" 2>&1
-rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$out/pmc_write" --output-format csv -- python3 "$root/bench.py" --steps 50 --warmup 10 --no-cpu --no-extras > "$out/pmc_write.log" 2>&1
+rocprofv3 --kernel-trace --stats -d "$out/stats_w256" --output-format csv -- python3 "$root/bench.py" --steps 20 --warmup 5 --full --no-cpu --no-extras --walkers 256 > "$out/stats_w256.log" 2>&1
+rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$out/pmc_fetch" --output-format csv -- python3 "$root/bench.py" --steps 50 --warmup 10 --full --no-cpu --no-extras > "$out/pmc_fetch.log" 2>&1
+rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$out/pmc_write" --output-format csv -- python3 "$root/bench.py" --steps 50 --warmup 10 --full --no-cpu --no-extras > "$out/pmc_write.log" 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$out/pmc_calib" --output-format csv -- python3 "$root/tools/pmc_calib.py" > "$out/pmc_calib.log" 2>&1
 rocprofv3 --kernel-trace --stats -d "$out/stats_transit" --output-format csv -- python3 "$root/tools/transit_bench.py" 10 256 > "$out/stats_transit.log" 2>&1
 rocprofv3 --kernel-trace --stats -d "$out/stats_6mol2cia" --output-format csv -- python3 "$root/tools/shape_bench.py" 1 10 256 > "$out/stats_6mol2cia.log" 2>&1
@@ -48,7 +48,7 @@ python3 tools/isa_stats.py --json profiles/isa_latest.json rt_eclipse_simpson_sl
 # SQ pass of the same build (roofline.bound_measured)
 bash tools/sq_counters.sh "$tag" > "$out/sq.log" 2>&1
 # the bench line last, so that its `traffic` / `bound_measured` / `fp64` are this build's figures
-python3 bench.py > "$out/bench.json" 2> "$out/bench.err"
+python3 bench.py --full > "$out/bench.json" 2> "$out/bench.err"
 cp "$out/bench.json" "profiles/${tag}_bench.json"
 cp bench_detail.json "profiles/${tag}_bench_detail.json"
 mkdir -p "$out/profiles" && cp profiles/${tag}_* profiles/pmc_latest.json profiles/isa_latest.json profiles/sq_latest.json "$out/profiles/" 2>/dev/null

@@ -9,10 +9,10 @@ root=$(pwd)
 out=$root/gpurun_out/$tag/sq
 rm -rf "$out"; mkdir -p "$out"
 cd /tmp
-B="--steps 60 --warmup 10 --no-cpu --no-extras"
+B="--steps 60 --warmup 10 --full --no-cpu --no-extras"
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVES -d "$out/w10" --output-format csv -- python3 "$root/bench.py" $B > "$out/w10.log" 2>&1
 rocprofv3 --kernel-trace --pmc SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_MISC SQ_WAIT_INST_LDS SQ_INSTS_VALU SQ_INSTS_SALU -d "$out/w10b" --output-format csv -- python3 "$root/bench.py" $B > "$out/w10b.log" 2>&1
-rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVES -d "$out/w256" --output-format csv -- python3 "$root/bench.py" --steps 20 --warmup 5 --no-cpu --no-extras --walkers 256 > "$out/w256.log" 2>&1
+rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVES -d "$out/w256" --output-format csv -- python3 "$root/bench.py" --steps 20 --warmup 5 --full --no-cpu --no-extras --walkers 256 > "$out/w256.log" 2>&1
 cd "$root"
 python3 - "$tag" <<'PY'
 import collections, csv, glob, json, os, sys
