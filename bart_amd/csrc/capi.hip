@@ -4,6 +4,7 @@
 #include <string>
 
 #include "../../include/bartrt.h"
+#include "contrib.hpp"
 #include "engine.hpp"
 #include "lbl.hpp"
 #include "share.hpp"
@@ -151,6 +152,7 @@ void teardown(double wait_s) {
   }
   if (g_eng) {
     (void)hipDeviceSynchronize();
+    cf_release();   // (the contribution-function tables and workspaces belong to this engine)
     delete g_eng;
     g_eng = nullptr;
   }
@@ -719,6 +721,59 @@ double bartrt_algorithmic_bytes(int nwalkers) {
   Engine *e = g_eng;
   const double L = e->L, W = e->W(), M = e->M, C = e->C, S = e->S;
   return nwalkers * (2.0 * L * W * M * 8.0 + 2.0 * L * W * C * 8.0 + (S + 1) * L * 8.0 + W * 8.0);
+}
+
+// ---- contribution functions / band transmittance (contrib.hip) ----------
+// what the batched post-processing does not serve: line-by-line engines, sharded engines (a service client never
+// gets here: NEED_ENGINE answers it with BARTRT_ENOTSUP)
+static int cf_unsupported(const Engine *e, const char *who) {
+  if (e->lbl) return fail(BARTRT_ENOTSUP, std::string(who) + ": line-by-line engines are not supported");
+  if (e->lo != 0 || e->hi != e->Wfull) return fail(BARTRT_ENOTSUP, std::string(who) + ": sharded engines are not supported");
+  return BARTRT_OK;
+}
+
+int bartrt_cf_setup(int nfilters, const int *idx0, const int *npts, const double *resp) {
+  NEED_ENGINE();
+  if (int rc = cf_unsupported(g_eng, "cf_setup")) return rc;
+  if (nfilters < 1 || !idx0 || !npts || !resp) return fail(BARTRT_EINVAL, "cf_setup: null buffer or no filters");
+  return guarded([&] {
+    cf_setup(*g_eng, nfilters, idx0, npts, resp);
+    return BARTRT_OK;
+  });
+}
+
+static int cf_check_kind(const Engine *e, int kind, const char *who) {
+  if (int rc = cf_unsupported(e, who)) return rc;
+  if (kind != BARTRT_CF_CONTRIB && kind != BARTRT_CF_TRANSMIT)
+    return fail(BARTRT_EINVAL, std::string(who) + ": kind must be BARTRT_CF_CONTRIB or BARTRT_CF_TRANSMIT");
+  if (kind == BARTRT_CF_CONTRIB && e->solution != 0)
+    return fail(BARTRT_ENOTSUP, std::string(who) + ": contribution functions need the eclipse geometry (transmittance serves transit)");
+  if (cf_nfilters() == 0) return fail(BARTRT_EINVAL, std::string(who) + ": call bartrt_cf_setup first");
+  return BARTRT_OK;
+}
+
+int bartrt_cf_batch(const double *prof, int nwalkers, int nprof, int kind, double *band, double *full, unsigned char *ok) {
+  NEED_ENGINE();
+  Engine *e = g_eng;
+  if (int rc = cf_check_kind(e, kind, "cf_batch")) return rc;
+  if (!prof || !band || nwalkers < 0) return fail(BARTRT_EINVAL, "cf_batch: null buffer");
+  if (nprof != (e->S + 1) * e->L) return fail(BARTRT_EINVAL, "cf_batch: profile length must be (nspecies+1)*nlayers");
+  return guarded([&] {
+    cf_run_host(*e, prof, nwalkers, kind, band, full, ok);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_cf_batch_dev(const double *d_prof, int nwalkers, int kind, double *d_band, double *d_full,
+                        unsigned char *d_ok, void *stream) {
+  NEED_ENGINE();
+  Engine *e = g_eng;
+  if (int rc = cf_check_kind(e, kind, "cf_batch_dev")) return rc;
+  if (!d_prof || !d_band || nwalkers < 0) return fail(BARTRT_EINVAL, "cf_batch_dev: null buffer");
+  return guarded([&] {
+    cf_run_dev(*e, d_prof, nwalkers, kind, d_band, d_full, d_ok, stream ? (hipStream_t)stream : e->stream);
+    return BARTRT_OK;
+  });
 }
 
 // ---- per-step converters (step.hip) ------------------------------------

@@ -1,0 +1,493 @@
+// Band-averaged contribution functions and transmittance of walker batches (include/bartrt.h, bartrt_cf_*).
+//
+// BART's last stage (reference code/cf.py:114-199) on the optical depths this engine walks, with no `toomuch` cut
+// (the `tau.dat` of a `toomuch 1e100` run, without writing it):
+//     cf[k] = B(T_k, nu) (exp(-tau[k-1]) - exp(-tau[k])) / (ln p_k - ln p_{k-1}),  cf[0] = 0   (eclipse / direct)
+//     tr[k] = exp(-tau[k])                                                                     (any geometry)
+// band-averaged per filter as filter_cf does it: trapz(x resp) / trapz(resp) with unit spacing over the grid samples
+// inside the filter.
+//
+//  cf_eclipse<INTEG>  one lane per (walker, wavenumber), one wave per workgroup, the walker's layer records staged in
+//                     LDS (the generic rt_eclipse's tiling, kernels.hip): per layer the table extinction (Rayleigh,
+//                     grey cloud, molecules, CIA), TauColumn<INTEG>, then the layer's value.
+//  cf_transit<STAGE>  the same for the transit geometry: the chord sum of the generic rt_transit (transit_geom.hip).
+//  Band reduction     every 16 layers the wave's values go to an LDS block [16 layers][64 lanes]; for each filter
+//                     that overlaps the tile, lane (j, q) sums layer j over the 16 wavenumbers of quarter q with the
+//                     filter's weights h_i resp_i (h = 1/2 at the window's ends), two cross-lane butterflies add the
+//                     quarters, and one partial per (walker, tile, filter, layer) goes to a workspace.
+//  cf_finish          sums each filter's partials in tile order, divides by trapz(resp).
+// Every sum has a fixed order and no atomics: the bits do not depend on the batch a walker is in.  Not part of the
+// per-step hot path: no kernel table, no run-time instantiation; molecule and CIA counts are run-time parameters.
+#include "contrib.hpp"
+#include "integ.hpp"
+#include "kernels.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+namespace bartrt {
+
+namespace {
+
+constexpr int kCfRows = 16;   // layers per reduction block
+constexpr int kCfPitch = 65;  // doubles per row of the LDS block (64 lanes + 1: rows start on different banks)
+
+struct CfArgs {
+  int L, M, C, W, nwalkers, ntiles, kind, nent;
+  const double *kappa, *cia, *wn;
+  const double *coef;
+  const idx_t *idx;
+  const int *kstop;
+  const double *rdlp;      // [L] 1 / (ln p_k - ln p_{k-1}), k from the top ([0] unused)
+  const double *rtop, *ds; // transit geometry: radii and chord table (prep_profiles, chord_table_fill)
+  const int *tile_ptr;     // [ntiles + 1]: the tile's entries (one per overlapping filter, ascending)
+  const double *wt;        // [nent][64]: the entry's weights h_i resp_i on the tile's lanes, 0 outside the window
+  double *part;            // [nwalkers][nent][L]
+  double *full;            // optional [nwalkers][W][L], atm layer order
+};
+
+// XCD-aware block -> (tile, walker) map (as the generic eclipse kernel's)
+__device__ inline void cf_block_to_work(int b, int nwalkers, int &tile, int &walker) {
+  const int xcd = b & 7, j = b >> 3;
+  walker = j % nwalkers;
+  tile = (j / nwalkers) * 8 + xcd;
+}
+
+// extinction of layer k for this lane: the generic kernels' table path (records in sC / sI)
+__device__ __forceinline__ double cf_extinction(const CfArgs &p, const double *sC, const idx_t *sI, int k, int ii,
+                                                double nu4) {
+  const int M = p.M, C = p.C;
+  const double *c = sC + (size_t)k * coef_stride(M, C);
+  const idx_t *ix = sI + (size_t)k * idx_stride(C);
+  double e = c[2 + 2 * M + 2 * C] * nu4 + c[3 + 2 * M + 2 * C];  // Rayleigh + grey cloud
+  // grid [plane][W][M], CIA [pair plane][W][2] (kernels.hpp, "Table layout")
+  const double *kb = reinterpret_cast<const double *>(reinterpret_cast<const char *>(p.kappa) + ix[0]) + (size_t)ii * M;
+  const size_t MW = (size_t)M * p.W;
+  for (int m = 0; m < M; m++) e += c[2 + 2 * m] * kb[m] + c[3 + 2 * m] * kb[MW + m];
+  for (int cc = 0; cc < C; cc++) {
+    const double *ab = reinterpret_cast<const double *>(reinterpret_cast<const char *>(p.cia) + ix[1 + cc]) + 2 * (size_t)ii;
+    e += c[2 + 2 * M + 2 * cc] * ab[0] + c[3 + 2 * M + 2 * cc] * ab[1];
+  }
+  return e;
+}
+
+// Layers k0 .. k0 + nk - 1 are in blk[j][lane]: one partial per overlapping filter and layer, and the full output.
+__device__ __forceinline__ void cf_flush(const CfArgs &p, const double *blk, int tile, int w, int k0, int nk) {
+  __syncthreads();
+  const int lane = threadIdx.x, j = lane & 15, q = lane >> 4;
+  const int e1 = p.tile_ptr[tile + 1];
+  for (int e = p.tile_ptr[tile]; e < e1; e++) {
+    const double *wr = p.wt + (size_t)e * 64 + 16 * q;
+    const double *row = blk + j * kCfPitch + 16 * q;
+    double s = 0.0;
+#pragma unroll
+    for (int t = 0; t < 16; t++) s = fma(row[t], wr[t], s);
+    s += __shfl_xor(s, 16);   // (q0 + q1), (q2 + q3)
+    s += __shfl_xor(s, 32);   // (q0 + q1) + (q2 + q3)
+    if (q == 0 && j < nk) p.part[((size_t)w * p.nent + e) * p.L + k0 + j] = s;
+  }
+  if (p.full && j < nk) {
+    const int L = p.L;
+    double *out = p.full + (size_t)w * p.W * L + (L - 1 - (k0 + j));
+    for (int r = q; r < 64; r += 4) {
+      const int i = tile * 64 + r;
+      if (i < p.W) out[(size_t)i * L] = blk[j * kCfPitch + r];
+    }
+  }
+  __syncthreads();
+}
+
+template <int INTEG>
+__global__ __launch_bounds__(64) void cf_eclipse(CfArgs p) {
+  extern __shared__ double smem[];
+  const int L = p.L, NC = coef_stride(p.M, p.C), NI = idx_stride(p.C);
+  int tile, w;
+  cf_block_to_work(blockIdx.x, p.nwalkers, tile, w);
+  if (tile >= p.ntiles) return;
+  double *sC = smem;
+  idx_t *sI = reinterpret_cast<idx_t *>(smem + (size_t)L * NC);
+  double *sW = smem + (size_t)L * NC + (size_t)L * NI;  // rule 1 only
+  double *blk = sW + (INTEG == kIntegSimpson ? simpson_lds_doubles(L) : 0);
+  stage2_to_lds(sC, p.coef + (size_t)w * L * NC, L * NC, sI, p.idx + (size_t)w * L * NI, L * NI, threadIdx.x, 64);
+  __syncthreads();
+  if (INTEG == kIntegSimpson) {
+    simpson_radius_weights(sW, sC, NC, L, threadIdx.x, 64);
+    __syncthreads();
+  }
+  const int i = tile * 64 + threadIdx.x;
+  const bool valid = i < p.W;
+  const int ii = valid ? i : p.W - 1;  // keep every lane's loads in range
+  const double nu = p.wn[ii];
+  const double bnum = 2.0 * kH * nu * nu * nu * kLS * kLS;
+  const double nu4 = (nu * nu) * (nu * nu);
+  const int kend = kstop_layer(p.kstop[w]);  // below it (a cloud deck) the optical depth repeats
+  TauColumn<INTEG> tc;
+  double Eprev = 1.0;
+  for (int k = 0; k < L; k++) {
+    if (k <= kend) tc.layer(k, true, 0.5, cf_extinction(p, sC, sI, k, ii, nu4), sC[(size_t)k * NC], sW);
+    const double E = exp_rt(fmax(-tc.tau, kExpMin));
+    double v = E;
+    if (p.kind == kCfContrib) {
+      const double B = bnum * rcp_n1(exp_rt(fmin(sC[(size_t)k * NC + 1] * nu, 700.0)) - 1.0);
+      v = k == 0 ? 0.0 : B * (Eprev - E) * p.rdlp[k];
+    }
+    Eprev = E;
+    blk[(k & (kCfRows - 1)) * kCfPitch + threadIdx.x] = valid ? v : 0.0;
+    if ((k & (kCfRows - 1)) == kCfRows - 1 || k == L - 1) cf_flush(p, blk, tile, w, k & ~(kCfRows - 1), (k & (kCfRows - 1)) + 1);
+  }
+}
+
+// STAGE: the layer records in LDS (without: read where they lie, for deep columns whose pair sums fill LDS)
+template <bool STAGE>
+__global__ __launch_bounds__(64) void cf_transit(CfArgs p) {
+  extern __shared__ double smem[];
+  const int L = p.L, NC = coef_stride(p.M, p.C), NI = idx_stride(p.C);
+  int tile, w;
+  cf_block_to_work(blockIdx.x, p.nwalkers, tile, w);
+  if (tile >= p.ntiles) return;
+  const double *gC = p.coef + (size_t)w * L * NC;
+  const idx_t *gI = p.idx + (size_t)w * L * NI;
+  const size_t nrec = STAGE ? (size_t)L * NC + (size_t)L * NI : 0;
+  double *sP = smem + nrec;              // pair sums e_{j-1} + e_j, [L][64]
+  double *blk = sP + (size_t)L * 64;
+  const double *sC = gC;
+  const idx_t *sI = gI;
+  if constexpr (STAGE) {
+    double *lC = smem;
+    idx_t *lI = reinterpret_cast<idx_t *>(smem + (size_t)L * NC);
+    stage2_to_lds(lC, gC, L * NC, lI, gI, L * NI, threadIdx.x, 64);
+    __syncthreads();
+    sC = lC;
+    sI = lI;
+  }
+  const int i = tile * 64 + threadIdx.x;
+  const bool valid = i < p.W;
+  const int ii = valid ? i : p.W - 1;
+  const double nu = p.wn[ii];
+  const double nu4 = (nu * nu) * (nu * nu);
+  const double *dsw = p.ds + (size_t)w * chord_table_size(L);
+  const int kend = kstop_layer(p.kstop[w]);
+  double eprev = 0.0, tau = 0.0;
+  for (int k = 0; k < L; k++) {
+    if (k <= kend) {
+      const double e = cf_extinction(p, sC, sI, k, ii, nu4);
+      if (k > 0) {
+        sP[(size_t)k * 64 + threadIdx.x] = eprev + e;
+        const double *dk = dsw + chord_table_index(L, k, 0);   // + (j / 4) * 64 + (j % 4) * 16 per layer j
+        double t = 0.0;
+        for (int j = 1; j <= k; j++) t = fma(sP[(size_t)j * 64 + threadIdx.x], dk[(j >> 2) * 64 + (j & 3) * 16], t);
+        tau = t;
+      }
+      eprev = e;
+    }
+    blk[(k & (kCfRows - 1)) * kCfPitch + threadIdx.x] = valid ? exp_rt(fmax(-tau, kExpMin)) : 0.0;
+    if ((k & (kCfRows - 1)) == kCfRows - 1 || k == L - 1) cf_flush(p, blk, tile, w, k & ~(kCfRows - 1), (k & (kCfRows - 1)) + 1);
+  }
+}
+
+// band[w][f][L - 1 - k] = sum over the filter's entries (tile order) of part[w][e][k] / trapz(resp_f); NaN for a
+// walker whose profile prep_profiles flagged
+__global__ __launch_bounds__(256) void cf_finish(const double *part, int nwalkers, int nf, int nent, int L,
+                                                 const int *f_ptr, const int *f_ent, const double *trapz,
+                                                 const unsigned char *ok, double *band) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)nwalkers * nf * L) return;
+  const int k = (int)(t % L);
+  const int f = (int)((t / L) % nf);
+  const int w = (int)(t / ((size_t)L * nf));
+  double s = 0.0;
+  for (int j = f_ptr[f]; j < f_ptr[f + 1]; j++) s += part[((size_t)w * nent + f_ent[j]) * L + k];
+  band[((size_t)w * nf + f) * L + (L - 1 - k)] = ok[w] ? s / trapz[f] : __builtin_nan("");
+}
+
+// ---- host state: the filter tables and the workspaces, owned here (not by Engine) ----
+struct CfState {
+  const Engine *eng = nullptr;   // the engine the tables were built for
+  int nf = 0, L = 0, W = 0, ntiles = 0, nent = 0;
+  int *d_tile_ptr = nullptr, *d_f_ptr = nullptr, *d_f_ent = nullptr;
+  double *d_wt = nullptr, *d_trapz = nullptr, *d_rdlp = nullptr;
+  // per-walker workspaces of one chunk of walkers
+  int cap = 0;
+  double *d_coef = nullptr, *d_rtop = nullptr, *d_ds = nullptr, *d_part = nullptr;
+  idx_t *d_idx = nullptr;
+  int *d_kstop = nullptr;
+  unsigned char *d_ok = nullptr;
+  // staging of the host-buffer call
+  size_t stage_bytes = 0;
+  char *d_stage = nullptr;
+  hipStream_t last_stream = nullptr;  // the workspaces' latest user
+};
+CfState g;
+
+template <class T>
+void cf_free(T *&p) {
+  if (p) (void)hipFree(p);
+  p = nullptr;
+}
+
+template <class T>
+void cf_alloc(T *&p, size_t count) {
+  cf_free(p);
+  HIPCHK(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
+}
+
+template <class T>
+T *cf_upload(const std::vector<T> &v) {
+  T *p = nullptr;
+  cf_alloc(p, v.size());
+  if (!v.empty()) HIPCHK(hipMemcpy(p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
+  return p;
+}
+
+void free_tables() {
+  cf_free(g.d_tile_ptr); cf_free(g.d_f_ptr); cf_free(g.d_f_ent);
+  cf_free(g.d_wt); cf_free(g.d_trapz); cf_free(g.d_rdlp);
+  g.eng = nullptr;
+  g.nf = g.nent = 0;
+}
+
+void free_workspace() {
+  cf_free(g.d_coef); cf_free(g.d_rtop); cf_free(g.d_ds); cf_free(g.d_part);
+  cf_free(g.d_idx); cf_free(g.d_kstop); cf_free(g.d_ok);
+  cf_free(g.d_stage);
+  g.cap = 0;
+  g.stage_bytes = 0;
+  g.last_stream = nullptr;
+}
+
+// Bytes of the workspaces (partials, layer records, chord tables) a chunk may hold: BARTRT_CF_WORKSPACE_BYTES,
+// default 256 MiB.  Read per call.
+size_t workspace_cap() {
+  const char *c = std::getenv("BARTRT_CF_WORKSPACE_BYTES");
+  return c && *c ? std::max<size_t>(1, std::strtoull(c, nullptr, 10)) : (size_t)256 << 20;
+}
+
+size_t per_walker_bytes(const Engine &e) {
+  size_t b = sizeof(double) * (size_t)g.nent * e.L + sizeof(double) * (size_t)e.L * coef_stride(e.M, e.C) +
+             sizeof(idx_t) * (size_t)e.L * idx_stride(e.C) + sizeof(int) + 1;
+  if (e.solution == 1) b += sizeof(double) * ((size_t)e.L + chord_table_size(e.L));
+  return b;
+}
+
+// a stream other than the previous call's may not reuse the workspaces while that call still runs
+void claim(hipStream_t st) {
+  if (g.last_stream && g.last_stream != st) HIPCHK(hipStreamSynchronize(g.last_stream));
+  g.last_stream = st;
+}
+
+void ensure_cap(const Engine &e, int n) {
+  if (n <= g.cap) return;
+  HIPCHK(hipDeviceSynchronize());   // (an earlier launch on any stream may still use the old buffers)
+  cf_alloc(g.d_coef, (size_t)n * e.L * coef_stride(e.M, e.C));
+  cf_alloc(g.d_idx, (size_t)n * e.L * idx_stride(e.C));
+  cf_alloc(g.d_kstop, (size_t)n);
+  cf_alloc(g.d_ok, (size_t)n);
+  cf_alloc(g.d_part, (size_t)n * g.nent * e.L);
+  if (e.solution == 1) {
+    cf_alloc(g.d_rtop, (size_t)n * e.L);
+    cf_alloc(g.d_ds, (size_t)n * chord_table_size(e.L));
+  }
+  g.cap = n;
+}
+
+void check_ready(const Engine &e, int kind) {
+  if (kind != kCfContrib && kind != kCfTransmit) throw std::invalid_argument("cf: kind must be BARTRT_CF_CONTRIB or BARTRT_CF_TRANSMIT");
+  if (!g.eng || g.eng != &e || g.L != e.L || g.W != e.W()) throw std::invalid_argument("cf: call bartrt_cf_setup first");
+}
+
+template <class K>
+void allow_lds(K kernel, size_t bytes) {
+  if (bytes > 160 * 1024) throw std::invalid_argument("cf: the column's layer records and sums do not fit in LDS (160 kB)");
+  if (bytes > 64 * 1024)
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+}
+
+// one chunk: m walkers whose flags go to okp
+void run_chunk(Engine &e, const double *d_prof, int m, int kind, double *d_band, double *d_full, unsigned char *okp,
+               hipStream_t st) {
+  // the layer records under the engine's settings, as run_transit_batch builds them, into this module's buffers
+  // (no radii output, no per-walker overrides: the engine's own state is left as it was)
+  PrepArgs pa = e.prep;
+  pa.nwalkers = m;
+  pa.prof = d_prof;
+  pa.gsurf = e.gsurf; pa.refradius = e.refradius;
+  pa.scat_flag = e.scat_flag; pa.scat_value = e.scat_value;
+  pa.has_cloud = e.has_cloud; pa.cloudtop = e.cloudtop;
+  pa.cloud_rup = e.cloud_rup; pa.cloud_rdown = e.cloud_rdown; pa.cloud_ext = e.cloud_ext;
+  pa.coef = g.d_coef; pa.idx = g.d_idx; pa.kstop = g.d_kstop; pa.ok = okp;
+  pa.rad_out = nullptr;
+  pa.over = nullptr;
+  pa.rtop = e.solution == 1 ? g.d_rtop : nullptr;
+  pa.ds = e.solution == 1 ? g.d_ds : nullptr;
+  HIPCHK(launch_prep(pa, st));
+  if (e.solution == 1) HIPCHK(launch_chord_table(pa, st));
+
+  CfArgs a{};
+  a.L = e.L; a.M = e.M; a.C = e.C; a.W = e.W(); a.nwalkers = m; a.ntiles = g.ntiles; a.kind = kind; a.nent = g.nent;
+  a.kappa = e.rt.kappa; a.cia = e.rt.cia; a.wn = e.rt.wn;
+  a.coef = g.d_coef; a.idx = g.d_idx; a.kstop = g.d_kstop;
+  a.rdlp = g.d_rdlp;
+  a.rtop = g.d_rtop; a.ds = g.d_ds;
+  a.tile_ptr = g.d_tile_ptr; a.wt = g.d_wt;
+  a.part = g.d_part; a.full = d_full;
+  const int nblocks = (g.ntiles + 7) / 8 * 8 * m;
+  const size_t L = e.L, NC = coef_stride(e.M, e.C), NI = idx_stride(e.C), blk = (size_t)kCfRows * kCfPitch;
+  if (e.solution == 1) {
+    const size_t with = sizeof(double) * (L * NC + L * NI + L * 64 + blk), without = sizeof(double) * (L * 64 + blk);
+    if (with <= 160 * 1024) {
+      allow_lds(cf_transit<true>, with);
+      hipLaunchKernelGGL(cf_transit<true>, dim3(nblocks), dim3(64), with, st, a);
+    } else {
+      allow_lds(cf_transit<false>, without);
+      hipLaunchKernelGGL(cf_transit<false>, dim3(nblocks), dim3(64), without, st, a);
+    }
+  } else {
+    const size_t base = sizeof(double) * (L * NC + L * NI + blk);
+    const size_t simp = base + sizeof(double) * simpson_lds_doubles(e.L);
+    switch (e.integ) {
+      case kIntegTransmittance:
+        allow_lds(cf_eclipse<kIntegTransmittance>, base);
+        hipLaunchKernelGGL(cf_eclipse<kIntegTransmittance>, dim3(nblocks), dim3(64), base, st, a);
+        break;
+      case kIntegSimpson:
+        allow_lds(cf_eclipse<kIntegSimpson>, simp);
+        hipLaunchKernelGGL(cf_eclipse<kIntegSimpson>, dim3(nblocks), dim3(64), simp, st, a);
+        break;
+      default:
+        allow_lds(cf_eclipse<kIntegTrapzTau>, base);
+        hipLaunchKernelGGL(cf_eclipse<kIntegTrapzTau>, dim3(nblocks), dim3(64), base, st, a);
+        break;
+    }
+  }
+  HIPCHK(hipGetLastError());
+  const size_t nout = (size_t)m * g.nf * e.L;
+  hipLaunchKernelGGL(cf_finish, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, g.d_part, m, g.nf, g.nent,
+                     e.L, g.d_f_ptr, g.d_f_ent, g.d_trapz, okp, d_band);
+  HIPCHK(hipGetLastError());
+}
+
+}  // namespace
+
+void cf_setup(Engine &e, int nf, const int *idx0, const int *npts, const double *resp) {
+  if (nf < 1 || !idx0 || !npts || !resp) throw std::invalid_argument("cf_setup: no filters");
+  const int W = e.W(), L = e.L;
+  std::vector<double> trapz(nf);
+  std::vector<size_t> off(nf + 1, 0);
+  for (int f = 0; f < nf; f++) {
+    if (npts[f] < 2 || idx0[f] < 0 || (long)idx0[f] + npts[f] > W)
+      throw std::invalid_argument("cf_setup: filter " + std::to_string(f) + " needs a window of at least two samples inside the grid");
+    off[f + 1] = off[f] + npts[f];
+  }
+  // trapz(resp) with unit spacing (np.trapz without x): half weights at the window's ends
+  auto weight = [&](int f, int s) { return (s == 0 || s == npts[f] - 1 ? 0.5 : 1.0) * resp[off[f] + s]; };
+  for (int f = 0; f < nf; f++) {
+    double t = 0.0;
+    for (int s = 0; s + 1 < npts[f]; s++) t += 0.5 * (resp[off[f] + s] + resp[off[f] + s + 1]);
+    if (!std::isfinite(t) || t == 0.0)
+      throw std::invalid_argument("cf_setup: filter " + std::to_string(f) + " has no response inside the grid");
+    trapz[f] = t;
+  }
+  const int ntiles = (W + 63) / 64;
+  std::vector<int> tile_ptr(ntiles + 1, 0), ent_f;
+  std::vector<double> wt;
+  for (int t = 0; t < ntiles; t++) {
+    for (int f = 0; f < nf; f++) {
+      const int a = std::max(idx0[f], 64 * t), b = std::min(idx0[f] + npts[f], 64 * t + 64);
+      if (a >= b) continue;
+      ent_f.push_back(f);
+      const size_t at = wt.size();
+      wt.resize(at + 64, 0.0);
+      for (int i = a; i < b; i++) wt[at + (i - 64 * t)] = weight(f, i - idx0[f]);
+    }
+    tile_ptr[t + 1] = (int)ent_f.size();
+  }
+  const int nent = (int)ent_f.size();
+  std::vector<int> f_ptr(nf + 1, 0), f_ent;
+  for (int f = 0; f < nf; f++) {
+    for (int j = 0; j < nent; j++)
+      if (ent_f[j] == f) f_ent.push_back(j);   // entries are tile-major: ascending j is tile order
+    f_ptr[f + 1] = (int)f_ent.size();
+  }
+  // 1 / (ln p_k - ln p_{k-1}), k from the top (cf_eq's d_logp, code/cf.py:130)
+  std::vector<double> rdlp(L, 0.0);
+  for (int k = 1; k < L; k++) rdlp[k] = 1.0 / (std::log(e.atm.press[L - 1 - k]) - std::log(e.atm.press[L - k]));
+
+  HIPCHK(hipDeviceSynchronize());   // (a CF launch may still read the old tables)
+  free_tables();
+  if (g.cap && nent != g.nent) free_workspace();   // partials are sized by the entry count
+  g.d_tile_ptr = cf_upload(tile_ptr);
+  g.d_f_ptr = cf_upload(f_ptr);
+  g.d_f_ent = cf_upload(f_ent);
+  g.d_wt = cf_upload(wt);
+  g.d_trapz = cf_upload(trapz);
+  g.d_rdlp = cf_upload(rdlp);
+  g.nf = nf; g.nent = nent; g.L = L; g.W = W; g.ntiles = ntiles;
+  g.eng = &e;
+}
+
+int cf_nfilters() { return g.eng ? g.nf : 0; }
+
+void cf_run_dev(Engine &e, const double *d_prof, int n, int kind, double *d_band, double *d_full, unsigned char *d_ok,
+                hipStream_t st) {
+  check_ready(e, kind);
+  if (n <= 0) return;
+  const int nprof = (e.S + 1) * e.L;
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, workspace_cap() / per_walker_bytes(e)));
+  ensure_cap(e, chunk);
+  claim(st);
+  for (int off = 0; off < n; off += chunk) {
+    const int m = std::min(chunk, n - off);
+    run_chunk(e, d_prof + (size_t)off * nprof, m, kind, d_band + (size_t)off * g.nf * e.L,
+              d_full ? d_full + (size_t)off * e.W() * e.L : nullptr, d_ok ? d_ok + off : g.d_ok, st);
+  }
+}
+
+void cf_run_host(Engine &e, const double *prof, int n, int kind, double *band, double *full, unsigned char *ok) {
+  check_ready(e, kind);
+  if (n <= 0) return;
+  const int nprof = (e.S + 1) * e.L;
+  const size_t bprof = sizeof(double) * nprof, bband = sizeof(double) * (size_t)g.nf * e.L,
+               bfull = full ? sizeof(double) * (size_t)e.W() * e.L : 0;
+  // the staging buffers and the workspaces of a chunk share the cap
+  const size_t per = per_walker_bytes(e) + bprof + bband + bfull + 1;
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, workspace_cap() / per));
+  ensure_cap(e, chunk);
+  const size_t need = (size_t)chunk * (bprof + bband + bfull) + chunk;
+  if (need > g.stage_bytes) {
+    HIPCHK(hipDeviceSynchronize());
+    cf_alloc(g.d_stage, need);
+    g.stage_bytes = need;
+  }
+  hipStream_t st = e.stream;
+  claim(st);
+  char *base = g.d_stage;
+  double *dp = reinterpret_cast<double *>(base);
+  double *db = reinterpret_cast<double *>(base + (size_t)chunk * bprof);
+  double *df = full ? reinterpret_cast<double *>(base + (size_t)chunk * (bprof + bband)) : nullptr;
+  unsigned char *dok = reinterpret_cast<unsigned char *>(base + (size_t)chunk * (bprof + bband + bfull));
+  std::vector<unsigned char> hok(chunk);
+  for (int off = 0; off < n; off += chunk) {
+    const int m = std::min(chunk, n - off);
+    HIPCHK(hipMemcpyAsync(dp, prof + (size_t)off * nprof, bprof * m, hipMemcpyHostToDevice, st));
+    run_chunk(e, dp, m, kind, db, df, dok, st);
+    HIPCHK(hipMemcpyAsync(band + (size_t)off * g.nf * e.L, db, bband * m, hipMemcpyDeviceToHost, st));
+    if (full) HIPCHK(hipMemcpyAsync(full + (size_t)off * e.W() * e.L, df, bfull * m, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hok.data(), dok, (size_t)m, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (ok) std::copy(hok.begin(), hok.begin() + m, ok + off);
+    else
+      for (int w = 0; w < m; w++)
+        if (!hok[w]) throw std::invalid_argument("cf: profile " + std::to_string(off + w) + " holds a non-finite or non-positive temperature");
+  }
+}
+
+void cf_release() {
+  free_tables();
+  free_workspace();
+}
+
+}  // namespace bartrt

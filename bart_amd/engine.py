@@ -10,6 +10,7 @@ converters of code/BARTfunc.py:309-399 on the device.
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -358,6 +359,19 @@ def step_batch_dev(d_params, nfilters, want_spec=False, stream=None):
     return (band, status, spec) if want_spec else (band, status)
 
 
+def step_profiles_dev(d_params, stream=None):
+    """Profiles [n, (S+1)*L] and status [n] of parameter vectors [n, npars] on the device (after step_setup;
+    include/bartrt.h, bartrt_step_profiles_dev): the input of run_batch_dev / contribution_dev."""
+    import torch
+    n, npars = d_params.shape
+    prof = torch.empty((n, nprof()), dtype=torch.float64, device=d_params.device)
+    status = torch.empty(n, dtype=torch.int32, device=d_params.device)
+    _check(trm.lib().bartrt_step_profiles_dev(
+        C.c_void_p(d_params.data_ptr()), n, npars, C.c_void_p(prof.data_ptr()),
+        C.c_void_p(status.data_ptr()), _stream_ptr(stream)))
+    return prof, status
+
+
 def step_batch_sharded(d_params, nfilters, group=None, stream=None, force=False):
     """Per-step callable on a wavenumber-sharded node: profiles on every rank,
     RT on the local block, all-gather, band integration on the full grid.
@@ -408,3 +422,91 @@ def walked_end():
 
 def algorithmic_bytes(nwalkers: int) -> float:
     return trm.lib().bartrt_algorithmic_bytes(int(nwalkers))
+
+
+# ---- contribution functions / band transmittance (include/bartrt.h, bartrt_cf_*) --------------
+CF_CONTRIB, CF_TRANSMIT = 0, 1
+_cf_nfilters = 0     # filters of the latest cf_setup (the band tensors' middle axis)
+
+
+def cf_setup(filters) -> int:
+    """The filter windows of the batched contribution-function calls: a list of filter files (read and
+    windowed on the engine's grid by bart_amd.cf.filter_windows) or the (idx0, npts, resp, trapz) that
+    function returns.  Kept by the engine until the next cf_setup / init / free_memory.  -> nfilters."""
+    if isinstance(filters, tuple) and len(filters) == 4 and not isinstance(filters[0], (str, bytes, os.PathLike)):
+        idx0, npts, resp, _ = filters
+    else:
+        from .cf import filter_windows
+        idx0, npts, resp, _ = filter_windows(trm.get_waveno_arr(trm.get_no_samples()), list(filters))
+    idx0, npts = np.ascontiguousarray(idx0, np.int32), np.ascontiguousarray(npts, np.int32)
+    resp = np.ascontiguousarray(resp, np.double)
+    assert idx0.size == npts.size and resp.size == int(npts.sum())
+    global _cf_nfilters
+    _check(trm.lib().bartrt_cf_setup(idx0.size, _ptr(idx0), _ptr(npts), _ptr(resp)))
+    _cf_nfilters = int(idx0.size)
+    return _cf_nfilters
+
+
+def _cf_batch(profiles, filters, kind, full, want_ok):
+    prof = np.ascontiguousarray(profiles, np.double).reshape(-1, nprof())
+    nf = cf_setup(filters)
+    n, L, W = prof.shape[0], nlayers(), trm.get_no_samples()
+    band = np.zeros((n, nf, L))
+    fout = np.zeros((n, W, L)) if full else None
+    ok = np.zeros(n, np.uint8)
+    _check(trm.lib().bartrt_cf_batch(_ptr(prof), n, prof.shape[1], kind, _ptr(band),
+                                     _ptr(fout) if full else None, _ptr(ok) if want_ok else None))
+    return band, fout, ok
+
+
+def contribution(profiles, filters, normalize=True, full=False, want_ok=False):
+    """Band-averaged contribution functions of a batch (cf.cf's result per walker; eclipse geometry):
+    profiles [nwalkers, (S+1)*L] as run_batch, filters as cf_setup ->
+    filt_cf [nwalkers, nfilters, L] in atm layer order, then (normalize) filt_cf_norm of the same shape,
+    then (full) the per-wavenumber values [nwalkers, W, L], then (want_ok) the walkers' flags -- without
+    want_ok a non-finite profile raises; with it, that walker's rows are NaN.  A single array is returned
+    bare, several as a tuple."""
+    from .cf import normalize as _norm
+    band, fout, ok = _cf_batch(profiles, filters, CF_CONTRIB, full, want_ok)
+    out = [band] + ([_norm(band)] if normalize else []) + ([fout] if full else []) + ([ok] if want_ok else [])
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def transmittance(profiles, filters, full=False, want_ok=False):
+    """Band-averaged transmittance exp(-tau) of a batch (cf.transmittance's result per walker; vertical depth
+    on an eclipse engine, chord depth on a transit engine): [nwalkers, nfilters, L] in atm layer order,
+    then (full) [nwalkers, W, L], then (want_ok) the flags, as contribution()."""
+    band, fout, ok = _cf_batch(profiles, filters, CF_TRANSMIT, full, want_ok)
+    out = [band] + ([fout] if full else []) + ([ok] if want_ok else [])
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def _cf_batch_dev(d_prof, kind, full, d_ok, stream):
+    import torch
+    assert d_prof.is_cuda and d_prof.dtype == torch.float64 and d_prof.is_contiguous()
+    n, L = d_prof.shape[0], nlayers()
+    if not _cf_nfilters:
+        raise trm.TransitError("contribution_dev / transmittance_dev: call engine.cf_setup(filters) first")
+    nf = _cf_nfilters
+    band = torch.empty((n, nf, L), dtype=torch.float64, device=d_prof.device)
+    fout = torch.empty((n, trm.get_no_samples(), L), dtype=torch.float64, device=d_prof.device) if full else None
+    if d_ok is not None:
+        assert d_ok.is_cuda and d_ok.dtype == torch.uint8 and d_ok.numel() >= n
+    _check(trm.lib().bartrt_cf_batch_dev(
+        C.c_void_p(d_prof.data_ptr()), n, kind, C.c_void_p(band.data_ptr()),
+        C.c_void_p(fout.data_ptr()) if full else None, C.c_void_p(d_ok.data_ptr()) if d_ok is not None else None,
+        _stream_ptr(stream)))
+    return (band, fout) if full else band
+
+
+def contribution_dev(d_prof, full=False, d_ok=None, stream=None):
+    """Device form of contribution() for the filters of the latest cf_setup: d_prof a float64 CUDA tensor
+    [nwalkers, (S+1)*L] (run_batch_dev's input, e.g. from bartrt_step_profiles_dev) -> band tensor
+    [nwalkers, nfilters, L] (atm layer order; not normalised), and [nwalkers, W, L] with ``full``.
+    Asynchronous on torch's current stream; d_ok (uint8 [nwalkers]) receives the flags (flagged rows: NaN)."""
+    return _cf_batch_dev(d_prof, CF_CONTRIB, full, d_ok, stream)
+
+
+def transmittance_dev(d_prof, full=False, d_ok=None, stream=None):
+    """Device form of transmittance(), as contribution_dev."""
+    return _cf_batch_dev(d_prof, CF_TRANSMIT, full, d_ok, stream)

@@ -105,6 +105,9 @@ def lib():
         L.bartrt_prefetch_profiles_dev.argtypes = [C.c_void_p, i]
         L.bartrt_get_integ.argtypes = [C.POINTER(i)]
         L.bartrt_walked_end.argtypes = [p, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.c_char_p, i]
+        L.bartrt_cf_setup.argtypes = [i, p, p, p]
+        L.bartrt_cf_batch.argtypes = [p, i, i, i, p, p, p]
+        L.bartrt_cf_batch_dev.argtypes = [p, i, i, p, p, p, p]
         L.bartrt_algorithmic_bytes.argtypes = [i]
         L.bartrt_algorithmic_bytes.restype = d
         _lib = L

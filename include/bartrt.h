@@ -315,6 +315,49 @@ int bartrt_get_angles(double *deg, int n);
 int bartrt_get_intensity(double *intens, int nangles, int nwave);
 int bartrt_get_intensity_of(int walker, double *intens, int nangles, int nwave);  /* as bartrt_get_tau_of */
 
+/* Band-averaged contribution functions and transmittance of a batch of profiles: BART's
+ * post-processing (code/cf.py:114-199, called at BART.py:626-644) on the optical depth
+ * bartrt_get_tau_of would return for each walker with `toomuch` infinite -- the engine's
+ * own `toomuch` and `cut` have no effect; below a cloud deck's layer the depth repeats.
+ * With tau[k] from the top (k = 0 the top layer):
+ *   BARTRT_CF_CONTRIB   cf[k] = B(T_k, nu) (exp(-tau[k-1]) - exp(-tau[k])) / (ln p_k - ln p_{k-1}),
+ *                       cf[0] = 0 (cf_eq; the vertical depth under the rule in force) --
+ *                       eclipse geometry only (BARTRT_ENOTSUP on a transit engine);
+ *   BARTRT_CF_TRANSMIT  exp(-tau[k]) (eclipse: vertical depth; transit: chord depth at r_k).
+ * Per filter f the band value is trapz(x resp) / trapz(resp) with UNIT spacing over the
+ * filter's window (filter_cf: np.trapz without x, half weights at the window's two ends).
+ * Normalisation (filt_cf_norm) is left to the caller (bart_amd.engine.contribution).
+ *
+ * bartrt_cf_setup: the filter windows on the FULL grid: filter f covers samples idx0[f] ..
+ * idx0[f] + npts[f] - 1 (at least two, inside the grid) with the filter's response already
+ * interpolated onto them, resp = the nfilters windows concatenated (bart_amd.cf.filter_windows
+ * builds them as filter_cf does: the samples strictly inside the filter's wavenumber range).
+ * Kept until the next setup, bartrt_init or bartrt_free_memory.
+ *
+ * bartrt_cf_batch: prof[nwalkers][nprof] as bartrt_run_transit_batch ->
+ * band[nwalkers][nfilters][nlayers] in atm layer order (what cf.cf / cf.transmittance return,
+ * per walker); full[nwalkers][nwave][nlayers] (atm layer order: the per-wavenumber values,
+ * cf_eq's array transposed) or NULL.  ok[nwalkers] as bartrt_run_transit_batch (a flagged
+ * walker's band rows are NaN); with ok NULL a flagged profile fails the call.
+ * bartrt_cf_batch_dev: the same on device buffers, asynchronous on `stream` (NULL: the
+ * engine's own); d_ok may be NULL.
+ *
+ * The engine-wide setters (radius, cloud top, scattering) apply as to run_transit_batch;
+ * there are no per-walker radius / cloud / scattering parameters inside one batch.  A call
+ * leaves the engine's other state alone: the profile behind bartrt_get_tau /
+ * _get_intensity, a pending bartrt_prefetch_profiles_dev request, the timing and
+ * walked-layer records, bartrt_get_radius.  Results are bit-identical from run to run and
+ * do not depend on which other walkers share the call.  Internally the walkers go in chunks
+ * whose workspace stays under BARTRT_CF_WORKSPACE_BYTES (default 256 MiB).
+ * BARTRT_ENOTSUP: line-by-line engines, sharded engines (--shard), chain-service clients. */
+#define BARTRT_CF_CONTRIB  0
+#define BARTRT_CF_TRANSMIT 1
+int bartrt_cf_setup(int nfilters, const int *idx0, const int *npts, const double *resp);
+int bartrt_cf_batch(const double *prof, int nwalkers, int nprof, int kind,
+                    double *band, double *full, unsigned char *ok);
+int bartrt_cf_batch_dev(const double *d_prof, int nwalkers, int kind,
+                        double *d_band, double *d_full, unsigned char *d_ok, void *stream);
+
 /* Line-by-line engines only (cfg has `linedb`, no `opacityfile`): the Voigt
  * extinction of one profile, ext[nlayers][nwave_local] in cm-1, atm layer order. */
 int bartrt_get_lbl_extinction(const double *prof, int nprof, double *ext,
