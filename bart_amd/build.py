@@ -10,10 +10,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbartrt.so")
 CLI = os.path.join(HERE, "transit")
-SOURCES = ["rt_eclipse_angles.hip", "rt_eclipse_slant_ilp.hip", "rt_eclipse_qadj.hip", "rt_eclipse_team.hip", "rt_eclipse_i0.hip", "rt_eclipse_i1.hip", "rt_eclipse_i2.hip", "rt_eclipse_i0_ilp.hip", "rt_eclipse_i1_ilp.hip", "lbl.hip",
+SOURCES = ["rt_eclipse_angles.hip", "rt_eclipse_slant_ilp.hip", "rt_eclipse_qadj.hip", "rt_eclipse_i0.hip", "rt_eclipse_i1.hip", "rt_eclipse_i2.hip", "rt_eclipse_i0_ilp.hip", "rt_eclipse_i1_ilp.hip", "lbl.hip",
            "transit_geom.hip", "contrib.hip",
            "kernels.hip", "capi.hip", "engine.hip", "step.hip", "mcmc.hip", "share.hip", "svc.hip", "rtc.hip", "io.cpp"]   # longest first
-HEADERS = ["engine.hpp", "kernels.hpp", "rt_eclipse.hpp", "rt_eclipse_s1.hpp", "rt_eclipse_s1s.hpp", "rt_eclipse_s1t.hpp", "rt_eclipse_qadj.hpp", "kernel_table.inc", "imw_tab.hpp", "integ.hpp", "step.hpp", "lbl.hpp", "voigt_coef.hpp", "expint_coef.hpp", "prep.hpp", "io.hpp", "share.hpp", "svc.hpp", "svc_core.hpp", "rtc.hpp", "contrib.hpp",
+HEADERS = ["engine.hpp", "kernels.hpp", "rt_eclipse.hpp", "rt_eclipse_s1.hpp", "rt_eclipse_s1s.hpp", "rt_eclipse_qadj.hpp", "kernel_table.inc", "imw_tab.hpp", "integ.hpp", "step.hpp", "lbl.hpp", "voigt_coef.hpp", "expint_coef.hpp", "prep.hpp", "io.hpp", "share.hpp", "svc.hpp", "svc_core.hpp", "rtc.hpp", "contrib.hpp",
            "transit_main.cpp", "../../include/bartrt.h"]
 
 
@@ -80,7 +80,7 @@ def code_id(objs) -> str:
 # the kernel headers embedded in the library as text: csrc/rtc.hip instantiates shapes outside the ahead-of-time set from
 # them with hiprtc (csrc/rtc.hpp)
 RTC_HEADERS = ["kernels.hpp", "integ.hpp", "prep.hpp", "rt_eclipse.hpp", "rt_eclipse_s1.hpp", "rt_eclipse_s1s.hpp",
-               "rt_eclipse_s1t.hpp", "rt_eclipse_qadj.hpp"]
+               "rt_eclipse_qadj.hpp"]
 RTC_INC = os.path.join(CSRC, "rtc_sources.inc")
 
 

@@ -22,19 +22,20 @@
 #include "prep.hpp"
 
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
-#include <string>
+#include <cstring>
 #include <utility>
 
 namespace bartrt {
 
 // specialised kernels, one instantiation set per integration rule (rt_eclipse_i*.hip)
 template <int INTEG>
-bool launch_rt_spec(const RtArgs &a, int block, hipStream_t st, const std::string &kmode, bool force_window,
+bool launch_rt_spec(const RtArgs &a, int block, hipStream_t st, KernelMode mode, bool force_window,
                     bool allow_sq, hipError_t &err, RtLaunchInfo *info, const PrepArgs *fold = nullptr);
-extern template bool launch_rt_spec<0>(const RtArgs &, int, hipStream_t, const std::string &, bool, bool, hipError_t &, RtLaunchInfo *, const PrepArgs *);
-extern template bool launch_rt_spec<1>(const RtArgs &, int, hipStream_t, const std::string &, bool, bool, hipError_t &, RtLaunchInfo *, const PrepArgs *);
-extern template bool launch_rt_spec<2>(const RtArgs &, int, hipStream_t, const std::string &, bool, bool, hipError_t &, RtLaunchInfo *, const PrepArgs *);
+extern template bool launch_rt_spec<0>(const RtArgs &, int, hipStream_t, KernelMode, bool, bool, hipError_t &, RtLaunchInfo *, const PrepArgs *);
+extern template bool launch_rt_spec<1>(const RtArgs &, int, hipStream_t, KernelMode, bool, bool, hipError_t &, RtLaunchInfo *, const PrepArgs *);
+extern template bool launch_rt_spec<2>(const RtArgs &, int, hipStream_t, KernelMode, bool, bool, hipError_t &, RtLaunchInfo *, const PrepArgs *);
 
 __global__ __launch_bounds__(256) void prep_profiles(PrepArgs p) {
   extern __shared__ double sm[];
@@ -231,12 +232,22 @@ static hipError_t launch_rt_t(const RtArgs &a, int block, int nblocks, hipStream
   return hipGetLastError();
 }
 
-static const std::string &rt_kmode() {
-  static const std::string kmode = [] {
-    const char *e = std::getenv("BARTRT_KERNEL");  // generic | mono | split | quad | octo (A/B runs)
-    return std::string(e ? e : "");
+KernelMode rt_kernel_mode() {
+  static const KernelMode mode = [] {
+    const char *e = std::getenv("BARTRT_KERNEL");
+    if (!e || !*e) return KernelMode::kDefault;
+    static const std::pair<const char *, KernelMode> names[] = {
+        {"generic", KernelMode::kGeneric}, {"mono", KernelMode::kMono}, {"mono_occ", KernelMode::kMonoOcc},
+        {"mono_ilp", KernelMode::kMonoIlp}, {"split", KernelMode::kSplit}, {"quad", KernelMode::kQuad},
+        {"octo", KernelMode::kOcto}, {"hexa", KernelMode::kHexa}, {"r32", KernelMode::kR32},
+        {"adj8", KernelMode::kAdj8}, {"adj16", KernelMode::kAdj16}};
+    for (const auto &n : names)
+      if (std::strcmp(e, n.first) == 0) return n.second;
+    std::fprintf(stderr, "libbartrt: BARTRT_KERNEL=%s is not a kernel form (generic, mono, mono_occ, mono_ilp, split, quad, "
+                         "octo, hexa, r32, adj8, adj16); ignored\n", e);
+    return KernelMode::kDefault;
   }();
-  return kmode;
+  return mode;
 }
 static bool rt_force_window() {
   static const bool v = std::getenv("BARTRT_WINDOW") != nullptr;  // windowed addressing on any grid (tests)
@@ -256,9 +267,9 @@ static bool rt_allow_sq() {
 hipError_t launch_rt_folded(const RtArgs &a, const PrepArgs &prep, int block, hipStream_t st, RtLaunchInfo *info, bool *folded) {
   *folded = false;
   static const bool on = [] { const char *e = std::getenv("BARTRT_FOLD"); return !(e && e[0] == '0'); }();
-  if (!on || a.nwalkers <= 0 || a.W <= 0 || a.integ != kIntegSimpson || rt_kmode() == "generic") return hipSuccess;
+  if (!on || a.nwalkers <= 0 || a.W <= 0 || a.integ != kIntegSimpson || rt_kernel_mode() == KernelMode::kGeneric) return hipSuccess;
   hipError_t err = hipSuccess;
-  *folded = launch_rt_spec<1>(a, block, st, rt_kmode(), rt_force_window(), rt_allow_sq(), err, info, &prep);
+  *folded = launch_rt_spec<1>(a, block, st, rt_kernel_mode(), rt_force_window(), rt_allow_sq(), err, info, &prep);
   return *folded ? err : hipSuccess;
 }
 
@@ -268,15 +279,15 @@ hipError_t launch_rt(const RtArgs &a, int block, hipStream_t st, RtLaunchInfo *i
   if (a.integ < 0 || a.integ >= kIntegCount) return hipErrorInvalidValue;
   const int ntiles8 = (a.ntiles + 7) / 8 * 8;
   const int nblocks = ntiles8 * a.nwalkers;
-  const std::string &kmode = rt_kmode();
+  const KernelMode mode = rt_kernel_mode();
   const bool force_window = rt_force_window(), allow_sq = rt_allow_sq();
-  if (kmode != "generic") {
+  if (mode != KernelMode::kGeneric) {
     hipError_t err = hipSuccess;
     bool done = false;
     switch (a.integ) {
-      case kIntegTransmittance: done = launch_rt_spec<0>(a, block, st, kmode, force_window, allow_sq, err, info); break;
-      case kIntegSimpson: done = launch_rt_spec<1>(a, block, st, kmode, force_window, allow_sq, err, info); break;
-      default: done = launch_rt_spec<2>(a, block, st, kmode, force_window, allow_sq, err, info); break;
+      case kIntegTransmittance: done = launch_rt_spec<0>(a, block, st, mode, force_window, allow_sq, err, info); break;
+      case kIntegSimpson: done = launch_rt_spec<1>(a, block, st, mode, force_window, allow_sq, err, info); break;
+      default: done = launch_rt_spec<2>(a, block, st, mode, force_window, allow_sq, err, info); break;
     }
     if (done) return err;
   }

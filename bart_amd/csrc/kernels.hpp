@@ -289,6 +289,14 @@ struct RtLaunchInfo {
   bool rtc = false;         // the kernel was instantiated at run time (rtc.hpp), not taken from the ahead-of-time set
 };
 
+#ifndef __HIPCC_RTC__
+// BARTRT_KERNEL (A/B runs, tests): the eclipse kernel form forced on the launches it can serve (rt_eclipse.hpp,
+// launch_rt_spec) -- generic | mono | mono_occ | mono_ilp | split | quad | octo | hexa | r32 | adj8 | adj16
+enum class KernelMode { kDefault, kGeneric, kMono, kMonoOcc, kMonoIlp, kSplit, kQuad, kOcto, kHexa, kR32, kAdj8, kAdj16 };
+// parsed once per process (kernels.hip); an unknown value is reported on stderr and the default choice applies
+KernelMode rt_kernel_mode();
+#endif
+
 // ---------------------------------------------------------------------------
 // exp(x) for -708 <= x <= 709 (callers clamp) without the special-case selects
 // of the library routine: the integer part n of x / ln2 comes out of one FMA

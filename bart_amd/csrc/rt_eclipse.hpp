@@ -19,7 +19,6 @@
 #ifndef __HIPCC_RTC__
 #include <cmath>
 #include <cstdlib>
-#include <string>
 #include <type_traits>
 #include <utility>
 #endif
@@ -49,8 +48,7 @@ namespace bartrt {
 constexpr long kQuadMaxColumns = 640, kQuadMaxColumnsSimpson = 480;
 // `cut slant`, rules 0 and 2: one ray per lane (rt_eclipse_quad<..., RAYS>) while the launch is a few thousand (walker,
 // wavenumber) pairs -- it redoes the extinction five times over, so on the 1e4-sample grid ONE walker already takes
-// what the single-wave kernel takes (63 against 58 us, +35 us per further walker).  (Rule 1 took this form on the demo
-// shape until the all-rays form below got 16 and 32 rows: one walker 25.1 us against 15.3.)
+// what the single-wave kernel takes (63 against 58 us, +35 us per further walker).
 constexpr long kQuadRaysMaxColumns = 80;
 constexpr long kOctoRaysMaxColumns = 40;
 // rule 1 under `cut slant`: all rays per lane in the layer-parallel walk (rt_eclipse_quad<..., ALLR>), R = 32 / 16 / 8
@@ -62,7 +60,7 @@ constexpr long kOctoRaysMaxColumns = 40;
 //     one ray per lane, R = 8: 25.1 36.6 48.9 60.3 73.0
 //   bench shape at W = 5 000, walkers 1 .. 3 = 79 / 158 / 237 columns
 //     R = 32: 29.4 40.8 56.8   R = 16: 25.3 38.6 44.0   R = 8: 29.6 37.4 37.2   single wave: 55.8 56.0 56.0
-//   bench shape (W = 1e4), one walker = 157 columns: R = 32 / 16 / 8 / 4 / team / single wave 42.8 / 40.2 / 37.6 / 47 / 43 / 58;
+//   bench shape (W = 1e4), one walker = 157 columns: R = 32 / 16 / 8 / 4 / single wave 42.8 / 40.2 / 37.6 / 47 / 58;
 //     two walkers = 314 columns: R = 8 58.4, single wave 58.0
 // The preparation folded into these kernels' prologue (every workgroup builds its walker's records itself: 6 us of
 // latency-shaped work instead of a prep_profiles launch, 8 us + a boundary) pays while the workgroups run in ONE round
@@ -71,13 +69,6 @@ constexpr long kOctoRaysMaxColumns = 40;
 constexpr int kFoldMaxWorkgroups = 512;
 // (which of these forms serves which launch: kernel_table.inc, below.  The figures above are what its first version
 // -- R = 32 to 64 columns, 16 to 128, 8 to 256; with one or two molecules 32 to 96, 16 to 176 -- was read from.)
-constexpr long kQuadAllMaxColumns = 256;    // the range of the layer-parallel walk under BARTRT_ALLR_ROWS (the A/B tools' switch)
-// `cut slant`, rule 1: a team of three waves per column (rt_eclipse_s1t.hpp) for ONE walker's worth of columns at
-// W = 1e4 -- 44 against the single-wave kernel's 58 us; from two walkers on the team loses (59 / 59, four walkers 76 /
-// 61, ten 135 / 98, 64: 639 / 429 us): its producer wave keeps its table loads one layer ahead only (the 128
-// registers that five teams per CU allow), the Planck term and the panel weights are computed twice, and three
-// waves meet at a barrier every six layers
-constexpr long kTeamMaxColumns = 0;   // (round 4, later: the all-rays quad kernel takes that range at 38 us; the team stays behind BARTRT_KERNEL=team)
 constexpr long kOctoMaxColumns = 400;  // eight layers per step (R = 8) below this
 constexpr long kSplitMinColumns = 1025, kSplitMaxColumns = 1300;
 constexpr long kIlpMaxColumns = 20000;  // single-wave kernel: the ILP-scheduled build below this (128 walkers at W = 1e4)
@@ -285,12 +276,13 @@ void rt_eclipse_fast(RtArgs p) {
 // -- it pays while the single-wave columns cannot load the 1 024 SIMDs evenly
 // (8 walkers: 68 vs 75 us; from 9 walkers on the single-wave kernel is as fast).
 // Hand-off: an LDS ring of two 4-layer halves per lane -- rule 0:
-// [tau, (B_{k-1}+B_k)/2 * live], rules 1 / 2: [tau, live ? B_k : -1] -- and ONE
+// [tau, (B_{k-1}+B_k)/2 * live], rule 2: [tau, live ? B_k : -1] -- and ONE
 // raw workgroup barrier per 4 layers (the consumer reads half b while the
-// producer fills half b+1).
+// producer fills half b+1).  Rules 0 and 2 only: rule 1 never takes the pair (the measurements above).
 template <int AT, int MT, int CT, bool SQ, int INTEG>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, BARTRT_WPE)))
 void rt_eclipse_split(RtArgs p) {
+  static_assert(INTEG != kIntegSimpson, "rt_eclipse_split: rules 0 and 2");
   extern __shared__ double smem[];
   constexpr int A = AT, M = MT, C = CT;
   constexpr int NC = 4 + 2 * M + 2 * C, NI = 1 + C, NLD = 2 * M + 2 * C;
@@ -311,7 +303,6 @@ void rt_eclipse_split(RtArgs p) {
   double *sX = smem + (size_t)L * NC + (size_t)L * NI;  // [2 halves][4 layers][tau, hb][64]
   int *sFlag = reinterpret_cast<int *>(sX + 1024);      // [half] producer saw every lane finished
   double *sEnd = sX + 1024 + 2;                         // [64] B of the last layer (cloud deck term)
-  const double *sW = sEnd + 64;                         // rule 1 only
   {
     const double *gC = p.coef + (size_t)w * L * NC;
     const idx_t *gI = p.idx + (size_t)w * L * NI;
@@ -319,10 +310,6 @@ void rt_eclipse_split(RtArgs p) {
     if (threadIdx.x < 2) sFlag[threadIdx.x] = 0;
   }
   __syncthreads();
-  if (INTEG == kIntegSimpson) {
-    simpson_radius_weights(const_cast<double *>(sW), sC, NC, L, threadIdx.x, 128);
-    __syncthreads();
-  }
 
   const int lane = threadIdx.x & 63;
   const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform
@@ -354,7 +341,7 @@ void rt_eclipse_split(RtArgs p) {
       double e = fma(cf[2 + 2 * M + 2 * C], nu4, cf[3 + 2 * M + 2 * C]);   // Rayleigh + grey cloud
 #pragma unroll
       for (int j = 0; j < NLD; j++) e = fma(cf[2 + j], r[j], e);
-      tc.layer(k, live, lv, e, cf[0], sW);
+      tc.layer(k, live, lv, e, cf[0], nullptr);
       const double B = bnum * rcp_n1(exp_rt(fmin(cf[1] * nu, 700.0)) - 1.0);
       double *slot = sX + (k & 7) * 128;   // half (k/4)&1, layer k&3
       slot[lane] = tc.tau;
@@ -467,12 +454,11 @@ void rt_eclipse_split(RtArgs p) {
 // point's index are added up.  The optical depth is the prefix sum of the even
 // rows' radius panels plus, on odd rows, the trapezoid of the last interval.
 //
-// RAYS: one ray angle per lane -- a wave's 64 / R columns are (wavenumber, ray) pairs instead of wavenumbers (R = 4,
-// five angles: three wavenumbers x five rays, one column idle).  Every lane then runs the single-ray form of the
-// walk with its own ray's constants: one transmittance, ITS cut (`cut slant`: the ray's threshold RtArgs::thr, so the
-// ballots that find a column's cut and the row that carries the padded point work per ray as they stand) and ITS pad
-// width (mu of vertical depth = one unit of slant depth); the five rays of a wavenumber meet in a five-lane sum at
-// the very end.  Extinction, optical depth and Planck term are computed five times over -- on launches that leave
+// RAYS (rules 0 / 2): one ray angle per lane -- a wave's 64 / R columns are (wavenumber, ray) pairs instead of
+// wavenumbers (R = 4, five angles: three wavenumbers x five rays, one column idle).  Every lane then runs the single-ray
+// form of the walk with its own ray's constants: one transmittance and ITS cut (`cut slant`: the ray's threshold
+// RtArgs::thr, so the ballots that find a column's cut work per ray as they stand); the five rays of a wavenumber meet
+// in a five-lane sum at the very end.  Extinction, optical depth and Planck term are computed five times over -- on launches that leave
 // most of the chip idle anyway (one to three walkers) -- in exchange for a layer-parallel walk whose per-step work
 // is a fifth of the five-ray lane's: this is how `cut slant`, whose rays cannot share a layer sum, keeps a
 // few-walker kernel (the single-wave slant kernel walks a column's 100 layers serially: 50 us at any small batch).
@@ -502,7 +488,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BARTRT_QUAD
   constexpr int AE = RAYS ? 1 : (SQ ? A - 1 : A);     // transmittances that need an exponential
   constexpr int WN = 64 / R;                          // columns per wave
   constexpr int WNR = RAYS ? WN / A : WN;             // wavenumbers per wave
-  static_assert(!RAYS || (WNR >= 1 && !SQ), "RAYS: the ray grid fits a lane row; no squared-transmittance shortcut");
+  static_assert(!RAYS || (WNR >= 1 && !SQ && INTEG != kIntegSimpson), "RAYS: rules 0 / 2, the ray grid fits a lane row, no squared-transmittance shortcut");
   static_assert(!ALLR || (INTEG == kIntegSimpson && !RAYS), "ALLR: rule 1, all rays per lane");
   constexpr bool SIMPSON = INTEG == kIntegSimpson;
   const int L = p.L, W = p.W;
@@ -552,15 +538,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BARTRT_QUAD
   const int i0 = (tile * 4 + (threadIdx.x >> 6)) * WNR;  // this wave's first wavenumber
   if (i0 >= W) return;
   const unsigned ii = (col_on && i0 + mw < W) ? (unsigned)(i0 + mw) : (unsigned)(W - 1);
-  // this lane's ray (RAYS) -- or, without, the column's cut and pad as they always were
-  double invmu_l = p.invmu[0], wgt_l = p.wgt[0], wq_l = p.wq[0], thr_l = p.toomuch, padw_l = 1.0;
+  // this lane's ray (RAYS) -- or, without, the column's cut as it always was
+  double invmu_l = p.invmu[0], wgt_l = p.wgt[0], wq_l = p.wq[0], thr_l = p.toomuch;
   if constexpr (RAYS) {
-    if (p.cut_slant) { thr_l = p.thr[0]; padw_l = p.mu[0]; }
+    if (p.cut_slant) thr_l = p.thr[0];
 #pragma unroll
     for (int a = 1; a < A; a++)
       if (ray == a) {
         invmu_l = p.invmu[a]; wgt_l = p.wgt[a]; wq_l = p.wq[a];
-        if (p.cut_slant) { thr_l = p.thr[a]; padw_l = p.mu[a]; }
+        if (p.cut_slant) thr_l = p.thr[a];
       }
   }
   const double nu = p.wn[ii];
@@ -799,7 +785,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BARTRT_QUAD
         const bool pad = j < L && ((cut_here && q == f + 1) || (pad_next && q == 0));
         if (cut_here) nend = R * s + f + ((R * s + f + 1 < L) ? 1 : 0);
         pad_next = cut_here && f == R - 1;
-        const double x = pad ? tau1 + padw_l : tau;
+        const double x = pad ? tau1 + 1.0 : tau;
         double w0, w1, w2;
         simpson_tau_weights(tau1 - tau2, x - tau1, w0, w1, w2);
         if (j == 1) { w0 = 0.0; w1 = 0.5 * (x - tau1); w2 = w1; }  // the first interval: a trapezoid
@@ -866,7 +852,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BARTRT_QUAD
 }  // namespace bartrt
 #include "rt_eclipse_s1.hpp"   // rule 1's single-wave kernel
 #include "rt_eclipse_s1s.hpp"  // ... with the `toomuch` cut on each ray's slant depth
-#include "rt_eclipse_s1t.hpp"  // ... as a team of three waves per column
 namespace bartrt {
 
 #ifndef __HIPCC_RTC__   // ---- host side: the launchers (to the end of the file)
@@ -923,10 +908,6 @@ inline bool order_angles_for_square(RtArgs &r) {
   return false;
 }
 
-// Launches the specialised kernel for this shape and batch size under rule INTEG;
-// returns false when the shape has none (the caller falls back to the generic
-// kernel).  `kmode`: forced variant (BARTRT_KERNEL), empty = by batch size.
-// info (optional): what was launched (name, wavenumbers per recorded column).
 // the single-wave kernel of rule 0 in its ILP-scheduled build (rt_eclipse_i0_ilp.hip);
 // false: no instantiation for this shape
 bool launch_rt_fast_ilp(const RtArgs &b, bool sq, int block, int nblocks, size_t sh, hipStream_t st, hipError_t &err);
@@ -952,329 +933,359 @@ bool launch_rt_qadj(const RtArgs &b, bool sq, int rows, int nblocks, size_t sh, 
 BARTRT_ANGLE_SIZES(BARTRT_DECL_ANGLES)
 #undef BARTRT_DECL_ANGLES
 
-// fold (optional): the preparation of this launch's walkers, NOT yet launched -- only the kernels that can run it in
-// their own prologue (the all-rays layer-parallel forms of rule 1 under `cut slant`) are considered then, and false
-// means "launch the preparation, then call again without it".
-template <int INTEG>
-bool launch_rt_spec(const RtArgs &a, int block, hipStream_t st, const std::string &kmode, bool force_window,
-                    bool allow_sq, hipError_t &err, RtLaunchInfo *info, const PrepArgs *fold = nullptr) {
-  if (fold && (INTEG != kIntegSimpson || !a.cut_slant || a.A != 5 || a.ext || a.intens_out || a.tau_out || a.nprep != 0)) return false;
-  const size_t sh_fold = fold ? sizeof(double) * prep_lds_doubles(fold->L, fold->S, fold->Nt, fold->ncia_temps) : 0;
-  const int ntiles8 = (a.ntiles + 7) / 8 * 8;
-  const int nblocks = ntiles8 * a.nwalkers;
-  const size_t sh = sizeof(double) * ((size_t)a.L * coef_stride(a.M, a.C) + integ_lds_doubles<INTEG>(a.L)) +
-                    sizeof(idx_t) * (size_t)a.L * idx_stride(a.C);
-  // (the specialised kernels rebuild their buffer descriptor per layer, so the
-  // table may be of any size; one layer's pair of planes must stay below 4 GB)
-  const bool plane_ok = 2ull * a.M * a.W * 8ull < (1ull << 31);
-  if (a.ext) {
-    // line-by-line hand-off: the single-wave kernel with the extinction array as one
-    // more load per layer (rules 0 and 1, no table; anything else takes the generic kernel)
-    if (!(INTEG != kIntegTrapzTau && a.A == 5 && a.M == 0 && (a.C <= 2 || a.C == 4) && !a.intens_out && !a.tau_out &&
-          sh <= 55 * 1024 && kmode != "generic"))
-      return false;
-    RtArgs b = a;
-    const bool sq = allow_sq && order_angles_for_square(b);
-    b.ntiles = a.ntiles;
-    if (info) { info->kernel = "rt_eclipse_fast (line-by-line extinction)"; info->wn_per_column = block; info->ncolumns = b.ntiles; }
-    err = hipSuccess;
-    if (a.cut_slant) {
-      if (info) info->kernel = "single-wave `cut slant` kernel (line-by-line extinction)";
-      return launch_rt_slant_ext(b, INTEG, sq, block, nblocks, sh, st, err);
-    }
-    if (INTEG == kIntegSimpson ? launch_rt_simpson_ext(b, sq, block, nblocks, sh, st, err)
-                               : launch_rt_fast_ext(b, sq, block, nblocks, sh, st, err))
-      return true;
-    return false;
-  }
-  if ((a.intens_out || a.tau_out) && a.cut_slant && INTEG == kIntegSimpson && a.A == 5 && a.slog && a.nwalkers == 1 &&
-      a.nprep == 0 && plane_ok && sh <= 55 * 1024 && kmode.empty()) {
-    // tau.dat / outintens of the default conventions: the single-wave slant kernel writes them on its way
-    if (info) { info->kernel = "rt_eclipse_simpson_slant (with optical-depth / intensity outputs)"; info->wn_per_column = block; info->ncolumns = a.ntiles; info->prep_fused = false; }
-    err = hipSuccess;
-    if (launch_rt_slant_out(a, block, nblocks, sh, st, err)) return true;
-    if (rtc_single_wave_ok(a) &&
-        rtc_try(info, false, dim3(nblocks), dim3(block), sh, st, a, err, "rt_eclipse_simpson_slant<5, %d, %d, false, 0, false, true>", a.M, a.C))
-      return true;
-  }
-  if (!(!a.intens_out && !a.tau_out && plane_ok && sh <= 55 * 1024)) return false;
-  // (the event log serves rule 1's single-wave kernels only -- rt_eclipse_s1s.hpp, rt_eclipse_s1t.hpp; rule 2 on other
-  // ray grids: generic kernel)
-  if (a.cut_slant && ((INTEG == kIntegSimpson && !a.slog) || (INTEG == kIntegTrapzTau && a.A != 5))) return false;
-  if (a.A != 5) {
-    // other ray-grid sizes: the single-wave kernel of rule 0 / rule 1 at every batch size
-    if (INTEG == kIntegTrapzTau || a.A < 1 || a.A > kMaxAngles || kmode == "quad" || kmode == "octo" || kmode == "split") return false;
-    size_t sha = sh;
-    int nba = nblocks;
+// ---------------------------------------------------------------------------
+// launch_rt_spec (below) chooses a form; each form's launcher owns its tiles, workgroups, LDS, RtLaunchInfo, ahead-of-time
+// (M, C) dispatch and run-time fallback, and returns false when it launched nothing.
+// SpecLaunch: what the forms share -- the launch's arguments (b: with the ray angles ordered for the SQ kernels and the
+// table's addressing chosen), the LDS of its walkers' layer records, and the next batch's preparation (RtArgs::nprep):
+// every five-angle form carries it at the head of its grid, prep_slots(nprep) more workgroups, LDS for the larger of the
+// two jobs.
+struct SpecLaunch {
+  const RtArgs &a;
+  RtArgs b;
+  bool sq = false;
+  int block;
+  hipStream_t st;
+  hipError_t &err;
+  RtLaunchInfo *info;
+  const PrepArgs *fold;   // (launch_rt_spec)
+  size_t sh;              // LDS of the layer records (+ rule 1's Simpson weights of the radius grid)
+  int nblocks;            // the single-wave grid without the preparation's workgroups
+  int nsel;               // the batch the form is chosen for (RtArgs::nsel)
+  int pslots = 0;         // the preparation's workgroups
+  size_t shp = 0;         // LDS the preparation needs beyond sh
+  size_t sh_fold = 0;     // LDS of the preparation of `fold`
+
+  SpecLaunch(const RtArgs &a_, size_t sh_, int block_, hipStream_t st_, hipError_t &err_, RtLaunchInfo *info_,
+             const PrepArgs *fold_)
+      : a(a_), b(a_), block(block_), st(st_), err(err_), info(info_), fold(fold_), sh(sh_),
+        nblocks((a_.ntiles + 7) / 8 * 8 * a_.nwalkers), nsel(a_.nsel > a_.nwalkers ? a_.nsel : a_.nwalkers) {
     if (a.nprep > 0) {
-      sha = std::max(sh, sizeof(double) * prep_lds_doubles(a.prep_next.L, a.prep_next.S, a.prep_next.Nt, a.prep_next.ncia_temps));
-      nba += prep_slots(a.nprep);
+      pslots = prep_slots(a.nprep);
+      const size_t need = sizeof(double) * prep_lds_doubles(a.prep_next.L, a.prep_next.S, a.prep_next.Nt, a.prep_next.ncia_temps);
+      shp = need > sh ? need - sh : 0;
     }
-    if (info) {
-      info->kernel = a.cut_slant ? (INTEG == kIntegSimpson ? "rt_eclipse_simpson_slant (ray grid of another size)"
-                                                          : "rt_eclipse_fast<SLANT> (ray grid of another size)")
-                     : INTEG == kIntegSimpson ? "rt_eclipse_simpson (ray grid of another size)" : "rt_eclipse_fast (ray grid of another size)";
-      info->wn_per_column = block; info->ncolumns = a.ntiles; info->prep_fused = a.nprep > 0;
-    }
-    err = hipSuccess;
-    bool done = false;
-    switch (a.A) {
-#define BARTRT_CASE_ANGLES(N) case N: done = launch_rt_angles_##N(a, INTEG, block, nba, sha, st, err); break;
-      BARTRT_ANGLE_SIZES(BARTRT_CASE_ANGLES)
+    if (fold) sh_fold = sizeof(double) * prep_lds_doubles(fold->L, fold->S, fold->Nt, fold->ncia_temps);
+  }
+  void order_angles(bool allow_sq) { sq = allow_sq && order_angles_for_square(b); }
+  // the layer-parallel kernels address the tables with per-lane 32-bit offsets (a grid of 4 GB or more through a window
+  // that moves with the step's layers)
+  bool addressable(int rows) const { return a.cia_bytes < (1ull << 32) - 4096 && (!b.window || window_fits(a, rows)); }
+  // workgroups of `ntiles` tiles per walker (block_to_work: whole rounds of eight), the preparation's included
+  int workgroups(int ntiles) const { return (ntiles + 7) / 8 * 8 * a.nwalkers + pslots; }
+  // one ahead-of-time kernel
+  void run(void (*kernel)(RtArgs), int nwg, int threads, size_t lds, const RtArgs &args) const {
+    BARTRT_RT_LAUNCH(kernel, dim3(nwg), dim3(threads), lds, st, args);
+    err = hipGetLastError();
+  }
+  // the form launched: what RtLaunchInfo records of it
+  bool launched(const char *kernel, int wn_per_column, int ncolumns, bool folded = false) const {
+    if (info) { info->kernel = kernel; info->wn_per_column = wn_per_column; info->ncolumns = ncolumns; info->prep_folded = folded; }
+    return true;
+  }
+};
+
+// f(M, C, SQ) -- integral constants -- for the launch's (molecules, CIA slots) pair of the ahead-of-time list
+// (BARTRT_MC_LIST); false: the pair is not on it
+template <class F>
+bool dispatch_mc(int M, int C, bool sq, F &&f) {
+#define BARTRT_MC_CASE(MM, CC)                                                                                   \
+  if (M == MM && C == CC) {                                                                                      \
+    if (sq) f(std::integral_constant<int, MM>(), std::integral_constant<int, CC>(), std::true_type());           \
+    else f(std::integral_constant<int, MM>(), std::integral_constant<int, CC>(), std::false_type());             \
+    return true;                                                                                                 \
+  }
+  BARTRT_MC_LIST(BARTRT_MC_CASE)
+#undef BARTRT_MC_CASE
+  return false;
+}
+
+// A layer-parallel launch (rt_eclipse_quad, rt_eclipse_qadj): workgroups of four waves of `wn` wavenumbers, R = rows
+// layers per step (from 16 rows on the layer records are padded: NCS).  folds: it prepares its own walkers -- asked to
+// (fold), LDS for both jobs, and its workgroups run in one round (kFoldMaxWorkgroups).
+struct LpGeom { RtArgs b; int wn, ncolumns, nwg; size_t lds; bool folds; };
+inline LpGeom lp_geom(const SpecLaunch &c, int rows, int wn) {
+  LpGeom g{c.b, wn, 0, 0, 0, false};
+  g.b.ntiles = (c.a.W + 4 * wn - 1) / (4 * wn);
+  g.ncolumns = 4 * g.b.ntiles;
+  g.nwg = c.workgroups(g.b.ntiles);
+  g.lds = c.sh + c.shp + (rows >= 16 ? sizeof(double) * (size_t)c.a.L : 0);
+  g.folds = c.fold && g.lds + c.sh_fold <= 64 * 1024 && (g.b.ntiles + 7) / 8 * 8 * c.nsel + c.pslots <= kFoldMaxWorkgroups;
+  if (g.folds) { g.b.nprep = -1; g.b.prep_next = *c.fold; g.lds += c.sh_fold; }
+  return g;
+}
+
+// line-by-line hand-off: the single-wave kernel with the extinction array as one more load per layer
+template <int INTEG>
+bool launch_form_ext(const SpecLaunch &c) {
+  const RtArgs &b = c.b;
+  if (b.cut_slant)
+    return launch_rt_slant_ext(b, INTEG, c.sq, c.block, c.nblocks, c.sh, c.st, c.err) &&
+           c.launched("single-wave `cut slant` kernel (line-by-line extinction)", c.block, b.ntiles);
+  return (INTEG == kIntegSimpson ? launch_rt_simpson_ext(b, c.sq, c.block, c.nblocks, c.sh, c.st, c.err)
+                                 : launch_rt_fast_ext(b, c.sq, c.block, c.nblocks, c.sh, c.st, c.err)) &&
+         c.launched("rt_eclipse_fast (line-by-line extinction)", c.block, b.ntiles);
+}
+
+// tau.dat / outintens of the default conventions (one walker): the single-wave slant kernel writes them on its way
+// (the ray angles in their own order)
+inline bool launch_form_slant_out(const SpecLaunch &c) {
+  const RtArgs &a = c.a;
+  return (launch_rt_slant_out(a, c.block, c.nblocks, c.sh, c.st, c.err) ||
+          (rtc_single_wave_ok(a) && rtc_try(c.info, false, dim3(c.nblocks), dim3(c.block), c.sh, c.st, a, c.err,
+                                            "rt_eclipse_simpson_slant<5, %d, %d, false, 0, false, true>", a.M, a.C))) &&
+         c.launched("rt_eclipse_simpson_slant (with optical-depth / intensity outputs)", c.block, a.ntiles);
+}
+
+// ray grids of other sizes than five, rules 0 / 1: the single-wave kernels (the ray angles in their own order)
+template <int INTEG>
+bool launch_form_angles(const SpecLaunch &c) {
+  const RtArgs &a = c.a;
+  const int nwg = c.workgroups(a.ntiles);
+  const size_t lds = c.sh + c.shp;
+  bool done = false;
+  switch (a.A) {
+#define BARTRT_CASE_ANGLES(N) case N: done = launch_rt_angles_##N(a, INTEG, c.block, nwg, lds, c.st, c.err); break;
+    BARTRT_ANGLE_SIZES(BARTRT_CASE_ANGLES)
 #undef BARTRT_CASE_ANGLES
-      default: break;
-    }
-    if (!done && rtc_single_wave_ok(a)) {
-      // (a ray grid of ten and more angles, or a (molecules, slots) pair outside the ahead-of-time list)
-      const dim3 g(nba), bl(block);
-      if (a.cut_slant)
-        done = INTEG == kIntegTransmittance
-                   ? rtc_try(info, true, g, bl, sha, st, a, err, "rt_eclipse_fast<%d, %d, %d, false, 0, 1, false, true>", a.A, a.M, a.C)
-                   : rtc_try(info, true, g, bl, sha, st, a, err, "rt_eclipse_simpson_slant<%d, %d, %d, false, %d>", a.A, a.M, a.C, a.A <= 6 ? 1 : 0);
-      else
-        done = INTEG == kIntegTransmittance
-                   ? rtc_try(info, true, g, bl, sha, st, a, err, "rt_eclipse_fast<%d, %d, %d, false, 0, 1>", a.A, a.M, a.C)
-                   : rtc_try(info, true, g, bl, sha, st, a, err, "rt_eclipse_simpson<%d, %d, %d, false, 1>", a.A, a.M, a.C);
-    }
-    if (!done && info) info->prep_fused = false;
-    return done;
+    default: break;
   }
-  // (the producer/consumer kernel adds 9 kB of its own)
-  RtArgs b = a;
-  const bool sq = allow_sq && order_angles_for_square(b);
-  // every specialised kernel carries the next batch's preparation (RtArgs::nprep) at the head of
-  // its grid: prep_slots(nprep) more workgroups, LDS for the larger of the two jobs
-  const int pslots = a.nprep > 0 ? prep_slots(a.nprep) : 0;
-  size_t shp = 0;   // LDS the preparation needs beyond the RT workgroups'
-  if (a.nprep > 0) {
-    const size_t need = sizeof(double) * prep_lds_doubles(a.prep_next.L, a.prep_next.S, a.prep_next.Nt, a.prep_next.ncia_temps);
-    shp = need > sh ? need - sh : 0;
-    if (info) info->prep_fused = true;
+  if (!done && rtc_single_wave_ok(a)) {
+    // (a ray grid of ten and more angles, or a (molecules, slots) pair outside the ahead-of-time list)
+    const dim3 g(nwg), bl(c.block);
+    if (a.cut_slant)
+      done = INTEG == kIntegTransmittance
+                 ? rtc_try(c.info, true, g, bl, lds, c.st, a, c.err, "rt_eclipse_fast<%d, %d, %d, false, 0, 1, false, true>", a.A, a.M, a.C)
+                 : rtc_try(c.info, true, g, bl, lds, c.st, a, c.err, "rt_eclipse_simpson_slant<%d, %d, %d, false, %d>", a.A, a.M, a.C, a.A <= 6 ? 1 : 0);
+    else
+      done = INTEG == kIntegTransmittance
+                 ? rtc_try(c.info, true, g, bl, lds, c.st, a, c.err, "rt_eclipse_fast<%d, %d, %d, false, 0, 1>", a.A, a.M, a.C)
+                 : rtc_try(c.info, true, g, bl, lds, c.st, a, c.err, "rt_eclipse_simpson<%d, %d, %d, false, 1>", a.A, a.M, a.C);
   }
-  // too few single-wave columns to load the 1 024 SIMDs evenly -> several
-  // waves per 64 wavenumbers: four 16-wavenumber waves that take four layers at
-  // a time (quad-layer), or a producer / consumer pair
-  const int nsel = a.nsel > a.nwalkers ? a.nsel : a.nwalkers;   // (the batch the variant is chosen for: RtArgs::nsel)
-  const long columns = (long)nsel * (((a.Wfull > 0 ? a.Wfull : a.W) + 63) / 64);   // (of the whole grid: RtArgs::Wfull)
-  const int ntiles64 = (a.W + 63) / 64;
-  const int nb64 = (ntiles64 + 7) / 8 * 8 * a.nwalkers;
-  // the quad-layer kernel addresses the tables with per-lane 32-bit offsets
-  // (a grid of 4 GB or more through a window that moves with the step's layers)
-  const bool octo = kmode == "octo" || (kmode.empty() && columns <= kOctoMaxColumns);
-  b.window = a.kappa_bytes >= (1ull << 32) - 4096 || force_window;
-  const bool fits32 = a.cia_bytes < (1ull << 32) - 4096 && (!b.window || window_fits(a, octo ? 8 : 4));
-  err = hipSuccess;
-  constexpr bool SQOK = true;   // exp(-2 tau / mu) = exp(-tau / mu)^2 under every rule
-  constexpr long quad_max = INTEG == kIntegSimpson ? kQuadMaxColumnsSimpson : kQuadMaxColumns;
-  if (a.cut_slant) {
-    // the per-ray cut: launches that leave the chip mostly idle take the layer-parallel walk with ONE RAY PER LANE
-    // (rt_eclipse_quad<..., RAYS>: three wavenumbers x five rays x four layers per wave and step) ...
-    // which of the two layer-parallel forms: one ray per lane for the smallest launches and for rules 0 / 2, all rays per
-    // lane (rule 1) above that (BARTRT_KERNEL: quad / octo = the rule's own choice of form, quadrays / octorays = one ray
-    // per lane)
-    const bool rays_forced = kmode == "quadrays" || kmode == "octorays";
-    const bool lp_forced = kmode == "quad" || kmode == "octo";
-    const bool use_rays = rays_forced || (INTEG != kIntegSimpson && (lp_forced || (kmode.empty() && columns <= kQuadRaysMaxColumns)));
-    if constexpr (INTEG == kIntegSimpson) {
-      // rule 1: the layer-parallel walk with ALL rays per lane (rt_eclipse_quad<..., ALLR>)
-      // rows = layers per step (and 64 / rows wavenumbers per wave): the fewer the columns, the more rows
-      static const int rows_env = [] { const char *v = std::getenv("BARTRT_ALLR_ROWS"); return v && *v ? atoi(v) : 0; }();
-      // the launch's variant: forced (BARTRT_KERNEL, BARTRT_ALLR_ROWS), else the measured table's (kernel_table.inc)
-      static const int adj_env = [] { const char *v = std::getenv("BARTRT_ADJ"); return v && *v ? atoi(v) : -1; }();
-      const KernelChoice &entry = slant_simpson_choice(a.M, columns);
-      const bool adj_ok = adj_env != 0 && rows_env == 0;
-      const bool adj_named = entry.variant == kVarAdj16 || entry.variant == kVarAdj8;
-      // (the layer-parallel form that runs should the adjacent one not launch: the entry's fallback)
-      const int other = adj_named ? entry.fallback : entry.variant;
-      int rows = kmode == "quad" ? 4 : kmode == "octo" ? 8 : kmode == "hexa" ? 16 : kmode == "r32" ? 32 : other == kVarSingle ? 4 : other;
-      if (rows_env == 4 || rows_env == 8 || rows_env == 16 || rows_env == 32) rows = rows_env;
-      const bool lpa_forced = lp_forced || kmode == "hexa" || kmode == "r32" || kmode == "adj8" || kmode == "adj16";
-      while (rows > 4 && b.window && !window_fits(a, rows)) rows /= 2;
-      // rt_eclipse_qadj (rows on adjacent lanes: DPP row shifts instead of ds_bpermute, carries in place) where the table
-      // names it; BARTRT_KERNEL=adj8 / adj16 force it, BARTRT_ADJ=0 switches it off
-      int adj_rows = kmode == "adj8" ? 8 : kmode == "adj16" ? 16 : 0;
-      if (kmode.empty() && adj_ok && adj_named) adj_rows = entry.variant == kVarAdj16 ? 16 : 8;
-      // (the layer-parallel walk at all: forced, or the table names one of its forms; BARTRT_ALLR_ROWS, the A/B tools'
-      // switch, keeps round 5's range for it)
-      const bool lp_by_table = kmode.empty() && (rows_env != 0 ? columns <= kQuadAllMaxColumns : other != kVarSingle);
-      if (adj_rows && !use_rays && a.cia_bytes < (1ull << 32) - 4096 && (!b.window || window_fits(a, adj_rows))) {
-        const int awn = 64 / adj_rows;
-        RtArgs ba = b;
-        ba.ntiles = (a.W + 4 * awn - 1) / (4 * awn);
-        const int nba = (ba.ntiles + 7) / 8 * 8 * a.nwalkers + pslots;
-        size_t sha = sh + shp + (adj_rows >= 16 ? sizeof(double) * (size_t)a.L : 0);
-        const bool folds = fold && sha + sh_fold <= 64 * 1024 && (ba.ntiles + 7) / 8 * 8 * nsel + pslots <= kFoldMaxWorkgroups;
-        if (folds) { ba.nprep = -1; ba.prep_next = *fold; sha += sh_fold; }
-        if (fold && !folds) return false;
-        RtLaunchInfo keep;
-        if (info) {
-          keep = *info;
-          info->kernel = adj_rows == 16 ? "rt_eclipse_qadj<R=16> (rows on adjacent lanes)" : "rt_eclipse_qadj<R=8> (rows on adjacent lanes)";
-          info->wn_per_column = awn; info->ncolumns = 4 * ba.ntiles;
-        }
-        err = hipSuccess;
-        if (info) info->prep_folded = folds;
-        if (launch_rt_qadj(ba, sq, adj_rows, nba, sha, st, err)) return true;
-        if (rtc_try(info, false, dim3(nba), dim3(256), sha, st, ba, err, "rt_eclipse_qadj<5, %d, %d, %s, %d>", a.M, a.C, tf(sq), adj_rows)) return true;
-        if (info) *info = keep;    // (neither an instantiation nor a compiler: the choice before it)
-      }
-      if (!use_rays && (lpa_forced || lp_by_table) && a.cia_bytes < (1ull << 32) - 4096 &&
-          (!b.window || window_fits(a, rows))) {
-        const int wnw = 64 / rows;   // wavenumbers per wave
-        b.ntiles = (a.W + 4 * wnw - 1) / (4 * wnw);
-        const int nbq = (b.ntiles + 7) / 8 * 8 * a.nwalkers + pslots;
-        size_t shq = sh + shp + (rows >= 16 ? sizeof(double) * (size_t)a.L : 0);   // (padded records: NCS)
-        const bool folds = fold && shq + sh_fold <= 64 * 1024 && (b.ntiles + 7) / 8 * 8 * nsel + pslots <= kFoldMaxWorkgroups;
-        if (fold && !folds) return false;
-        if (folds) { b.nprep = -1; b.prep_next = *fold; shq += sh_fold; }
-        if (info) info->prep_folded = folds;
-        if (info) {
-          info->kernel = rows == 32 ? "rt_eclipse_quad<R=32, all rays per lane>" : rows == 16 ? "rt_eclipse_quad<R=16, all rays per lane>"
-                         : rows == 8 ? "rt_eclipse_quad<R=8, all rays per lane>" : "rt_eclipse_quad<R=4, all rays per lane>";
-          info->wn_per_column = wnw; info->ncolumns = 4 * b.ntiles;
-        }
-#define BARTRT_QUADALL_R(MM, CC, RR)                                                                                         \
-      if (sq) BARTRT_RT_LAUNCH((rt_eclipse_quad<5, MM, CC, true, RR, INTEG, false, true>), dim3(nbq), dim3(256), shq, st, b); \
-      else BARTRT_RT_LAUNCH((rt_eclipse_quad<5, MM, CC, false, RR, INTEG, false, true>), dim3(nbq), dim3(256), shq, st, b);
-#define BARTRT_QUADALL(MM, CC)                                                                                               \
-  if (a.M == MM && a.C == CC) {                                                                                              \
-    if (rows == 32) { BARTRT_QUADALL_R(MM, CC, 32) }                                                                         \
-    else if (rows == 16) { BARTRT_QUADALL_R(MM, CC, 16) }                                                                    \
-    else if (rows == 8) { BARTRT_QUADALL_R(MM, CC, 8) }                                                                      \
-    else { BARTRT_QUADALL_R(MM, CC, 4) }                                                                                     \
-    err = hipGetLastError();                                                                                                 \
-    return true;                                                                                                             \
-  }
-        BARTRT_MC_LIST(BARTRT_QUADALL)
-#undef BARTRT_QUADALL
-#undef BARTRT_QUADALL_R
-        if (rtc_try(info, false, dim3(nbq), dim3(256), shq, st, b, err, "rt_eclipse_quad<5, %d, %d, %s, %d, %d, false, true>", a.M, a.C,
-                    tf(sq), rows, INTEG))
-          return true;
-        if (folds) { b.nprep = 0; if (info) info->prep_folded = false; }
-      }
-      if (fold) return false;   // (no kernel that prepares its own walkers serves this launch: the caller launches prep_profiles)
-    }
-    if (use_rays && fits32) {
-      // (the smallest launches -- one walker on the demo shape -- eight layers per step: one wavenumber x five rays per wave)
-      const bool octor = kmode == "octo" || kmode == "octorays" || (kmode.empty() && columns <= kOctoRaysMaxColumns);
-      const bool win_ok = !b.window || window_fits(a, octor ? 8 : 4);
-      if (win_ok) {
-        b.ntiles = octor ? (a.W + 3) / 4 : (a.W + 11) / 12;          // a workgroup: four waves of one / three wavenumbers
-        const int nbq = (b.ntiles + 7) / 8 * 8 * a.nwalkers + pslots;
-        const size_t shq = sh + shp;
-        if (info) {
-          info->kernel = octor ? "rt_eclipse_quad<R=8, one ray per lane>" : "rt_eclipse_quad<R=4, one ray per lane>";
-          info->wn_per_column = octor ? 1 : 3; info->ncolumns = 4 * b.ntiles;
-        }
-#define BARTRT_QUADRAYS(MM, CC)                                                                                          \
-  if (a.M == MM && a.C == CC) {                                                                                          \
-    if (octor) BARTRT_RT_LAUNCH((rt_eclipse_quad<5, MM, CC, false, 8, INTEG, true>), dim3(nbq), dim3(256), shq, st, b);  \
-    else BARTRT_RT_LAUNCH((rt_eclipse_quad<5, MM, CC, false, 4, INTEG, true>), dim3(nbq), dim3(256), shq, st, b);        \
-    err = hipGetLastError();                                                                                             \
-    return true;                                                                                                         \
-  }
-        BARTRT_MC_LIST(BARTRT_QUADRAYS)
-#undef BARTRT_QUADRAYS
-        if (rtc_try(info, false, dim3(nbq), dim3(256), shq, st, b, err, "rt_eclipse_quad<5, %d, %d, false, %d, %d, true>", a.M, a.C,
-                    octor ? 8 : 4, INTEG))
-          return true;
-      }
-    }
-    // ... a team of three waves per column (rule 1) while single-wave columns would load the SIMDs unevenly ...
-    if (INTEG == kIntegSimpson && (kmode == "team" || (kmode.empty() && columns <= kTeamMaxColumns))) {
-      b.ntiles = ntiles64;
-      const size_t sht = sh + sizeof(double) * team_lds_doubles() + shp;
-      if (info) { info->kernel = "rt_eclipse_slant_team (three waves per column)"; info->wn_per_column = 64; info->ncolumns = b.ntiles; }
-      if (launch_rt_slant_team(b, sq, nb64 + pslots, sht, st, err)) return true;
-    }
-    // ... everything else the single-wave kernels (each ray its own sums in one lane)
-    b.ntiles = a.ntiles;
-    if (info) {
-      info->kernel = INTEG == kIntegSimpson ? "rt_eclipse_simpson_slant (ILP-scheduled build)" : "rt_eclipse_fast<SLANT> (ILP-scheduled build)";
-      info->wn_per_column = block; info->ncolumns = b.ntiles;
-    }
-    if (launch_rt_slant(b, INTEG, sq, block, nblocks + pslots, sh + shp, st, err)) return true;
-    if (!rtc_single_wave_ok(a)) { if (info) info->prep_fused = false; return false; }
-    if (INTEG == kIntegSimpson
-            ? rtc_try(info, true, dim3(nblocks + pslots), dim3(block), sh + shp, st, b, err, "rt_eclipse_simpson_slant<5, %d, %d, %s, %d>", a.M, a.C, tf(sq),
-                      slant_sched(a.M, a.C, 1))
-            : rtc_try(info, true, dim3(nblocks + pslots), dim3(block), sh + shp, st, b, err, "rt_eclipse_fast<5, %d, %d, %s, %d, 1, false, true>", a.M,
-                      a.C, tf(sq), INTEG))
-      return true;
-    if (info) info->prep_fused = false;
-    return false;
-  }
-  if ((kmode == "quad" || kmode == "octo" || (kmode.empty() && columns <= quad_max)) && fits32) {
-    // the smallest launches take eight layers per step (8 wavenumbers per wave)
-    b.ntiles = octo ? (a.W + 31) / 32 : ntiles64;
-    const int nbq = (b.ntiles + 7) / 8 * 8 * a.nwalkers + pslots;
-    const size_t shq = sh + shp;
-    if (info) { info->kernel = octo ? "rt_eclipse_quad<R=8>" : "rt_eclipse_quad<R=4>"; info->wn_per_column = octo ? 8 : 16; info->ncolumns = 4 * b.ntiles; }
-#define BARTRT_QUAD(MM, CC)                                                                                          \
-  if (a.M == MM && a.C == CC) {                                                                                      \
-    if (octo) {                                                                                                      \
-      if (sq) BARTRT_RT_LAUNCH((rt_eclipse_quad<5, MM, CC, SQOK, 8, INTEG>), dim3(nbq), dim3(256), shq, st, b);     \
-      else BARTRT_RT_LAUNCH((rt_eclipse_quad<5, MM, CC, false, 8, INTEG>), dim3(nbq), dim3(256), shq, st, b);       \
-    } else {                                                                                                         \
-      if (sq) BARTRT_RT_LAUNCH((rt_eclipse_quad<5, MM, CC, SQOK, 4, INTEG>), dim3(nbq), dim3(256), shq, st, b);     \
-      else BARTRT_RT_LAUNCH((rt_eclipse_quad<5, MM, CC, false, 4, INTEG>), dim3(nbq), dim3(256), shq, st, b);       \
-    }                                                                                                                \
-    err = hipGetLastError();                                                                                         \
-    return true;                                                                                                     \
-  }
-    BARTRT_MC_LIST(BARTRT_QUAD)
-#undef BARTRT_QUAD
-    if (rtc_try(info, false, dim3(nbq), dim3(256), shq, st, b, err, "rt_eclipse_quad<5, %d, %d, %s, %d, %d>", a.M, a.C, tf(sq), octo ? 8 : 4, INTEG))
-      return true;
-  }
-  if (kmode == "split" ||
-      (kmode.empty() && INTEG != kIntegSimpson && columns >= kSplitMinColumns && columns <= kSplitMaxColumns)) {
-    b.ntiles = ntiles64;
-    const size_t shs = sh + sizeof(double) * (1024 + 2 + 64) + shp;
-    const int nbs = nb64 + pslots;
-    if (info) { info->kernel = "rt_eclipse_split"; info->wn_per_column = 64; info->ncolumns = b.ntiles; }
-#define BARTRT_SPLIT(MM, CC)                                                                                       \
-  if (a.M == MM && a.C == CC) {                                                                                    \
-    if (sq) BARTRT_RT_LAUNCH((rt_eclipse_split<5, MM, CC, SQOK, INTEG>), dim3(nbs), dim3(128), shs, st, b);     \
-    else BARTRT_RT_LAUNCH((rt_eclipse_split<5, MM, CC, false, INTEG>), dim3(nbs), dim3(128), shs, st, b);       \
-    err = hipGetLastError();                                                                                       \
-    return true;                                                                                                   \
-  }
-    BARTRT_MC_LIST(BARTRT_SPLIT)
-#undef BARTRT_SPLIT
-    if (rtc_try(info, false, dim3(nbs), dim3(128), shs, st, b, err, "rt_eclipse_split<5, %d, %d, %s, %d>", a.M, a.C, tf(sq), INTEG)) return true;
-  }
-  b.ntiles = a.ntiles;
-  if (info) { info->kernel = "rt_eclipse_fast"; info->wn_per_column = block; info->ncolumns = b.ntiles; }
-  const size_t sh1 = sh + shp;
-  const int nblocks1 = nblocks + pslots;
-  [[maybe_unused]] const bool ilp = kmode != "mono_occ" && (kmode == "mono_ilp" || columns < kIlpMaxColumns);
+  return done && c.launched(a.cut_slant ? (INTEG == kIntegSimpson ? "rt_eclipse_simpson_slant (ray grid of another size)"
+                                                                  : "rt_eclipse_fast<SLANT> (ray grid of another size)")
+                            : INTEG == kIntegSimpson ? "rt_eclipse_simpson (ray grid of another size)"
+                                                     : "rt_eclipse_fast (ray grid of another size)",
+                            c.block, a.ntiles);
+}
+
+// rule 1 / `cut slant`: rt_eclipse_qadj, the rows of a column on adjacent lanes (R = 8 / 16)
+inline bool launch_form_qadj(const SpecLaunch &c, const LpGeom &g, int rows) {
+  const RtArgs &b = g.b;
+  return (launch_rt_qadj(b, c.sq, rows, g.nwg, g.lds, c.st, c.err) ||
+          rtc_try(c.info, false, dim3(g.nwg), dim3(256), g.lds, c.st, b, c.err, "rt_eclipse_qadj<5, %d, %d, %s, %d>", b.M, b.C,
+                  tf(c.sq), rows)) &&
+         c.launched(rows == 16 ? "rt_eclipse_qadj<R=16> (rows on adjacent lanes)" : "rt_eclipse_qadj<R=8> (rows on adjacent lanes)",
+                    g.wn, g.ncolumns, g.folds);
+}
+
+// rule 1 / `cut slant`: rt_eclipse_quad<..., ALLR>, all rays per lane (R = 4 / 8 / 16 / 32)
+template <int INTEG>
+bool launch_form_quad_allr(const SpecLaunch &c, const LpGeom &g, int rows) {
+  static_assert(INTEG == kIntegSimpson, "the all-rays form: rule 1");
+  const RtArgs &b = g.b;
+  return (dispatch_mc(b.M, b.C, c.sq, [&](auto m, auto cc, auto sq) {
+            constexpr int M = decltype(m)::value, C = decltype(cc)::value;
+            constexpr bool SQ = decltype(sq)::value;
+            c.run(rows == 32   ? rt_eclipse_quad<5, M, C, SQ, 32, INTEG, false, true>
+                  : rows == 16 ? rt_eclipse_quad<5, M, C, SQ, 16, INTEG, false, true>
+                  : rows == 8  ? rt_eclipse_quad<5, M, C, SQ, 8, INTEG, false, true>
+                               : rt_eclipse_quad<5, M, C, SQ, 4, INTEG, false, true>,
+                  g.nwg, 256, g.lds, b);
+          }) ||
+          rtc_try(c.info, false, dim3(g.nwg), dim3(256), g.lds, c.st, b, c.err, "rt_eclipse_quad<5, %d, %d, %s, %d, %d, false, true>",
+                  b.M, b.C, tf(c.sq), rows, INTEG)) &&
+         c.launched(rows == 32   ? "rt_eclipse_quad<R=32, all rays per lane>"
+                    : rows == 16 ? "rt_eclipse_quad<R=16, all rays per lane>"
+                    : rows == 8  ? "rt_eclipse_quad<R=8, all rays per lane>"
+                                 : "rt_eclipse_quad<R=4, all rays per lane>",
+                    g.wn, g.ncolumns, g.folds);
+}
+
+// rules 0 / 2, `cut slant`: rt_eclipse_quad<..., RAYS>, one ray per lane (R = 4 / 8: three wavenumbers / one x five rays
+// per wave)
+template <int INTEG>
+bool launch_form_quad_rays(const SpecLaunch &c, int rows) {
+  static_assert(INTEG != kIntegSimpson, "the one-ray-per-lane form: rules 0 / 2");
+  const LpGeom g = lp_geom(c, rows, 64 / rows / 5);
+  const RtArgs &b = g.b;
+  return (dispatch_mc(b.M, b.C, false, [&](auto m, auto cc, auto) {
+            constexpr int M = decltype(m)::value, C = decltype(cc)::value;
+            c.run(rows == 8 ? rt_eclipse_quad<5, M, C, false, 8, INTEG, true> : rt_eclipse_quad<5, M, C, false, 4, INTEG, true>,
+                  g.nwg, 256, g.lds, b);
+          }) ||
+          rtc_try(c.info, false, dim3(g.nwg), dim3(256), g.lds, c.st, b, c.err, "rt_eclipse_quad<5, %d, %d, false, %d, %d, true>",
+                  b.M, b.C, rows, INTEG)) &&
+         c.launched(rows == 8 ? "rt_eclipse_quad<R=8, one ray per lane>" : "rt_eclipse_quad<R=4, one ray per lane>", g.wn, g.ncolumns);
+}
+
+// `cut slant`: the single-wave kernels, each ray its own sums in one lane (ILP-scheduled builds, rt_eclipse_slant_ilp.hip)
+template <int INTEG>
+bool launch_form_slant(const SpecLaunch &c) {
+  const RtArgs &b = c.b;
+  const int nwg = c.workgroups(b.ntiles);
+  const size_t lds = c.sh + c.shp;
+  return (launch_rt_slant(b, INTEG, c.sq, c.block, nwg, lds, c.st, c.err) ||
+          (rtc_single_wave_ok(b) &&
+           (INTEG == kIntegSimpson
+                ? rtc_try(c.info, true, dim3(nwg), dim3(c.block), lds, c.st, b, c.err, "rt_eclipse_simpson_slant<5, %d, %d, %s, %d>",
+                          b.M, b.C, tf(c.sq), slant_sched(b.M, b.C, 1))
+                : rtc_try(c.info, true, dim3(nwg), dim3(c.block), lds, c.st, b, c.err, "rt_eclipse_fast<5, %d, %d, %s, %d, 1, false, true>",
+                          b.M, b.C, tf(c.sq), INTEG)))) &&
+         c.launched(INTEG == kIntegSimpson ? "rt_eclipse_simpson_slant (ILP-scheduled build)" : "rt_eclipse_fast<SLANT> (ILP-scheduled build)",
+                    c.block, b.ntiles);
+}
+
+// `cut vertical`: rt_eclipse_quad, R = 4 / 8 rows of 16 / 8 wavenumbers
+template <int INTEG>
+bool launch_form_quad(const SpecLaunch &c, int rows) {
+  const LpGeom g = lp_geom(c, rows, 64 / rows);
+  const RtArgs &b = g.b;
+  return (dispatch_mc(b.M, b.C, c.sq, [&](auto m, auto cc, auto sq) {
+            constexpr int M = decltype(m)::value, C = decltype(cc)::value;
+            constexpr bool SQ = decltype(sq)::value;
+            c.run(rows == 8 ? rt_eclipse_quad<5, M, C, SQ, 8, INTEG> : rt_eclipse_quad<5, M, C, SQ, 4, INTEG>, g.nwg, 256, g.lds, b);
+          }) ||
+          rtc_try(c.info, false, dim3(g.nwg), dim3(256), g.lds, c.st, b, c.err, "rt_eclipse_quad<5, %d, %d, %s, %d, %d>", b.M, b.C,
+                  tf(c.sq), rows, INTEG)) &&
+         c.launched(rows == 8 ? "rt_eclipse_quad<R=8>" : "rt_eclipse_quad<R=4>", g.wn, g.ncolumns);
+}
+
+// `cut vertical`, rules 0 / 2: rt_eclipse_split, a producer / consumer pair of waves per 64 wavenumbers
+template <int INTEG>
+bool launch_form_split(const SpecLaunch &c) {
+  RtArgs b = c.b;
+  b.ntiles = (b.W + 63) / 64;
+  const int nwg = c.workgroups(b.ntiles);
+  const size_t lds = c.sh + sizeof(double) * (1024 + 2 + 64) + c.shp;   // + the hand-off ring, the exit flags, the deck terms
+  return (dispatch_mc(b.M, b.C, c.sq, [&](auto m, auto cc, auto sq) {
+            c.run(rt_eclipse_split<5, decltype(m)::value, decltype(cc)::value, decltype(sq)::value, INTEG>, nwg, 128, lds, b);
+          }) ||
+          rtc_try(c.info, false, dim3(nwg), dim3(128), lds, c.st, b, c.err, "rt_eclipse_split<5, %d, %d, %s, %d>", b.M, b.C, tf(c.sq), INTEG)) &&
+         c.launched("rt_eclipse_split", 64, b.ntiles);
+}
+
+// `cut vertical`: the single-wave kernels.  ilp: rule 0 in its ILP-scheduled build (rt_eclipse_i0_ilp.hip).
+template <int INTEG>
+bool launch_form_single(const SpecLaunch &c, bool ilp) {
+  const RtArgs &b = c.b;
+  const int nwg = c.workgroups(b.ntiles);
+  const size_t lds = c.sh + c.shp;
   if constexpr (INTEG == kIntegSimpson) {
     // rule 1 has its own single-wave kernel (rt_eclipse_s1.hpp), built under the ILP schedule
     // only: that build is the faster one at every batch size (10 walkers 73 against 80 us,
     // 64: 333 / 375, 256: 1 138 / 1 220 -- the default schedule needs 182 registers for two
     // resident waves, or drops the record read-ahead for three and waits on LDS instead)
-    if (info) info->kernel = "rt_eclipse_simpson (ILP-scheduled build)";
-    if (launch_rt_simpson_ilp(b, sq, block, nblocks1, sh1, st, err)) return true;
-    if (rtc_single_wave_ok(a) && rtc_try(info, true, dim3(nblocks1), dim3(block), sh1, st, b, err, "rt_eclipse_simpson<5, %d, %d, %s, 1>", a.M, a.C, tf(sq))) return true;
+    return (launch_rt_simpson_ilp(b, c.sq, c.block, nwg, lds, c.st, c.err) ||
+            (rtc_single_wave_ok(b) && rtc_try(c.info, true, dim3(nwg), dim3(c.block), lds, c.st, b, c.err,
+                                              "rt_eclipse_simpson<5, %d, %d, %s, 1>", b.M, b.C, tf(c.sq)))) &&
+           c.launched("rt_eclipse_simpson (ILP-scheduled build)", c.block, b.ntiles);
   } else {
-    if (INTEG == kIntegTransmittance && ilp) {
-      if (info) info->kernel = "rt_eclipse_fast (ILP-scheduled build)";
-      if (launch_rt_fast_ilp(b, sq, block, nblocks1, sh1, st, err)) return true;
+    ilp = ilp && INTEG == kIntegTransmittance;
+    return ((ilp && launch_rt_fast_ilp(b, c.sq, c.block, nwg, lds, c.st, c.err)) ||
+            dispatch_mc(b.M, b.C, c.sq, [&](auto m, auto cc, auto sq) {
+              c.run(rt_eclipse_fast<5, decltype(m)::value, decltype(cc)::value, decltype(sq)::value, INTEG>, nwg, c.block, lds, b);
+            }) ||
+            (rtc_single_wave_ok(b) && rtc_try(c.info, false, dim3(nwg), dim3(c.block), lds, c.st, b, c.err,
+                                              "rt_eclipse_fast<5, %d, %d, %s, %d>", b.M, b.C, tf(c.sq), INTEG))) &&
+           c.launched(ilp ? "rt_eclipse_fast (ILP-scheduled build)" : "rt_eclipse_fast", c.block, b.ntiles);
+  }
+}
+
+// Launches the specialised kernel for this shape and batch size under rule INTEG; false: the shape has none (the caller
+// falls back to the generic kernel).  mode: the form BARTRT_KERNEL forces (KernelMode::kDefault: the choice by shape and
+// batch size).  info (optional): what was launched.
+// fold (optional): the preparation of this launch's walkers, NOT yet launched -- only the kernels that can run it in
+// their own prologue (the all-rays layer-parallel forms of rule 1 under `cut slant`) are considered then, and false
+// means "launch the preparation, then call again without it".
+template <int INTEG>
+bool launch_rt_spec(const RtArgs &a, int block, hipStream_t st, KernelMode mode, bool force_window, bool allow_sq,
+                    hipError_t &err, RtLaunchInfo *info, const PrepArgs *fold = nullptr) {
+  if (fold && (INTEG != kIntegSimpson || !a.cut_slant || a.A != 5 || a.ext || a.intens_out || a.tau_out || a.nprep != 0)) return false;
+  SpecLaunch c(a,
+               sizeof(double) * ((size_t)a.L * coef_stride(a.M, a.C) + integ_lds_doubles<INTEG>(a.L)) +
+                   sizeof(idx_t) * (size_t)a.L * idx_stride(a.C),
+               block, st, err, info, fold);
+  err = hipSuccess;
+  // (the specialised kernels rebuild their buffer descriptor per layer, so the
+  // table may be of any size; one layer's pair of planes must stay below 4 GB)
+  const bool fits = 2ull * a.M * a.W * 8ull < (1ull << 31) && c.sh <= 55 * 1024;
+
+  // line-by-line input: rules 0 and 1, no table (anything else takes the generic kernel)
+  if (a.ext) {
+    if (!(INTEG != kIntegTrapzTau && a.A == 5 && a.M == 0 && (a.C <= 2 || a.C == 4) && !a.intens_out && !a.tau_out &&
+          c.sh <= 55 * 1024))
+      return false;
+    c.order_angles(allow_sq);
+    return launch_form_ext<INTEG>(c);
+  }
+  // tau / intensity outputs: the default conventions' slant kernel at one walker, the generic kernel otherwise
+  if (a.intens_out || a.tau_out)
+    return INTEG == kIntegSimpson && a.cut_slant && a.A == 5 && a.slog && a.nwalkers == 1 && a.nprep == 0 && fits &&
+           mode == KernelMode::kDefault && launch_form_slant_out(c);
+  if (!fits) return false;
+  // (the event log serves rule 1's single-wave slant kernels only -- rt_eclipse_s1s.hpp; rule 2 on other ray grids:
+  // generic kernel)
+  if (a.cut_slant && ((INTEG == kIntegSimpson && !a.slog) || (INTEG == kIntegTrapzTau && a.A != 5))) return false;
+  if (info) info->prep_fused = a.nprep > 0;
+
+  // other ray-grid sizes: the single-wave kernel of rule 0 / rule 1 at every batch size
+  if (a.A != 5)
+    return INTEG != kIntegTrapzTau && a.A >= 1 && a.A <= kMaxAngles && mode != KernelMode::kQuad && mode != KernelMode::kOcto &&
+           mode != KernelMode::kSplit && launch_form_angles<INTEG>(c);
+
+  // five ray angles: too few single-wave columns to load the 1 024 SIMDs evenly -> several waves per 64 wavenumbers
+  c.order_angles(allow_sq);
+  c.b.window = a.kappa_bytes >= (1ull << 32) - 4096 || force_window;
+  const bool dflt = mode == KernelMode::kDefault;
+  const long columns = (long)c.nsel * (((a.Wfull > 0 ? a.Wfull : a.W) + 63) / 64);   // (of the whole grid: RtArgs::Wfull)
+  const bool octo = mode == KernelMode::kOcto || (dflt && columns <= kOctoMaxColumns);
+  const bool fits32 = c.addressable(octo ? 8 : 4);
+  if (a.cut_slant) {
+    if constexpr (INTEG == kIntegSimpson) {
+      // rule 1: the layer-parallel walk with all rays per lane, forced or where the measured table (kernel_table.inc) names
+      // it -- rows on adjacent lanes (rt_eclipse_qadj; BARTRT_KERNEL=adj8 / adj16 force it, BARTRT_ADJ=0 switches it off),
+      // else across lane rows (rt_eclipse_quad<..., ALLR>, the entry's fallback should the adjacent form not launch)
+      static const int adj_env = [] { const char *v = std::getenv("BARTRT_ADJ"); return v && *v ? atoi(v) : -1; }();
+      const KernelChoice &entry = slant_simpson_choice(a.M, columns);
+      const bool adj_named = entry.variant == kVarAdj16 || entry.variant == kVarAdj8;
+      const int other = adj_named ? entry.fallback : entry.variant;
+      int rows = mode == KernelMode::kQuad ? 4 : mode == KernelMode::kOcto ? 8 : mode == KernelMode::kHexa ? 16
+                 : mode == KernelMode::kR32 ? 32 : other == kVarSingle ? 4 : other;
+      while (rows > 4 && c.b.window && !window_fits(a, rows)) rows /= 2;
+      int adj_rows = mode == KernelMode::kAdj8 ? 8 : mode == KernelMode::kAdj16 ? 16 : 0;
+      if (dflt && adj_env != 0 && adj_named) adj_rows = entry.variant == kVarAdj16 ? 16 : 8;
+      if (adj_rows && c.addressable(adj_rows)) {
+        const LpGeom g = lp_geom(c, adj_rows, 64 / adj_rows);
+        if (fold && !g.folds) return false;
+        if (launch_form_qadj(c, g, adj_rows)) return true;
+      }
+      const bool lp_forced = mode == KernelMode::kQuad || mode == KernelMode::kOcto || mode == KernelMode::kHexa ||
+                             mode == KernelMode::kR32 || mode == KernelMode::kAdj8 || mode == KernelMode::kAdj16;
+      if ((lp_forced || (dflt && other != kVarSingle)) && c.addressable(rows)) {
+        const LpGeom g = lp_geom(c, rows, 64 / rows);
+        if (fold && !g.folds) return false;
+        if (launch_form_quad_allr<INTEG>(c, g, rows)) return true;
+      }
+      if (fold) return false;   // (no kernel that prepares its own walkers serves this launch: the caller launches prep_profiles)
+    } else if ((mode == KernelMode::kQuad || mode == KernelMode::kOcto || (dflt && columns <= kQuadRaysMaxColumns)) && fits32) {
+      // rules 0 / 2: one ray per lane for the launches that leave the chip mostly idle, eight rows for the smallest
+      if (launch_form_quad_rays<INTEG>(c, mode == KernelMode::kOcto || (dflt && columns <= kOctoRaysMaxColumns) ? 8 : 4)) return true;
     }
-#define BARTRT_FAST(MM, CC)                                                                                        \
-  if (a.M == MM && a.C == CC) {                                                                                    \
-    if (sq) BARTRT_RT_LAUNCH((rt_eclipse_fast<5, MM, CC, SQOK, INTEG>), dim3(nblocks1), dim3(block), sh1, st, b); \
-    else BARTRT_RT_LAUNCH((rt_eclipse_fast<5, MM, CC, false, INTEG>), dim3(nblocks1), dim3(block), sh1, st, b);   \
-    err = hipGetLastError();                                                                                       \
-    return true;                                                                                                   \
+    return launch_form_slant<INTEG>(c);
   }
-    BARTRT_MC_LIST(BARTRT_FAST)
-#undef BARTRT_FAST
-    if (rtc_single_wave_ok(a) && rtc_try(info, false, dim3(nblocks1), dim3(block), sh1, st, b, err, "rt_eclipse_fast<5, %d, %d, %s, %d>", a.M, a.C, tf(sq), INTEG)) return true;
+  // `cut vertical`: quad-layer while the columns leave SIMDs empty, the producer / consumer pair (rules 0 / 2) for the first
+  // columns that have to share one, single-wave beyond (the measurements at the top of this file)
+  constexpr long quad_max = INTEG == kIntegSimpson ? kQuadMaxColumnsSimpson : kQuadMaxColumns;
+  if ((mode == KernelMode::kQuad || mode == KernelMode::kOcto || (dflt && columns <= quad_max)) && fits32 &&
+      launch_form_quad<INTEG>(c, octo ? 8 : 4))
+    return true;
+  if constexpr (INTEG != kIntegSimpson) {
+    if ((mode == KernelMode::kSplit || (dflt && columns >= kSplitMinColumns && columns <= kSplitMaxColumns)) &&
+        launch_form_split<INTEG>(c))
+      return true;
   }
-  return false;
+  return launch_form_single<INTEG>(c, mode != KernelMode::kMonoOcc && (mode == KernelMode::kMonoIlp || columns < kIlpMaxColumns));
 }
 
 #endif  // !__HIPCC_RTC__

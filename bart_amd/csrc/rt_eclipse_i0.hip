@@ -4,6 +4,6 @@
 #include "rt_eclipse.hpp"
 
 namespace bartrt {
-template bool launch_rt_spec<0>(const RtArgs &, int, hipStream_t, const std::string &, bool, bool, hipError_t &,
+template bool launch_rt_spec<0>(const RtArgs &, int, hipStream_t, KernelMode, bool, bool, hipError_t &,
                                 RtLaunchInfo *, const PrepArgs *);
 }  // namespace bartrt

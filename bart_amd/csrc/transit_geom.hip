@@ -29,7 +29,6 @@
 #include "kernels.hpp"
 
 #include <cstdlib>
-#include <string>
 
 namespace bartrt {
 
@@ -316,10 +315,7 @@ hipError_t launch_transit(const RtArgs &a, hipStream_t st) {
                                       (size_t)a.L * idx_stride(a.C) + (size_t)a.L * 64);
   const size_t sh_pairs = sizeof(double) * (size_t)a.L * 64;
   if (sh_pairs > 160 * 1024) return hipErrorInvalidValue;  // more than 320 layers
-  static const bool generic_only = [] {
-    const char *e = std::getenv("BARTRT_KERNEL");
-    return e && std::string(e) == "generic";
-  }();
+  const bool generic_only = rt_kernel_mode() == KernelMode::kGeneric;
   static const bool force_window = std::getenv("BARTRT_WINDOW") != nullptr;  // (tests)
   const bool window = a.kappa_bytes >= (1ull << 32) - 4096 || force_window;
   const bool fits32 = a.cia_bytes < (1ull << 32) - 4096 && (!window || window_fits(a, 4));

@@ -178,40 +178,76 @@ def wide_cases(tmp_path_factory):
             for nm in (6, 8)}
 
 
-@pytest.mark.parametrize("integ", [0, 1, 2])
-@pytest.mark.parametrize("mode", ["generic", "mono_occ", "mono_ilp", "split", "quad", "octo"])
+def forced_kernel(mode, integ, cut, single_wave=True):
+    """The kernel BARTRT_KERNEL=mode launches under rule `integ` and `cut` (RtLaunchInfo::kernel, csrc/rt_eclipse.hpp).
+    single_wave: the shape has single-wave builds (at most 20 table loads per layer, 2 M + 2 C; wider shapes leave
+    those forms to the generic kernel)."""
+    if mode == "generic" or (mode.startswith("mono") and not single_wave):
+        return "rt_eclipse (generic)"
+    if mode in ("quad", "octo"):
+        rows = 4 if mode == "quad" else 8
+        if cut == "vertical":
+            return "rt_eclipse_quad<R=%d>" % rows
+        return "rt_eclipse_quad<R=%d, %s per lane>" % (rows, "all rays" if integ == 1 else "one ray")
+    if mode == "split":
+        return "rt_eclipse_split"
+    if cut == "slant":
+        return "rt_eclipse_simpson_slant (ILP-scheduled build)" if integ == 1 else "rt_eclipse_fast<SLANT> (ILP-scheduled build)"
+    if integ == 1:
+        return "rt_eclipse_simpson (ILP-scheduled build)"
+    return "rt_eclipse_fast (ILP-scheduled build)" if (mode == "mono_ilp" and integ == 0) else "rt_eclipse_fast"
+
+
+# (the producer / consumer split exists for rules 0 and 2 under `cut vertical` only)
+@pytest.mark.parametrize("mode,integ", [(m, i) for m in ("generic", "mono_occ", "mono_ilp", "split", "quad", "octo")
+                                        for i in (0, 1, 2) if (m, i) != ("split", 1)])
 def test_every_kernel_variant_matches_oracle(small_case, wide_cases, mode, integ):
-    """The RT kernels (generic fallback, single-wave specialised, producer/consumer
-    split, quad-layer with four and with eight lane rows) under each integration
+    """The RT kernels (generic fallback, single-wave specialised in its default and ILP-scheduled builds,
+    producer/consumer split, quad-layer with four and with eight lane rows) under each integration
     rule (0 transmittance trapezoid, 1 the Simpson hybrid of SURVEY App. A-4, 2
-    trapezoid in tau; oracle/rt_oracle.c column_eclipse) on the same batches --
+    trapezoid in tau; oracle/rt_oracle.c column_eclipse) and each cut (`cut slant`: the per-ray forms
+    of the single-wave and layer-parallel kernels; `cut vertical`; the split only there) on the same batches --
     four molecules + one CIA pair, six + two, eight + two -- without and with an
     opaque cloud deck (its surface term takes a different route in each kernel),
     and with `toomuch` lowered so the cut (and rule 1's padded point) falls in the
     middle of the column.  BARTRT_KERNEL is read once per process, so each variant
-    runs in a child; the rule travels as BARTRT_INTEG."""
-    import subprocess, sys, os
+    runs in a child; the rule travels as BARTRT_INTEG.  The child reports the kernel
+    each batch launched: it must be the forced form."""
+    import json, subprocess, sys, os
     from oracle import rt_oracle as orc
     cases = [small_case, wide_cases[6], wide_cases[8]]
+    cuts = ("vertical",) if mode == "split" else ("slant", "vertical")
     jobs = []
     for c in cases:
         profs = walkers(c, 5, seed=8)
         np.save(os.path.join(c.dir, "p.npy"), profs)
-        jobs.append((os.path.join(c.dir, "p.npy"), c.tcfg, os.path.join(c.dir, "s_%s_%d.npy" % (mode, integ))))
-    code = ("import numpy as np, sys; sys.path.insert(0, %r)\n"
+        for cut in cuts:
+            jobs.append((os.path.join(c.dir, "p.npy"), c.tcfg, cut, os.path.join(c.dir, "s_%s_%d_%s.npy" % (mode, integ, cut))))
+    code = ("import json, numpy as np, sys; sys.path.insert(0, %r)\n"
             "from bart_amd import engine, transit_module as trm\n"
-            "for pfile, tcfg, out in %r:\n"
+            "names = []\n"
+            "for pfile, tcfg, cut, out in %r:\n"
             "    p = np.load(pfile); engine.init(tcfg); assert trm.get_integ() == %d\n"
-            "    a = engine.run_batch(p)\n"
-            "    trm.set_cloudtop(-1.0); b = engine.run_batch(p)\n"
-            "    np.save(out, np.array([a, b])); trm.free_memory()\n"
+            "    trm.set_cut(cut); assert trm.get_cut() == cut\n"
+            "    engine.walked_begin(); a = engine.run_batch(p); ka = engine.walked_end()[2]\n"
+            "    trm.set_cloudtop(-1.0)\n"
+            "    engine.walked_begin(); b = engine.run_batch(p); kb = engine.walked_end()[2]\n"
+            "    np.save(out, np.array([a, b])); names.append([ka, kb, trm.get_cia_interp()]); trm.free_memory()\n"
+            "print('KERNELS' + json.dumps(names))\n"
             % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), jobs, integ))
-    subprocess.check_call([sys.executable, "-c", code],
-                          env=dict(os.environ, BARTRT_KERNEL=mode, BARTRT_INTEG=str(integ)), timeout=600)
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, BARTRT_KERNEL=mode, BARTRT_INTEG=str(integ)),
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    names = json.loads([l for l in r.stdout.splitlines() if l.startswith("KERNELS")][0][7:])
     others = []
-    for c, (pfile, _, out) in zip(cases, jobs):
+    for (pfile, tcfg, cut, out), (ka, kb, interp) in zip(jobs, names):
+        c = cases[[x.tcfg for x in cases].index(tcfg)]
+        nslot = len(c.cia) * (2 if interp == "spline" else 1)     # (CIA table slots: two per file under the spline)
+        want = forced_kernel(mode, integ, cut, single_wave=2 * len(c.opmol) + 2 * nslot <= 20)
+        # (the name without its notes: "[instantiated at run time]", "[prepares its own walkers]")
+        assert ka.split(" [")[0] == want and kb.split(" [")[0] == want, (cut, len(c.opmol), nslot, ka, kb)
         profs, got = np.load(pfile), np.load(out)
-        o = orc.OracleEngine(c.tcfg, integ=integ)
+        o = orc.OracleEngine(tcfg, integ=integ, cut=cut)
         np.testing.assert_allclose(got[0], o.run_batch(profs), rtol=RTOL)
         o.set_cloudtop(-1.0)
         np.testing.assert_allclose(got[1], o.run_batch(profs), rtol=RTOL)

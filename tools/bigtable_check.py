@@ -3,8 +3,8 @@ the row-per-layer kernels; the device re-layout of a big table): 100 layers x 27
 temperatures x 4 molecules x 52 000 samples = 4.49 GB, eclipse and transit geometry,
 1 / 3 / 12 walkers (quad-layer, single-wave, MFMA transit kernels) against the oracle.
     python tools/bigtable_check.py [eclipse|transit|both]         (GPU box; ~2 min, 5 GB of /tmp per geometry)
-BARTRT_KERNEL in the environment forces a kernel variant (quad: under the default `cut slant` the one-ray-per-lane
-kernel with its moving window; team: the three-wave column team).
+BARTRT_KERNEL in the environment forces a kernel variant (quad: under the default conventions the all-rays
+layer-parallel kernel with four rows and its moving window).
 Uses the oracle: a test driver, not part of the product."""
 import os
 import sys
