@@ -853,7 +853,11 @@ void Engine::run_chunk(const double *d_prof_in, int n, double *d_spec_out,
     walked_nwalkers = n;
   }
   if (lbl_fused) lbl_rt_eclipse(*this, d_prof_in, n, r, st);
-  else if (solution == 1) HIPCHK(launch_transit(r, st));
+  else if (solution == 1) {
+    RtLaunchInfo li;   // (the transit kernels keep no walked-layer record: the name only)
+    HIPCHK(launch_transit(r, st, &li));
+    if (want_walked) walked_info = li;
+  }
   else {
     RtLaunchInfo li;
     bool folded = false;

@@ -13,7 +13,8 @@ namespace bartrt {
 hipError_t launch_prep(const PrepArgs &a, hipStream_t st);
 hipError_t launch_rt(const RtArgs &a, int block, hipStream_t st, RtLaunchInfo *info = nullptr);
 hipError_t launch_rt_folded(const RtArgs &a, const PrepArgs &prep, int block, hipStream_t st, RtLaunchInfo *info, bool *folded);
-hipError_t launch_transit(const RtArgs &a, hipStream_t st);
+// info (optional): what was launched (its name; window: the matrix-tile kernel read the table through the moving window)
+hipError_t launch_transit(const RtArgs &a, hipStream_t st, RtLaunchInfo *info = nullptr);
 hipError_t launch_chord_table(const PrepArgs &a, hipStream_t st);  // transit geometry, after launch_prep
 hipError_t launch_grid_transpose(const double *src, double *dst, long planes, int M, int W, hipStream_t st);
 

@@ -287,6 +287,7 @@ struct RtLaunchInfo {
   bool prep_fused = false;  // the launch carried RtArgs::nprep workgroups of the next batch's preparation
   bool prep_folded = false; // the kernel prepared its own walkers' layer records (RtArgs::nprep < 0): no prep_profiles launch
   bool rtc = false;         // the kernel was instantiated at run time (rtc.hpp), not taken from the ahead-of-time set
+  bool window = false;      // a row-per-layer kernel addressed the table through the moving window (RtArgs::window)
 };
 
 #ifndef __HIPCC_RTC__

@@ -979,8 +979,12 @@ struct SpecLaunch {
     err = hipGetLastError();
   }
   // the form launched: what RtLaunchInfo records of it
-  bool launched(const char *kernel, int wn_per_column, int ncolumns, bool folded = false) const {
-    if (info) { info->kernel = kernel; info->wn_per_column = wn_per_column; info->ncolumns = ncolumns; info->prep_folded = folded; }
+  // (window: the layer-parallel forms pass their RtArgs::window)
+  bool launched(const char *kernel, int wn_per_column, int ncolumns, bool folded = false, bool window = false) const {
+    if (info) {
+      info->kernel = kernel; info->wn_per_column = wn_per_column; info->ncolumns = ncolumns; info->prep_folded = folded;
+      info->window = window;
+    }
     return true;
   }
 };
@@ -1076,7 +1080,7 @@ inline bool launch_form_qadj(const SpecLaunch &c, const LpGeom &g, int rows) {
           rtc_try(c.info, false, dim3(g.nwg), dim3(256), g.lds, c.st, b, c.err, "rt_eclipse_qadj<5, %d, %d, %s, %d>", b.M, b.C,
                   tf(c.sq), rows)) &&
          c.launched(rows == 16 ? "rt_eclipse_qadj<R=16> (rows on adjacent lanes)" : "rt_eclipse_qadj<R=8> (rows on adjacent lanes)",
-                    g.wn, g.ncolumns, g.folds);
+                    g.wn, g.ncolumns, g.folds, b.window != 0);
 }
 
 // rule 1 / `cut slant`: rt_eclipse_quad<..., ALLR>, all rays per lane (R = 4 / 8 / 16 / 32)
@@ -1099,7 +1103,7 @@ bool launch_form_quad_allr(const SpecLaunch &c, const LpGeom &g, int rows) {
                     : rows == 16 ? "rt_eclipse_quad<R=16, all rays per lane>"
                     : rows == 8  ? "rt_eclipse_quad<R=8, all rays per lane>"
                                  : "rt_eclipse_quad<R=4, all rays per lane>",
-                    g.wn, g.ncolumns, g.folds);
+                    g.wn, g.ncolumns, g.folds, b.window != 0);
 }
 
 // rules 0 / 2, `cut slant`: rt_eclipse_quad<..., RAYS>, one ray per lane (R = 4 / 8: three wavenumbers / one x five rays
@@ -1116,7 +1120,8 @@ bool launch_form_quad_rays(const SpecLaunch &c, int rows) {
           }) ||
           rtc_try(c.info, false, dim3(g.nwg), dim3(256), g.lds, c.st, b, c.err, "rt_eclipse_quad<5, %d, %d, false, %d, %d, true>",
                   b.M, b.C, rows, INTEG)) &&
-         c.launched(rows == 8 ? "rt_eclipse_quad<R=8, one ray per lane>" : "rt_eclipse_quad<R=4, one ray per lane>", g.wn, g.ncolumns);
+         c.launched(rows == 8 ? "rt_eclipse_quad<R=8, one ray per lane>" : "rt_eclipse_quad<R=4, one ray per lane>", g.wn, g.ncolumns,
+                    false, b.window != 0);
 }
 
 // `cut slant`: the single-wave kernels, each ray its own sums in one lane (ILP-scheduled builds, rt_eclipse_slant_ilp.hip)
@@ -1148,7 +1153,7 @@ bool launch_form_quad(const SpecLaunch &c, int rows) {
           }) ||
           rtc_try(c.info, false, dim3(g.nwg), dim3(256), g.lds, c.st, b, c.err, "rt_eclipse_quad<5, %d, %d, %s, %d, %d>", b.M, b.C,
                   tf(c.sq), rows, INTEG)) &&
-         c.launched(rows == 8 ? "rt_eclipse_quad<R=8>" : "rt_eclipse_quad<R=4>", g.wn, g.ncolumns);
+         c.launched(rows == 8 ? "rt_eclipse_quad<R=8>" : "rt_eclipse_quad<R=4>", g.wn, g.ncolumns, false, b.window != 0);
 }
 
 // `cut vertical`, rules 0 / 2: rt_eclipse_split, a producer / consumer pair of waves per 64 wavenumbers

@@ -309,7 +309,7 @@ static hipError_t allow_lds(K kernel, size_t bytes, size_t &allowed) {
   return e;
 }
 
-hipError_t launch_transit(const RtArgs &a, hipStream_t st) {
+hipError_t launch_transit(const RtArgs &a, hipStream_t st, RtLaunchInfo *info) {
   if (a.nwalkers <= 0 || a.W <= 0) return hipSuccess;
   const size_t sh = sizeof(double) * ((size_t)a.L * coef_stride(a.M, a.C) +
                                       (size_t)a.L * idx_stride(a.C) + (size_t)a.L * 64);
@@ -325,6 +325,7 @@ hipError_t launch_transit(const RtArgs &a, hipStream_t st) {
     RtArgs b = a;
     b.window = 0;
     b.ntiles = (a.W + 63) / 64;
+    if (info) { *info = RtLaunchInfo{}; info->kernel = "rt_transit_mfma (line-by-line extinction)"; }
     const int nb = (b.ntiles + 7) / 8 * 8 * a.nwalkers;
     const size_t shm = sizeof(double) * ((size_t)a.L * coef_stride(0, a.C) + (size_t)a.L * idx_stride(a.C) + (size_t)a.L);
 #define BARTRT_TRANSIT_EXT(CC)                                                                       \
@@ -348,6 +349,8 @@ hipError_t launch_transit(const RtArgs &a, hipStream_t st) {
     RtArgs b = a;
     b.window = window;
     b.ntiles = (a.W + 63) / 64;
+    // (recorded ahead of the dispatch below; a pair outside the list falls through to the scalar kernel, which records itself)
+    if (info) { *info = RtLaunchInfo{}; info->kernel = "rt_transit_mfma"; info->window = window; }
     const int nb = (b.ntiles + 7) / 8 * 8 * a.nwalkers;
     const size_t shm = shm_tab;
 #define BARTRT_TRANSIT(MM, CC)                                                              \
@@ -368,6 +371,7 @@ hipError_t launch_transit(const RtArgs &a, hipStream_t st) {
   RtArgs b = a;
   b.ntiles = (a.W + 63) / 64;
   const int nb = (b.ntiles + 7) / 8 * 8 * a.nwalkers;
+  if (info) { *info = RtLaunchInfo{}; info->kernel = "rt_transit"; }   // (64-bit addressing: no window)
   static size_t allowed = 48 * 1024, allowed_pairs = 48 * 1024;
   if (sh <= 160 * 1024) {
     hipError_t e = allow_lds(rt_transit<true>, sh, allowed);

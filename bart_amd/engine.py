@@ -404,19 +404,20 @@ def timing_end():
 
 
 def walked_begin():
-    """Record, for the eclipse launches that follow, how many layers each wave walks."""
+    """Record, for the eclipse launches that follow, how many layers each wave walks (transit launches: the kernel
+    name only)."""
     _check(trm.lib().bartrt_walked_begin())
 
 
 def walked_end():
     """-> (walked[nwalkers, ncolumns], wavenumbers per column, kernel name) of the last launch."""
     n, nc, wpc = C.c_int(), C.c_int(), C.c_int()
-    name = C.create_string_buffer(128)
-    _check(trm.lib().bartrt_walked_end(None, 0, C.byref(n), C.byref(nc), C.byref(wpc), name, 128))
+    name = C.create_string_buffer(256)   # (the name and its notes)
+    _check(trm.lib().bartrt_walked_end(None, 0, C.byref(n), C.byref(nc), C.byref(wpc), name, 256))
     # the record itself (the first call switched recording off; the buffer stays)
     out = np.zeros((n.value, nc.value), np.int32)
     if out.size:
-        _check(trm.lib().bartrt_walked_end(_ptr(out), out.size, C.byref(n), C.byref(nc), C.byref(wpc), name, 128))
+        _check(trm.lib().bartrt_walked_end(_ptr(out), out.size, C.byref(n), C.byref(nc), C.byref(wpc), name, 256))
     return out, wpc.value, name.value.decode()
 
 

@@ -380,7 +380,8 @@ int bartrt_timing_end(double *kernel_ms, int *nlaunch);
  * launch records how many layers each wave walked before all its lanes passed
  * `toomuch`.  end returns the record of the LAST launch: walked[nwalkers][ncolumns]
  * (columns of wn_per_column consecutive wavenumbers, as the launched kernel tiles
- * the grid) and that kernel's name. */
+ * the grid) and that kernel's name.  A transit launch records its kernel's name only
+ * (no walkers, no columns). */
 int bartrt_walked_begin(void);
 int bartrt_walked_end(int *walked, int cap, int *nwalkers, int *ncolumns, int *wn_per_column,
                       char *kernel, int kernel_len);
@@ -390,7 +391,9 @@ int bartrt_walked_end(int *walked, int cap, int *nwalkers, int *ncolumns, int *w
  * libhiprtc: the generic kernel serves them, 3-10x slower).  *available: a compiler is at hand; kernels compiled /
  * loaded from the disk cache / failed by this process so far, and the seconds spent compiling.  bartrt_walked_end's
  * kernel name carries " [instantiated at run time]" for such a launch (and " [prepares its own walkers]" where a
- * few-walker launch built its layer records in its own prologue instead of a preparation launch: BARTRT_FOLD=0 off).  Pointers may be NULL. */
+ * few-walker launch built its layer records in its own prologue instead of a preparation launch: BARTRT_FOLD=0 off;
+ * " [table through a moving window]" where a row-per-layer kernel addressed a table of 4 GB or more, or any table under
+ * BARTRT_WINDOW, through its per-step window).  Pointers may be NULL. */
 int bartrt_get_rtc_stats(int *available, int *compiled, int *from_disk, int *failed, double *compile_seconds);
 /* Compiles bartrt::<expr> (a template-id of the kernel headers, e.g. "rt_eclipse_simpson_slant<5, 9, 4, true, 1>")
  * for gfx950 and discards the result: *code_bytes = the code object's size.  Needs no GPU -- a check that the embedded

@@ -184,6 +184,11 @@ def forced_kernel(mode, integ, cut, single_wave=True):
     those forms to the generic kernel)."""
     if mode == "generic" or (mode.startswith("mono") and not single_wave):
         return "rt_eclipse (generic)"
+    # (the rows-on-adjacent-lanes form and the 16 / 32-row all-rays forms: rule 1 under `cut slant` only)
+    if mode in ("adj8", "adj16"):
+        return "rt_eclipse_qadj<R=%s> (rows on adjacent lanes)" % mode[3:]
+    if mode in ("hexa", "r32"):
+        return "rt_eclipse_quad<R=%d, all rays per lane>" % (16 if mode == "hexa" else 32)
     if mode in ("quad", "octo"):
         rows = 4 if mode == "quad" else 8
         if cut == "vertical":

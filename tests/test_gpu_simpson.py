@@ -40,10 +40,13 @@ def check(cfg, profs, what, clouds=(None,)):
         o = orc.OracleEngine(cfg, integ=INTEG, cut=CUT)
         if CUT == "slant":          # the per-ray cut runs its own single-wave kernels, not the generic one
             engine.walked_begin(); engine.run_batch(profs); kname = engine.walked_end()[2]
-            assert "slant" in kname.lower() or "per lane" in kname, kname
             km = os.environ.get("BARTRT_KERNEL")
-            assert ("per lane" in kname) == (km in ("quad", "octo", "hexa", "r32")), kname
-            assert ("all rays per lane" in kname) == (km in ("quad", "octo", "hexa", "r32") and INTEG == 1), kname
+            if km in ("adj8", "adj16"):     # rt_eclipse_qadj: the rows of a column on adjacent lanes
+                assert INTEG == 1 and kname.startswith("rt_eclipse_qadj<R=%%s> " %% km[3:]), kname
+            else:
+                assert "slant" in kname.lower() or "per lane" in kname, kname
+                assert ("per lane" in kname) == (km in ("quad", "octo", "hexa", "r32")), kname
+                assert ("all rays per lane" in kname) == (km in ("quad", "octo", "hexa", "r32") and INTEG == 1), kname
         for ct in clouds:
             if ct is not None:
                 trm.set_cloudtop(float(ct)); o.set_cloudtop(float(ct))
@@ -57,7 +60,11 @@ def check(cfg, profs, what, clouds=(None,)):
         trm.free_memory()
 
 if mode == "lengths":
-    for L in (2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 29, 30, 31, 32, 100):
+    Ls = [2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 29, 30, 31, 32, 100]
+    if os.environ.get("BARTRT_KERNEL") in ("adj8", "adj16"):
+        # qadj flips its row order on odd steps: columns that end on either parity of an 8 / 16-row step, and just past it
+        Ls += [15, 16, 17, 33, 47, 48, 49]
+    for L in Ls:
         c = synth.make_case(os.path.join(tmp, "L%%d" %% L), nlayers=L, nwave=130)
         profs = walkers(c, 6, seed=L)
         lp = np.log10(c.press_bar)
@@ -99,13 +106,15 @@ print("ok")
 @pytest.mark.parametrize("cut,integ,kernel", [("vertical", 1, "mono_ilp"), ("slant", 1, "mono_ilp"), ("slant", 0, "mono_ilp"),
                                               ("slant", 2, "mono_ilp"), ("slant", 1, "quad"), ("slant", 0, "quad"),
                                               ("slant", 2, "quad"), ("slant", 1, "octo"), ("slant", 1, "hexa"),
-                                              ("slant", 1, "r32")])
+                                              ("slant", 1, "r32"), ("slant", 1, "adj8"), ("slant", 1, "adj16")])
 @pytest.mark.parametrize("mode", ["lengths", "cuts", "zero"])
 def test_simpson_single_wave_kernel(tmp_path, mode, cut, integ, kernel):
     """(cut slant: the same sweeps through rt_eclipse_simpson_slant / rt_eclipse_fast<SLANT>, where every ray
     angle ends on its own layer -- the deaths, pads and decks of five rays land on every block position -- and,
     kernel = quad / octo / hexa / r32, through the layer-parallel walk with all rays per lane (rule 1: rt_eclipse_quad<..., ALLR>,
-    4 / 8 / 16 / 32 layers per step) or one ray per lane (rules 0 / 2: <..., RAYS>).)"""
+    4 / 8 / 16 / 32 layers per step) or one ray per lane (rules 0 / 2: <..., RAYS>); kernel = adj8 / adj16, through
+    rt_eclipse_qadj<R=8 / 16> (rt_eclipse_qadj.hpp: rows on adjacent lanes, row order flipped on odd steps), with more
+    column lengths around its step parity.)"""
     env = dict(os.environ, BARTRT_KERNEL=kernel)
     out = subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT}, mode, str(tmp_path), cut, str(integ)],
                          env=env, capture_output=True, text=True, timeout=900)
