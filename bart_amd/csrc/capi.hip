@@ -4,6 +4,7 @@
 #include <string>
 
 #include "../../include/bartrt.h"
+#include "comm.hpp"
 #include "contrib.hpp"
 #include "engine.hpp"
 #include "lbl.hpp"
@@ -42,6 +43,8 @@ static int guarded(F &&f) {
   } catch (const HipError &e) {
     return fail(BARTRT_ENODEV, std::string(e.what) + ": " + hipGetErrorString(e.e));
   } catch (const svc::Error &e) {
+    return fail(e.code, e.msg);
+  } catch (const CommError &e) {
     return fail(e.code, e.msg);
   } catch (const std::exception &e) {
     return fail(BARTRT_EINVAL, e.what());
@@ -134,6 +137,7 @@ std::string what_failed() {
   } catch (const IoError &e) { return e.msg;
   } catch (const HipError &e) { return std::string(e.what) + ": " + hipGetErrorString(e.e);
   } catch (const svc::Error &e) { return e.msg;
+  } catch (const CommError &e) { return e.msg;
   } catch (const std::exception &e) { return e.what();
   } catch (...) { return "unknown error"; }
 }
@@ -152,6 +156,8 @@ void teardown(double wait_s) {
   }
   if (g_eng) {
     (void)hipDeviceSynchronize();
+    comm_destroy(g_eng->comm);   // (before the engine's device state goes)
+    g_eng->comm = nullptr;
     cf_release();   // (the contribution-function tables and workspaces belong to this engine)
     delete g_eng;
     g_eng = nullptr;
@@ -874,6 +880,68 @@ int bartrt_mcmc_run(int nchains, int npars, long nsteps, const double *params, c
   return guarded([&] {
     mcmc_run(*g_eng, nchains, npars, nsteps, params, pmin, pmax, stepsize, ndata, data, uncert,
              snooker, seed, chain, chisq, naccept, nbad);
+    return BARTRT_OK;
+  });
+}
+
+// ---- the ranks' communicator (comm.hip) -----------------------------------
+int bartrt_comm_get_unique_id(void *id) {
+  // (needs no engine: rank 0 may ask before its bartrt_init; a chain-service client gets what every non-reference
+  // call gives it)
+  if (g_cli && !g_eng)
+    return fail(BARTRT_ENOTSUP, "comm_get_unique_id: this process is a client of the shareOpacity chain service");
+  if (!id) return fail(BARTRT_EINVAL, "comm_get_unique_id: null buffer");
+  return guarded([&] {
+    comm_get_unique_id(id);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_comm_init(const void *id, int rank, int nranks) {
+  NEED_ENGINE();
+  Engine *e = g_eng;
+  if (!id) return fail(BARTRT_EINVAL, "comm_init: null id");
+  if (e->comm) return fail(BARTRT_EINVAL, "comm_init: a communicator is already attached (bartrt_comm_free first)");
+  // the engine's block must be block `rank` of `nranks` under the engine's split (an unsharded engine is 0 / 1)
+  if (nranks < 1 || rank < 0 || rank >= nranks || nranks > e->Wfull ||
+      e->lo != (int)((long long)e->Wfull * rank / nranks) || e->hi != (int)((long long)e->Wfull * (rank + 1) / nranks))
+    return fail(BARTRT_EINVAL, "comm_init: rank " + std::to_string(rank) + " of " + std::to_string(nranks) +
+                                   " is not this engine's --shard (it holds samples [" + std::to_string(e->lo) + ", " +
+                                   std::to_string(e->hi) + ") of " + std::to_string(e->Wfull) + ")");
+  return guarded([&] {
+    e->comm = comm_create(e->device, id, rank, nranks);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_comm_free(void) {
+  NEED_ENGINE();
+  return guarded([&] {
+    Comm *c = g_eng->comm;
+    g_eng->comm = nullptr;
+    comm_destroy(c);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_get_comm(int *rank, int *nranks, unsigned long long *ncollectives) {
+  NEED_ENGINE();
+  const Comm *c = g_eng->comm;
+  if (rank) *rank = c ? c->rank : -1;
+  if (nranks) *nranks = c ? c->nranks : 0;
+  if (ncollectives) *ncollectives = g_eng->ncollectives;
+  return BARTRT_OK;
+}
+
+int bartrt_step_bandflux_blocks_dev(const double *d_blocks, int nranks, int nwalkers, int *d_status,
+                                    double *d_bandflux, void *stream) {
+  NEED_ENGINE();
+  if (!g_eng->step) return fail(BARTRT_EINVAL, "step_bandflux_blocks: call bartrt_step_setup first");
+  if (!d_blocks || !d_bandflux || !d_status || nwalkers < 0)
+    return fail(BARTRT_EINVAL, "step_bandflux_blocks: null buffer");
+  return guarded([&] {
+    hipStream_t st = stream ? (hipStream_t)stream : g_eng->stream;
+    step_bandflux_blocks_dev(*g_eng, d_blocks, nranks, nwalkers, d_status, d_bandflux, st);
     return BARTRT_OK;
   });
 }

@@ -26,6 +26,7 @@ int resolve_share_mode(const TCfg &cfg, bool no_service);
 struct TableShare;  // the opacity grid shared between processes (share.hpp)
 struct StepArgs;  // converters around the engine (step.hip)
 struct Lbl;       // line-by-line extinction (lbl.hip)
+struct Comm;      // the ranks' communicator (comm.hpp)
 
 struct Engine {
   // configuration
@@ -150,6 +151,11 @@ struct Engine {
                hipStream_t st, bool want_tau);
   void run_chunk(const double *d_prof_in, int n, double *d_spec_out, unsigned char *d_okp,
                  hipStream_t st, bool want_tau, const double *d_ext, bool lbl_fused = false);
+
+  // bartrt_comm_init: with a communicator the per-step path gathers the ranks' blocks itself (step.hip).  Owned and
+  // destroyed by capi.hip (bartrt_comm_free, bartrt_free_memory, a re-bartrt_init) before the engine goes.
+  Comm *comm = nullptr;
+  unsigned long long ncollectives = 0;  // collectives this engine has issued (kept across bartrt_comm_free)
 };
 
 struct HipError {

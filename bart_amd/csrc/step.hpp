@@ -61,6 +61,13 @@ void step_profiles_dev(Engine &e, const double *d_params, int n, int npars, doub
 // status_out (optional, device-accessible): final status per walker
 void step_bandflux_dev(Engine &e, const double *d_spec_full, int n, int *d_status,
                        double *d_bandflux, hipStream_t st, int *status_out = nullptr);
+// the ranks' blocks as an all-gather leaves them (nranks slots of n * step_block_max doubles, slot r = [n][W_r]) ->
+// bandflux[n][F]: the same terms in the same order as step_bandflux_dev on the reassembled spectra
+size_t step_block_max(int Wfull, int nranks);
+void step_bandflux_blocks_dev(Engine &e, const double *d_blocks, int nranks, int n, int *d_status,
+                              double *d_bandflux, hipStream_t st, int *status_out = nullptr);
+// with a communicator attached (e.comm), the RT block, one all-gather and the block integration; without one the
+// engine must hold the whole grid
 void step_run_dev(Engine &e, const double *d_params, int n, int npars, double *d_bandflux,
                   int *d_status, double *d_spec, hipStream_t st, int *status_out = nullptr);
 void step_run_host(Engine &e, const double *params, int n, int npars, double *bandflux,

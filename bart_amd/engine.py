@@ -392,6 +392,71 @@ def step_batch_sharded(d_params, nfilters, group=None, stream=None, force=False)
     return band, status, spec
 
 
+def step_bandflux_blocks_dev(d_blocks, nranks, d_status, nfilters, stream=None):
+    """Band fluxes [n, nfilters] of the ranks' blocks where an all-gather leaves them: d_blocks a float64 CUDA tensor
+    of nranks slots of n * max(block_sizes) doubles, slot r = [n, W_r] packed rows of block r (include/bartrt.h,
+    bartrt_step_bandflux_blocks_dev).  d_status (int32 [n], from step_profiles_dev) may be set to 3 (energy balance).
+    The same bits as the band integration of the reassembled spectra."""
+    import torch
+    assert d_blocks.is_cuda and d_blocks.dtype == torch.float64 and d_blocks.is_contiguous()
+    assert d_status.is_cuda and d_status.dtype == torch.int32
+    n = d_status.shape[0]
+    assert d_blocks.numel() >= nranks * n * max(block_sizes(trm.get_no_samples(), nranks))
+    band = torch.empty((n, nfilters), dtype=torch.float64, device=d_blocks.device)
+    _check(trm.lib().bartrt_step_bandflux_blocks_dev(
+        C.c_void_p(d_blocks.data_ptr()), int(nranks), n, C.c_void_p(d_status.data_ptr()),
+        C.c_void_p(band.data_ptr()), _stream_ptr(stream)))
+    return band
+
+
+# ---- the library's own communicator (include/bartrt.h, bartrt_comm_*) -------
+COMM_ID_BYTES = 128
+
+
+def comm_unique_id() -> bytes:
+    """Rank 0's part of the bring-up: the id every rank passes to comm_attach."""
+    buf = (C.c_char * COMM_ID_BYTES)()
+    _check(trm.lib().bartrt_comm_get_unique_id(C.cast(buf, C.c_void_p)))
+    return bytes(buf)
+
+
+def comm_attach(uid: bytes, rank: int, nranks: int) -> None:
+    """Every rank, its engine initialised with --shard rank nranks (unsharded: 0 / 1), attaches the communicator
+    named by rank 0's id (a launcher of its own -- MPI, a file -- hands the bytes over)."""
+    assert len(uid) == COMM_ID_BYTES
+    buf = (C.c_char * COMM_ID_BYTES).from_buffer_copy(uid)
+    _check(trm.lib().bartrt_comm_init(C.cast(buf, C.c_void_p), int(rank), int(nranks)))
+
+
+def comm_init(group=None) -> None:
+    """Attaches the library's communicator over the ranks of a torch process group (gloo or nccl): rank 0 makes the
+    id, one broadcast over the group hands its 128 bytes to the others, every rank attaches.  The group's ranks must be
+    the engine's --shard ranks.  Afterwards step_batch / step_batch_dev / sampler.run_native run on the sharded engine
+    with one collective per step, inside the library."""
+    import torch
+    import torch.distributed as dist
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    uid = comm_unique_id() if rank == 0 else bytes(COMM_ID_BYTES)
+    t = torch.tensor(list(uid), dtype=torch.uint8)
+    if dist.get_backend(group) == "nccl":
+        t = t.cuda()
+    src = dist.get_global_rank(group, 0) if group is not None else 0
+    dist.broadcast(t, src=src, group=group)
+    comm_attach(bytes(t.cpu().tolist()), rank, world)
+
+
+def comm_free() -> None:
+    _check(trm.lib().bartrt_comm_free())
+
+
+def comm_info() -> dict:
+    """-> dict(rank, nranks, ncollectives): the attached communicator (rank -1, nranks 0 without one) and the
+    collectives the engine has issued."""
+    r, n, k = C.c_int(0), C.c_int(0), C.c_ulonglong(0)
+    _check(trm.lib().bartrt_get_comm(C.byref(r), C.byref(n), C.byref(k)))
+    return {"rank": r.value, "nranks": n.value, "ncollectives": k.value}
+
+
 def timing_begin(stride: int = 1):
     """HIP events around every `stride`-th RT launch until timing_end()."""
     _check(trm.lib().bartrt_timing_begin_sampled(int(stride)))

@@ -2,10 +2,14 @@
 
     python -m bart_amd.retrieve -c BART.cfg [--out DIR]
     python -m torch.distributed.run --nproc-per-node 8 -m bart_amd.retrieve -c BART.cfg
+    python -m torch.distributed.run --nproc-per-node 8 -m bart_amd.retrieve -c BART.cfg --native-sharded
 
 The second form shards the wavenumber axis over the node's GPUs (one process
 per GPU; every rank runs the same seeded sampler, each computes its block of
-every spectrum, one RCCL all-gather per step reassembles them).  Reads the
+every spectrum, one RCCL all-gather per step reassembles them).  By default
+the sharded ranks run the Python sampler loop; ``--native-sharded`` attaches
+the library's own communicator and runs the native loop on every rank in
+lockstep (include/bartrt.h, bartrt_comm_init).  Reads the
 reference's ``[MCMC]`` keys (examples/demo/BART_eclipse.cfg) and writes
 ``output.npy`` (posterior sample [nchains, nsteps, npars]), ``bestFit.txt`` and
 ``MCMC.log`` in the output directory.
@@ -28,6 +32,9 @@ def main(argv=None):
     ap.add_argument("--numit", type=int, default=None)
     ap.add_argument("--python-loop", action="store_true",
                     help="run the sampler loop in Python (sampler.run) instead of the native one")
+    ap.add_argument("--native-sharded", action="store_true",
+                    help="with WORLD_SIZE > 1: attach the library's communicator and run the native loop on every "
+                         "rank (one collective per step inside the library) instead of the Python loop")
     a = ap.parse_args(argv)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -51,7 +58,10 @@ def main(argv=None):
             print(msg, flush=True)
 
     t0 = time.perf_counter()
-    native = not a.python_loop and world == 1
+    native = not a.python_loop and (world == 1 or a.native_sharded)
+    if native and world > 1:
+        from . import engine
+        engine.comm_init()
     res = sampler.run_native(w, scfg, log=log) if native else sampler.run(w.step, scfg, log=log)
     dt = time.perf_counter() - t0
     nmodel = res["chain"].shape[0] * res["chain"].shape[1]

@@ -192,12 +192,14 @@ def run_native(worker, cfg: SamplerConfig, log=None):
     """The same sampler through ``bartrt_mcmc_run`` (csrc/mcmc.hip): the loop,
     its random draws and the chi-square in C++, one batched model call per
     iteration -- about twice the iterations per second of :func:`run` at ten
-    chains.  Needs an unsharded engine; same result dictionary as :func:`run`."""
+    chains.  Needs an unsharded engine or, on a sharded one, the library's
+    communicator (engine.comm_init): every rank then runs this same seeded loop
+    in lockstep and gets the same chains.  Same result dictionary as :func:`run`."""
     import ctypes as C
     from . import engine, transit_module as trm
     lo, hi = engine.local_range()
-    if hi - lo != worker.nwave:
-        raise ValueError("run_native: the engine is sharded; use run()")
+    if hi - lo != worker.nwave and engine.comm_info()["nranks"] == 0:
+        raise ValueError("run_native: the engine is sharded and has no communicator (engine.comm_init); use run()")
     nch = cfg.nchains
     _check_stepsize(cfg.stepsize)
     nsteps = max(1, int(np.ceil(cfg.numit / nch)))

@@ -80,6 +80,11 @@ def lib():
         L.bartrt_step_batch_dev.argtypes = [p, i, i, p, p, p, p]
         L.bartrt_step_profiles_dev.argtypes = [p, i, i, p, p, p]
         L.bartrt_step_bandflux_dev.argtypes = [p, i, p, p, p]
+        L.bartrt_step_bandflux_blocks_dev.argtypes = [p, i, i, p, p, p]
+        L.bartrt_comm_get_unique_id.argtypes = [p]
+        L.bartrt_comm_init.argtypes = [p, i, i]
+        L.bartrt_comm_free.argtypes = []
+        L.bartrt_get_comm.argtypes = [C.POINTER(i), C.POINTER(i), C.POINTER(C.c_ulonglong)]
         L.bartrt_get_local_range.argtypes = [C.POINTER(i), C.POINTER(i)]
         L.bartrt_get_species.argtypes = [C.c_char_p, i]
         L.bartrt_get_pressure.argtypes = [p, i]

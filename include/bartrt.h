@@ -273,6 +273,50 @@ int bartrt_step_profiles_dev(const double *d_params, int nwalkers, int npars,
                              double *d_prof, int *d_status, void *stream);
 int bartrt_step_bandflux_dev(const double *d_spec_full, int nwalkers,
                              int *d_status, double *d_bandflux, void *stream);
+/* The band integration on the ranks' blocks where an all-gather leaves them, for callers that run their own
+ * collective (torch, MPI) and for one GPU standing in for any rank count: d_blocks holds nranks slots of
+ * nwalkers * wmax doubles (wmax = the largest block), slot r = [nwalkers][W_r] packed rows of block r, which covers
+ * samples [Wfull*r/nranks, Wfull*(r+1)/nranks) of the full grid (W_r = Wfull*(r+1)/nranks - Wfull*r/nranks; the
+ * split of "--shard r nranks"); a slot's tail past nwalkers * W_r is not read.  Same terms in the same order as
+ * bartrt_step_bandflux_dev on the reassembled [nwalkers][Wfull] spectra: the same band fluxes and statuses, bit for
+ * bit.  Any engine after bartrt_step_setup, sharded or not; 1 <= nranks <= Wfull.  Asynchronous on `stream`. */
+int bartrt_step_bandflux_blocks_dev(const double *d_blocks, int nranks, int nwalkers,
+                                    int *d_status, double *d_bandflux, void *stream);
+
+/* ---- the ranks' communicator: the per-step path on sharded engines ----------------------------
+ * The library's own RCCL communicator over the ranks of a wavenumber-sharded run ("--shard r n", one GPU per
+ * block).  RCCL is opened at run time, not linked: the copy already mapped into the process if there is one (torch
+ * ships its own librccl.so; a live torch `nccl` group has it mapped), else BARTRT_RCCL_LIB, else
+ * /opt/rocm/lib/librccl.so.1.  Without RCCL every bartrt_comm_* call returns BARTRT_ENOTSUP.
+ *
+ * Bring-up: rank 0 calls bartrt_comm_get_unique_id (no engine needed), the launcher hands the
+ * BARTRT_COMM_ID_BYTES bytes to every rank (torch: bart_amd.engine.comm_init; MPI: MPI_Bcast), and
+ * every rank, its engine initialised, calls bartrt_comm_init with the rank and count of its "--shard r n" (an
+ * unsharded engine is 0 / 1).  A rank / count that is not the engine's block, a second init, or no engine:
+ * BARTRT_EINVAL.  The communicator lives on the engine's device; bartrt_comm_free, bartrt_free_memory and a new
+ * bartrt_init destroy it.  Chain-service clients get BARTRT_ENOTSUP.
+ *
+ * With a communicator attached, bartrt_step_batch, bartrt_step_batch_dev and bartrt_mcmc_run run on sharded engines
+ * -- and on an unsharded engine with a communicator of one rank, the same code: the RT launch writes this rank's
+ * block straight into its slot of a receive buffer (the layout of bartrt_step_bandflux_blocks_dev), ONE in-place
+ * ncclAllGather per call on the call's stream fills the other slots (ordered on the device: no host wait), and the
+ * band integration reads the slots in place.  bartrt_step_batch_dev's d_spec, when given, receives the reassembled
+ * [nwalkers][Wfull] spectra through one copy kernel.  Every rank makes the same calls with the same parameters:
+ * collectives must match across ranks.  Under kernel_by whole (bartrt_set_kernel_by) the band fluxes, statuses and
+ * spectra are the unsharded engine's bits; under kernel_by local they agree with them to rounding and agree across
+ * ranks bit for bit.
+ * LOCKSTEP: bartrt_mcmc_run is host code around that step -- every rank runs the same seeded loop on band fluxes that
+ * are the same bits on every rank, so the ranks draw the same proposals, issue the same collectives and write
+ * identical chains; give every rank the same arguments.
+ * Line-by-line engines: the step with a communicator returns BARTRT_ENOTSUP.  Contribution functions stay
+ * unsupported on sharded engines.  Without a communicator a sharded engine's step fails as before. */
+#define BARTRT_COMM_ID_BYTES 128          /* = NCCL_UNIQUE_ID_BYTES */
+int bartrt_comm_get_unique_id(void *id);  /* rank 0 calls it; the launcher broadcasts the bytes */
+int bartrt_comm_init(const void *id, int rank, int nranks);
+int bartrt_comm_free(void);
+/* *rank / *nranks of the attached communicator (-1 / 0 without one); *ncollectives: collectives this engine has
+ * issued (counted across bartrt_comm_free, reset by bartrt_init).  Pointers may be NULL. */
+int bartrt_get_comm(int *rank, int *nranks, unsigned long long *ncollectives);
 
 /* ---- introspection ----------------------------------------------------- */
 const char *bartrt_last_error(void);
