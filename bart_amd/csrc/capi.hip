@@ -158,7 +158,7 @@ void teardown(double wait_s) {
     (void)hipDeviceSynchronize();
     comm_destroy(g_eng->comm);   // (before the engine's device state goes)
     g_eng->comm = nullptr;
-    cf_release();   // (the contribution-function tables and workspaces belong to this engine)
+    // (the contribution-function tables and workspaces belong to this engine and go with it)
     delete g_eng;
     g_eng = nullptr;
   }
@@ -479,9 +479,9 @@ int bartrt_run_transit_batch(const double *prof, int nwalkers, int nprof,
       e->last_prof = e->d_prof;
       e->last_n = nwalkers;
       HIPCHK(hipMemcpyAsync(e->d_prof, e->h_pin, pb, hipMemcpyHostToDevice, e->stream));
-      e->run_dev(e->d_prof, nwalkers, e->d_spec, e->d_ok, e->stream, false);
+      e->run_dev(e->d_prof, nwalkers, e->d_spec, e->rec[0].ok, e->stream, false);
       HIPCHK(hipMemcpyAsync(hs, e->d_spec, sb, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(hipMemcpyAsync(hok, e->d_ok, nwalkers, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(hipMemcpyAsync(hok, e->rec[0].ok, nwalkers, hipMemcpyDeviceToHost, e->stream));
     }
     e->wait(e->stream);
     const size_t off = nwave == Wl ? 0 : (size_t)e->lo;
@@ -534,7 +534,7 @@ int bartrt_get_tau_of(int walker, double *tau, int *last, int nwave, int nlayers
     return fail(BARTRT_EINVAL, "get_tau: shape must be [local samples][nlayers]");
   return guarded([&] {
     // re-run that profile of the latest host-buffer call with the optical-depth output enabled
-    e->run_dev(latest_profile(e, walker, "get_tau"), 1, e->d_spec, e->d_ok, e->stream, true);
+    e->run_dev(latest_profile(e, walker, "get_tau"), 1, e->d_spec, e->rec[0].ok, e->stream, true);
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipMemcpy(tau, e->d_tau, sizeof(double) * (size_t)nwave * nlayers, hipMemcpyDeviceToHost));
     if (last) HIPCHK(hipMemcpy(last, e->d_last, sizeof(int) * (size_t)nwave, hipMemcpyDeviceToHost));
@@ -601,7 +601,7 @@ int bartrt_get_intensity_of(int walker, double *intens, int nangles, int nwave) 
     const double *prof = latest_profile(e, walker, "get_intensity");
     e->want_intens = true;
     try {
-      e->run_dev(prof, 1, e->d_spec, e->d_ok, e->stream, false);
+      e->run_dev(prof, 1, e->d_spec, e->rec[0].ok, e->stream, false);
     } catch (...) { e->want_intens = false; throw; }
     e->want_intens = false;
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -755,7 +755,7 @@ static int cf_check_kind(const Engine *e, int kind, const char *who) {
     return fail(BARTRT_EINVAL, std::string(who) + ": kind must be BARTRT_CF_CONTRIB or BARTRT_CF_TRANSMIT");
   if (kind == BARTRT_CF_CONTRIB && e->solution != 0)
     return fail(BARTRT_ENOTSUP, std::string(who) + ": contribution functions need the eclipse geometry (transmittance serves transit)");
-  if (cf_nfilters() == 0) return fail(BARTRT_EINVAL, std::string(who) + ": call bartrt_cf_setup first");
+  if (cf_nfilters(*e) == 0) return fail(BARTRT_EINVAL, std::string(who) + ": call bartrt_cf_setup first");
   return BARTRT_OK;
 }
 

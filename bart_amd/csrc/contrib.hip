@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -204,60 +205,23 @@ __global__ __launch_bounds__(256) void cf_finish(const double *part, int nwalker
   band[((size_t)w * nf + f) * L + (L - 1 - k)] = ok[w] ? s / trapz[f] : __builtin_nan("");
 }
 
-// ---- host state: the filter tables and the workspaces, owned here (not by Engine) ----
-struct CfState {
-  const Engine *eng = nullptr;   // the engine the tables were built for
-  int nf = 0, L = 0, W = 0, ntiles = 0, nent = 0;
-  int *d_tile_ptr = nullptr, *d_f_ptr = nullptr, *d_f_ent = nullptr;
-  double *d_wt = nullptr, *d_trapz = nullptr, *d_rdlp = nullptr;
-  // per-walker workspaces of one chunk of walkers
+}  // namespace
+
+// ---- host state of one engine (Engine::cf; made by cf_setup): the per-walker workspaces of one chunk of walkers ----
+struct CfWork {
   int cap = 0;
-  double *d_coef = nullptr, *d_rtop = nullptr, *d_ds = nullptr, *d_part = nullptr;
-  idx_t *d_idx = nullptr;
-  int *d_kstop = nullptr;
-  unsigned char *d_ok = nullptr;
-  // staging of the host-buffer call
-  size_t stage_bytes = 0;
-  char *d_stage = nullptr;
+  RecordSet rec;
+  DevBuf<double> d_rtop, d_ds, d_part;
+  DevBuf<char> d_stage;               // staging of the host-buffer call
   hipStream_t last_stream = nullptr;  // the workspaces' latest user
 };
-CfState g;
+struct CfState : CfWork {   // ... and the filter tables
+  int nf = 0, ntiles = 0, nent = 0;
+  DevBuf<int> d_tile_ptr, d_f_ptr, d_f_ent;
+  DevBuf<double> d_wt, d_trapz, d_rdlp;
+};
 
-template <class T>
-void cf_free(T *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
-template <class T>
-void cf_alloc(T *&p, size_t count) {
-  cf_free(p);
-  HIPCHK(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
-}
-
-template <class T>
-T *cf_upload(const std::vector<T> &v) {
-  T *p = nullptr;
-  cf_alloc(p, v.size());
-  if (!v.empty()) HIPCHK(hipMemcpy(p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
-  return p;
-}
-
-void free_tables() {
-  cf_free(g.d_tile_ptr); cf_free(g.d_f_ptr); cf_free(g.d_f_ent);
-  cf_free(g.d_wt); cf_free(g.d_trapz); cf_free(g.d_rdlp);
-  g.eng = nullptr;
-  g.nf = g.nent = 0;
-}
-
-void free_workspace() {
-  cf_free(g.d_coef); cf_free(g.d_rtop); cf_free(g.d_ds); cf_free(g.d_part);
-  cf_free(g.d_idx); cf_free(g.d_kstop); cf_free(g.d_ok);
-  cf_free(g.d_stage);
-  g.cap = 0;
-  g.stage_bytes = 0;
-  g.last_stream = nullptr;
-}
+namespace {
 
 // Bytes of the workspaces (partials, layer records, chord tables) a chunk may hold: BARTRT_CF_WORKSPACE_BYTES,
 // default 256 MiB.  Read per call.
@@ -267,6 +231,7 @@ size_t workspace_cap() {
 }
 
 size_t per_walker_bytes(const Engine &e) {
+  const CfState &g = *e.cf;
   size_t b = sizeof(double) * (size_t)g.nent * e.L + sizeof(double) * (size_t)e.L * coef_stride(e.M, e.C) +
              sizeof(idx_t) * (size_t)e.L * idx_stride(e.C) + sizeof(int) + 1;
   if (e.solution == 1) b += sizeof(double) * ((size_t)e.L + chord_table_size(e.L));
@@ -274,29 +239,27 @@ size_t per_walker_bytes(const Engine &e) {
 }
 
 // a stream other than the previous call's may not reuse the workspaces while that call still runs
-void claim(hipStream_t st) {
+void claim(CfState &g, hipStream_t st) {
   if (g.last_stream && g.last_stream != st) HIPCHK(hipStreamSynchronize(g.last_stream));
   g.last_stream = st;
 }
 
 void ensure_cap(const Engine &e, int n) {
+  CfState &g = *e.cf;
   if (n <= g.cap) return;
   HIPCHK(hipDeviceSynchronize());   // (an earlier launch on any stream may still use the old buffers)
-  cf_alloc(g.d_coef, (size_t)n * e.L * coef_stride(e.M, e.C));
-  cf_alloc(g.d_idx, (size_t)n * e.L * idx_stride(e.C));
-  cf_alloc(g.d_kstop, (size_t)n);
-  cf_alloc(g.d_ok, (size_t)n);
-  cf_alloc(g.d_part, (size_t)n * g.nent * e.L);
+  g.rec.reserve((size_t)n, e.L, e.M, e.C);
+  g.d_part.reserve((size_t)n * g.nent * e.L);
   if (e.solution == 1) {
-    cf_alloc(g.d_rtop, (size_t)n * e.L);
-    cf_alloc(g.d_ds, (size_t)n * chord_table_size(e.L));
+    g.d_rtop.reserve((size_t)n * e.L);
+    g.d_ds.reserve((size_t)n * chord_table_size(e.L));
   }
   g.cap = n;
 }
 
 void check_ready(const Engine &e, int kind) {
   if (kind != kCfContrib && kind != kCfTransmit) throw std::invalid_argument("cf: kind must be BARTRT_CF_CONTRIB or BARTRT_CF_TRANSMIT");
-  if (!g.eng || g.eng != &e || g.L != e.L || g.W != e.W()) throw std::invalid_argument("cf: call bartrt_cf_setup first");
+  if (!e.cf) throw std::invalid_argument("cf: call bartrt_cf_setup first");
 }
 
 template <class K>
@@ -309,27 +272,21 @@ void allow_lds(K kernel, size_t bytes) {
 // one chunk: m walkers whose flags go to okp
 void run_chunk(Engine &e, const double *d_prof, int m, int kind, double *d_band, double *d_full, unsigned char *okp,
                hipStream_t st) {
+  const CfState &g = *e.cf;
   // the layer records under the engine's settings, as run_transit_batch builds them, into this module's buffers
   // (no radii output, no per-walker overrides: the engine's own state is left as it was)
-  PrepArgs pa = e.prep;
-  pa.nwalkers = m;
-  pa.prof = d_prof;
-  pa.gsurf = e.gsurf; pa.refradius = e.refradius;
-  pa.scat_flag = e.scat_flag; pa.scat_value = e.scat_value;
-  pa.has_cloud = e.has_cloud; pa.cloudtop = e.cloudtop;
-  pa.cloud_rup = e.cloud_rup; pa.cloud_rdown = e.cloud_rdown; pa.cloud_ext = e.cloud_ext;
-  pa.coef = g.d_coef; pa.idx = g.d_idx; pa.kstop = g.d_kstop; pa.ok = okp;
+  PrepArgs pa = e.prep_args(d_prof, m, okp, g.rec);
   pa.rad_out = nullptr;
   pa.over = nullptr;
-  pa.rtop = e.solution == 1 ? g.d_rtop : nullptr;
-  pa.ds = e.solution == 1 ? g.d_ds : nullptr;
+  pa.rtop = e.solution == 1 ? g.d_rtop.get() : nullptr;
+  pa.ds = e.solution == 1 ? g.d_ds.get() : nullptr;
   HIPCHK(launch_prep(pa, st));
   if (e.solution == 1) HIPCHK(launch_chord_table(pa, st));
 
   CfArgs a{};
   a.L = e.L; a.M = e.M; a.C = e.C; a.W = e.W(); a.nwalkers = m; a.ntiles = g.ntiles; a.kind = kind; a.nent = g.nent;
   a.kappa = e.rt.kappa; a.cia = e.rt.cia; a.wn = e.rt.wn;
-  a.coef = g.d_coef; a.idx = g.d_idx; a.kstop = g.d_kstop;
+  a.coef = g.rec.coef; a.idx = g.rec.idx; a.kstop = g.rec.kstop;
   a.rdlp = g.d_rdlp;
   a.rtop = g.d_rtop; a.ds = g.d_ds;
   a.tile_ptr = g.d_tile_ptr; a.wt = g.d_wt;
@@ -417,38 +374,41 @@ void cf_setup(Engine &e, int nf, const int *idx0, const int *npts, const double 
   for (int k = 1; k < L; k++) rdlp[k] = 1.0 / (std::log(e.atm.press[L - 1 - k]) - std::log(e.atm.press[L - k]));
 
   HIPCHK(hipDeviceSynchronize());   // (a CF launch may still read the old tables)
-  free_tables();
-  if (g.cap && nent != g.nent) free_workspace();   // partials are sized by the entry count
-  g.d_tile_ptr = cf_upload(tile_ptr);
-  g.d_f_ptr = cf_upload(f_ptr);
-  g.d_f_ent = cf_upload(f_ent);
-  g.d_wt = cf_upload(wt);
-  g.d_trapz = cf_upload(trapz);
-  g.d_rdlp = cf_upload(rdlp);
-  g.nf = nf; g.nent = nent; g.L = L; g.W = W; g.ntiles = ntiles;
-  g.eng = &e;
+  std::unique_ptr<CfState> old(std::exchange(e.cf, nullptr)), g(new CfState());
+  g->d_tile_ptr.upload(tile_ptr);
+  g->d_f_ptr.upload(f_ptr);
+  g->d_f_ent.upload(f_ent);
+  g->d_wt.upload(wt);
+  g->d_trapz.upload(trapz);
+  g->d_rdlp.upload(rdlp);
+  g->nf = nf; g->nent = nent; g->ntiles = ntiles;
+  // an earlier setup's workspaces stay unless the entry count changes (it sizes the partials); its tables go with `old`
+  if (old && old->nent == nent) static_cast<CfWork &>(*g) = std::move(*old);
+  e.cf = g.release();
 }
 
-int cf_nfilters() { return g.eng ? g.nf : 0; }
+int cf_nfilters(const Engine &e) { return e.cf ? e.cf->nf : 0; }
 
 void cf_run_dev(Engine &e, const double *d_prof, int n, int kind, double *d_band, double *d_full, unsigned char *d_ok,
                 hipStream_t st) {
   check_ready(e, kind);
   if (n <= 0) return;
+  CfState &g = *e.cf;
   const int nprof = (e.S + 1) * e.L;
   const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, workspace_cap() / per_walker_bytes(e)));
   ensure_cap(e, chunk);
-  claim(st);
+  claim(g, st);
   for (int off = 0; off < n; off += chunk) {
     const int m = std::min(chunk, n - off);
     run_chunk(e, d_prof + (size_t)off * nprof, m, kind, d_band + (size_t)off * g.nf * e.L,
-              d_full ? d_full + (size_t)off * e.W() * e.L : nullptr, d_ok ? d_ok + off : g.d_ok, st);
+              d_full ? d_full + (size_t)off * e.W() * e.L : nullptr, d_ok ? d_ok + off : g.rec.ok.get(), st);
   }
 }
 
 void cf_run_host(Engine &e, const double *prof, int n, int kind, double *band, double *full, unsigned char *ok) {
   check_ready(e, kind);
   if (n <= 0) return;
+  CfState &g = *e.cf;
   const int nprof = (e.S + 1) * e.L;
   const size_t bprof = sizeof(double) * nprof, bband = sizeof(double) * (size_t)g.nf * e.L,
                bfull = full ? sizeof(double) * (size_t)e.W() * e.L : 0;
@@ -457,13 +417,12 @@ void cf_run_host(Engine &e, const double *prof, int n, int kind, double *band, d
   const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, workspace_cap() / per));
   ensure_cap(e, chunk);
   const size_t need = (size_t)chunk * (bprof + bband + bfull) + chunk;
-  if (need > g.stage_bytes) {
+  if (need > g.d_stage.count()) {
     HIPCHK(hipDeviceSynchronize());
-    cf_alloc(g.d_stage, need);
-    g.stage_bytes = need;
+    g.d_stage.reserve(need);
   }
   hipStream_t st = e.stream;
-  claim(st);
+  claim(g, st);
   char *base = g.d_stage;
   double *dp = reinterpret_cast<double *>(base);
   double *db = reinterpret_cast<double *>(base + (size_t)chunk * bprof);
@@ -485,9 +444,9 @@ void cf_run_host(Engine &e, const double *prof, int n, int kind, double *band, d
   }
 }
 
-void cf_release() {
-  free_tables();
-  free_workspace();
+void cf_release(Engine &e) {
+  delete e.cf;
+  e.cf = nullptr;
 }
 
 }  // namespace bartrt

@@ -2,6 +2,7 @@
 // drives the kernels.  One engine per process (one process per GPU).
 #include "engine.hpp"
 #include "lbl.hpp"
+#include "contrib.hpp"
 #include "share.hpp"
 #include "step.hpp"
 #include "svc.hpp"
@@ -17,28 +18,17 @@
 
 namespace bartrt {
 
-template <class T>
-static T *dev_upload(const std::vector<T> &v) {
-  T *d = nullptr;
-  size_t n = std::max<size_t>(v.size(), 1);
-  HIPCHK(hipMalloc(&d, n * sizeof(T)));
-  if (!v.empty()) HIPCHK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  return d;
+EngineStream::~EngineStream() {
+  for (auto e : ev) (void)hipEventDestroy(e);
+  if (stream) (void)hipStreamDestroy(stream);
 }
 
+// (the buffers are members: they free themselves after this body, before the events and the stream of the base)
 Engine::~Engine() {
   delete step;
   delete lbl;
-  auto fr = [](void *p) { if (p) (void)hipFree(p); };
-  if (kappa_share) { kappa_share->release(); kappa_share = nullptr; d_kappa = nullptr; }
-  fr(d_kappa); fr(d_cia); fr(d_wn); fr(d_wn_full); fr(d_press); fr(d_mass);
-  fr(d_prep_consts); fr(d_diam); fr(d_prof); fr(d_coef); fr(d_spec);
-  fr(d_idx); fr(d_kstop); fr(d_rtop); fr(d_ds); fr(d_rad); fr(d_intens); fr(d_ok); fr(d_tau); fr(d_last);
-  fr(d_walked); fr(d_coef2); fr(d_idx2); fr(d_kstop2); fr(d_ok2); fr(d_slog);
-  if (h_pin) (void)hipHostFree(h_pin);
-  if (h_flag) (void)hipHostFree(h_flag);
-  for (auto e : ev) (void)hipEventDestroy(e);
-  if (stream) (void)hipStreamDestroy(stream);
+  cf_release(*this);
+  if (kappa_share) { kappa_share->release(); kappa_share = nullptr; }
 }
 
 void Engine::init(int argc, const char **argv) {
@@ -108,11 +98,11 @@ static bool file_exists(const std::string &p) {
   return f != nullptr;
 }
 
-void Engine::setup(const TCfg &cfg_in, int shard_rank, int shard_n) {
-  cfg = cfg_in;
-  // Keys of the reference's whitelist (code/makecfg.py:36-52) accepted without
-  // effect: verb, allowq, rad*, orbpars*, tauiso, outtau, taulevel, modlevel --
-  // sampling and diagnostic controls of the CPU engine.
+// Stage 1 (host only): settings from the configuration and the environment.
+// Keys of the reference's whitelist (code/makecfg.py:36-52) accepted without
+// effect: verb, allowq, rad*, orbpars*, tauiso, outtau, taulevel, modlevel --
+// sampling and diagnostic controls of the CPU engine.
+void Engine::read_settings() {
   // Radius-ramp cloud (makecfg.py:46-47): `cloudrad <up> <down>` (blank or comma
   // separated, in units of `cloudfct`, default `radfct`, default km) and `cloudext`
   // (cm-1): grey extinction 0 above <up>, rising linearly to cloudext at <down>,
@@ -135,29 +125,6 @@ void Engine::setup(const TCfg &cfg_in, int shard_rank, int shard_n) {
   // last chord; no effect on the eclipse geometry
   transparent = cfg_has(cfg, "transparent") && cfg["transparent"] != "0" && cfg["transparent"] != "no" &&
                 cfg["transparent"] != "false";
-  // An opacity file that does not exist yet is generated from the line list
-  // first (what `transit --justOpacity` does, BART.py:561-565), by a
-  // temporary line-by-line engine on the same configuration.
-  if (cfg_has(cfg, "opacityfile") && !file_exists(cfg["opacityfile"])) {
-    if (!cfg_has(cfg, "linedb"))
-      throw IoError{"cannot open opacity file '" + cfg["opacityfile"] + "' (and no 'linedb' to build it from)"};
-    if (shard_rank == 0) {
-      TCfg gcfg = cfg;
-      gcfg.erase("opacityfile");
-      Engine gen;
-      gen.device = device;
-      gen.share_mode = kShareOff;
-      gen.setup(gcfg, 0, 1);
-      std::vector<double> tg;
-      const double tlow = cfg_num(cfg, "tlow", 500.0), thigh = cfg_num(cfg, "thigh", 3000.0),
-                   dt = cfg_num(cfg, "tempdelt", 100.0);
-      if (!(dt > 0) || !(thigh > tlow)) throw IoError{"transit cfg: bad tlow/thigh/tempdelt"};
-      for (int k = 0; tlow + k * dt <= thigh + 1e-9 * dt; k++) tg.push_back(tlow + k * dt);
-      lbl_write_opacity(gen, cfg["opacityfile"], tg);
-    } else {
-      throw IoError{"opacity file missing: generate it on an unsharded engine first"};
-    }
-  }
   if (!cfg_has(cfg, "atm")) throw IoError{"transit cfg: missing 'atm'"};
   if (!cfg_has(cfg, "molfile")) throw IoError{"transit cfg: missing 'molfile'"};
   std::string sol = cfg_has(cfg, "solution") ? cfg["solution"] : "eclipse";
@@ -170,32 +137,59 @@ void Engine::setup(const TCfg &cfg_in, int shard_rank, int shard_n) {
   } else if (sol != "eclipse") {
     throw IoError{"unknown solution '" + sol + "' (eclipse or transit)"};
   }
+  // a key of this engine's own: the cfg's value (or the default), overridden by a non-empty environment variable
+  auto setting = [&](const char *key, const char *env, const char *dflt) {
+    std::string v = cfg_has(cfg, key) ? cfg[key] : dflt;
+    if (const char *ev = std::getenv(env)) if (*ev) v = ev;
+    return v;
+  };
   // integration rule of the eclipse geometry (integ.hpp): `integ` in the cfg (this
   // engine's own key: the reference's source, which would settle the rule, is
   // absent), overridden by BARTRT_INTEG; number or name
-  {
-    // default: rule 1, the integrator SURVEY.md App. A-4 recalls for the reference's engine
-    std::string v = cfg_has(cfg, "integ") ? cfg["integ"] : "1";
-    if (const char *ev = std::getenv("BARTRT_INTEG")) if (*ev) v = ev;
-    integ = parse_integ(v);
-  }
+  // default: rule 1, the integrator SURVEY.md App. A-4 recalls for the reference's engine
+  integ = parse_integ(setting("integ", "BARTRT_INTEG", "1"));
   // `voigt exact | grid` (line-by-line evaluation, lbl.hpp / DESIGN.md C18) is checked whether or
   // not this engine ends up reading the lines
   if (cfg_has(cfg, "voigt") && cfg["voigt"] != "exact" && cfg["voigt"] != "grid")
     throw IoError{"voigt: '" + cfg["voigt"] + "' is neither exact nor grid"};
   // `cut vertical | slant`: which optical depth `toomuch` is compared with
-  {
-    std::string v = cfg_has(cfg, "cut") ? cfg["cut"] : "slant";
-    if (const char *ev = std::getenv("BARTRT_CUT")) if (*ev) v = ev;
-    if (v != "vertical" && v != "slant") throw IoError{"cut: '" + v + "' is neither vertical nor slant"};
-    cut_slant = v == "slant";
-  }
-  {
-    std::string v = cfg_has(cfg, "kernel_by") ? cfg["kernel_by"] : "local";
-    if (const char *ev = std::getenv("BARTRT_KERNEL_BY")) if (*ev) v = ev;
-    if (v != "whole" && v != "local") throw IoError{"kernel_by: '" + v + "' is neither whole nor local"};
-    kernel_by_local = v == "local";
-  }
+  std::string v = setting("cut", "BARTRT_CUT", "slant");
+  if (v != "vertical" && v != "slant") throw IoError{"cut: '" + v + "' is neither vertical nor slant"};
+  cut_slant = v == "slant";
+  v = setting("kernel_by", "BARTRT_KERNEL_BY", "local");
+  if (v != "whole" && v != "local") throw IoError{"kernel_by: '" + v + "' is neither whole nor local"};
+  kernel_by_local = v == "local";
+  // `cia_interp` (BARTRT_CIA_INTERP): spline (default: the reading of the reference believed in,
+  // DESIGN.md C20) -- natural cubic splines in wavenumber and temperature -- or linear in both (resample_cia)
+  v = setting("cia_interp", "BARTRT_CIA_INTERP", "spline");
+  if (v != "linear" && v != "spline") throw IoError{"cia_interp: '" + v + "' is neither linear nor spline"};
+  cia_spline = v == "spline";
+}
+
+// Stage 2: an opacity file that does not exist yet is generated from the line list
+// first (what `transit --justOpacity` does, BART.py:561-565), by a
+// temporary line-by-line engine on the same configuration.
+void Engine::generate_missing_opacity_file(int shard_rank) {
+  if (!cfg_has(cfg, "opacityfile") || file_exists(cfg["opacityfile"])) return;
+  if (!cfg_has(cfg, "linedb"))
+    throw IoError{"cannot open opacity file '" + cfg["opacityfile"] + "' (and no 'linedb' to build it from)"};
+  if (shard_rank != 0) throw IoError{"opacity file missing: generate it on an unsharded engine first"};
+  TCfg gcfg = cfg;
+  gcfg.erase("opacityfile");
+  Engine gen;
+  gen.device = device;
+  gen.share_mode = kShareOff;
+  gen.setup(gcfg, 0, 1);
+  std::vector<double> tg;
+  const double tlow = cfg_num(cfg, "tlow", 500.0), thigh = cfg_num(cfg, "thigh", 3000.0),
+               dt = cfg_num(cfg, "tempdelt", 100.0);
+  if (!(dt > 0) || !(thigh > tlow)) throw IoError{"transit cfg: bad tlow/thigh/tempdelt"};
+  for (int k = 0; tlow + k * dt <= thigh + 1e-9 * dt; k++) tg.push_back(tlow + k * dt);
+  lbl_write_opacity(gen, cfg["opacityfile"], tg);
+}
+
+// Stage 3 (host only): atmosphere, molecule file, species masses.
+void Engine::read_atmosphere() {
   atm = read_atm(cfg["atm"]);
   mol = read_molfile(cfg["molfile"]);
   L = (int)atm.press.size();
@@ -211,11 +205,12 @@ void Engine::setup(const TCfg &cfg_in, int shard_rank, int shard_n) {
   for (int l = 0; l + 1 < L; l++)
     if (!(atm.press[l] > atm.press[l + 1]))
       throw IoError{"atmosphere file: layers must run bottom -> top (decreasing pressure)"};
+}
 
-  // ---- wavenumber grid and opacity table
-  OpacityHeader oh;
-  const bool have_table = cfg_has(cfg, "opacityfile");
-  if (have_table) {
+// Stage 4 (host only): wavenumber grid -- the opacity file's (its header goes to oh) or the cfg's -- and this
+// rank's block of it.
+void Engine::read_grid(OpacityHeader &oh, int shard_rank, int shard_n) {
+  if (cfg_has(cfg, "opacityfile")) {
     oh = read_opacity_header(cfg["opacityfile"]);
     if (oh.nlayer != L) throw IoError{"opacity file: layer count differs from the atmosphere file"};
     for (int l = 0; l < L; l++)
@@ -258,9 +253,10 @@ void Engine::setup(const TCfg &cfg_in, int shard_rank, int shard_n) {
   lo = (int)((long)Wfull * shard_rank / shard_n);
   hi = (int)((long)Wfull * (shard_rank + 1) / shard_n);
   if (hi <= lo) throw IoError{"--shard leaves this rank without wavenumber samples"};
-  const int Wl = W();
+}
 
-  // ---- geometry, hydrostatic reference
+// Stage 5 (host only): ray grid, `toomuch`, hydrostatic keys, cloud top, scattering.
+void Engine::read_geometry() {
   angles = cfg_list(cfg, "raygrid");
   if (angles.empty()) angles = {0, 20, 40, 60, 80};
   A = (int)angles.size();
@@ -276,8 +272,10 @@ void Engine::setup(const TCfg &cfg_in, int shard_rank, int shard_n) {
   refradius = cfg_num(cfg, "refradius", 0) * 1e5;    // km -> cm
   if (cfg_has(cfg, "cloudtop")) { has_cloud = 1; cloudtop = std::pow(10.0, cfg_num(cfg, "cloudtop", 0)) * 1e6; }
   if (cfg_has(cfg, "scattering")) { scat_flag = 1; scat_value = cfg_num(cfg, "scattering", 0); }
+}
 
-  // ---- device
+// Stage 6: device, stream, and the pinned word wait() polls.
+void Engine::open_device() {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
     throw HipError{hipErrorNoDevice, "no HIP device: libbartrt computes on the GPU only"};
@@ -287,222 +285,226 @@ void Engine::setup(const TCfg &cfg_in, int shard_rank, int shard_n) {
   }
   HIPCHK(hipSetDevice(device));
   HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-  {
-    const char *e = std::getenv("BARTRT_SYNC");
-    sync_poll = !(e && std::string(e) == "stream");
-    if (sync_poll) {
-      void *dv = nullptr;
-      if (hipHostMalloc(reinterpret_cast<void **>(&h_flag), 64, hipHostMallocDefault) == hipSuccess &&
-          hipHostGetDevicePointer(&dv, h_flag, 0) == hipSuccess) {
-        *h_flag = 0;
-        d_flag = static_cast<unsigned int *>(dv);
-      } else {
-        (void)hipGetLastError();
-        sync_poll = false;
-      }
-    }
+  const char *e = std::getenv("BARTRT_SYNC");
+  sync_poll = !(e && std::string(e) == "stream");
+  if (!sync_poll) return;
+  try {
+    void *dv = nullptr;
+    h_flag.reserve(16);   // (64 bytes)
+    HIPCHK(hipHostGetDevicePointer(&dv, h_flag.get(), 0));
+    *h_flag = 0;
+    d_flag = static_cast<unsigned int *>(dv);
+  } catch (const HipError &) {   // no pinned word: hipStreamSynchronize
+    (void)hipGetLastError();
+    sync_poll = false;
   }
+}
 
-  // ---- tables to HBM
-  std::vector<double> wn_loc(wn_full.begin() + lo, wn_full.begin() + hi);
-  d_wn = dev_upload(wn_loc);
-  d_wn_full = dev_upload(wn_full);
-  if (M > 0) {
-    // The file's order o[L][Nt][M][W] goes up slab by slab -- a bounded number of (layer,
-    // temperature) planes through one pinned host buffer and one device staging buffer
-    // (256 MB, BARTRT_INIT_SLAB_BYTES) -- and is re-laid out on the device with each
-    // wavenumber's molecules contiguous (kernels.hpp, "Table layout"): peak memory during
-    // init is the table + one slab, on the device and on the host.
-    const size_t n = (size_t)L * Nt * M * Wl;
-    const long planes = (long)L * Nt;
-    const size_t plane_doubles = (size_t)M * Wl;
-    size_t slab_bytes = (size_t)256 << 20;
-    if (const char *e = std::getenv("BARTRT_INIT_SLAB_BYTES")) slab_bytes = std::max<size_t>(1, std::strtoull(e, nullptr, 10));
-    const long per = std::max<long>(1, std::min<long>(planes, (long)(slab_bytes / (plane_doubles * sizeof(double)))));
-    auto upload = [&](double *dst) {
-      double *h = nullptr, *d_stage = nullptr;
-      hipError_t er = hipHostMalloc(&h, (size_t)per * plane_doubles * sizeof(double), hipHostMallocDefault);
-      if (er == hipSuccess) er = hipMalloc(&d_stage, (size_t)per * plane_doubles * sizeof(double));
-      try {
-        for (long p0 = 0; p0 < planes && er == hipSuccess; p0 += per) {
-          const long np = std::min(per, planes - p0);
-          read_opacity_rows(cfg["opacityfile"], oh, lo, hi, p0 * M, np * M, h);
-          er = hipMemcpyAsync(d_stage, h, (size_t)np * plane_doubles * sizeof(double), hipMemcpyHostToDevice, stream);
-          if (er == hipSuccess) er = launch_grid_transpose(d_stage, dst + (size_t)p0 * plane_doubles, np, M, Wl, stream);
-          if (er == hipSuccess) er = hipStreamSynchronize(stream);   // the slab buffers are reused
-        }
-      } catch (...) {
-        if (h) (void)hipHostFree(h);
-        if (d_stage) (void)hipFree(d_stage);
-        throw;
-      }
-      if (h) (void)hipHostFree(h);
-      if (d_stage) (void)hipFree(d_stage);
-      HIPCHK(er);
-    };
-    // `shareOpacity` (code/makecfg.py:106-107: BART's worker processes share ONE opacity grid; a bare key in
-    // the cfg makeTransit writes) or BARTRT_SHARE_OPACITY=1: the first process of this (file, device, block)
-    // uploads the grid, the others map its HBM allocation through an IPC handle (share.hpp)
-    if (share_mode < 0) share_mode = resolve_share_mode(cfg, true);
-    if (share_mode == kShareIpc) {
-      struct stat fst;
-      if (stat(cfg["opacityfile"].c_str(), &fst) != 0) throw IoError{"opacity file: cannot stat " + cfg["opacityfile"]};
-      char rp[PATH_MAX];
-      const std::string real = realpath(cfg["opacityfile"].c_str(), rp) ? std::string(rp) : cfg["opacityfile"];
-      int bus = 0;
-      hipDeviceProp_t prop;
-      std::string devid = std::to_string(device);
-      if (hipGetDeviceProperties(&prop, device) == hipSuccess) {
-        bus = prop.pciBusID;
-        devid = std::to_string(prop.pciDomainID) + ":" + std::to_string(bus) + ":" + std::to_string(prop.pciDeviceID);
-      }
-      const std::string key = real + "|" + std::to_string((long long)fst.st_size) + "|" + std::to_string((long long)fst.st_mtime) +
-                              "|" + std::to_string((long long)getuid()) + "|dev " + devid + "|wn " + std::to_string(lo) + ":" +
-                              std::to_string(hi) + "|layout LTWM v1";
-      kappa_share = TableShare::attach(key, n * sizeof(double), upload);
-      d_kappa = kappa_share->ptr;
-    } else {
-      HIPCHK(hipMalloc(&d_kappa, n * sizeof(double)));
-      upload(d_kappa);
+// What names one process's upload of the table to the others of `shareOpacity`: the file (path, size, time), the
+// user, the device and this rank's block.
+static std::string share_key(const std::string &file, int device, int lo, int hi) {
+  struct stat fst;
+  if (stat(file.c_str(), &fst) != 0) throw IoError{"opacity file: cannot stat " + file};
+  char rp[PATH_MAX];
+  const std::string real = realpath(file.c_str(), rp) ? std::string(rp) : file;
+  hipDeviceProp_t prop;
+  std::string devid = std::to_string(device);
+  if (hipGetDeviceProperties(&prop, device) == hipSuccess)
+    devid = std::to_string(prop.pciDomainID) + ":" + std::to_string(prop.pciBusID) + ":" + std::to_string(prop.pciDeviceID);
+  return real + "|" + std::to_string((long long)fst.st_size) + "|" + std::to_string((long long)fst.st_mtime) +
+         "|" + std::to_string((long long)getuid()) + "|dev " + devid + "|wn " + std::to_string(lo) + ":" +
+         std::to_string(hi) + "|layout LTWM v1";
+}
+
+// Stage 7: the wavenumber grids and the opacity table to HBM.
+void Engine::upload_table(const OpacityHeader &oh) {
+  const int Wl = W();
+  d_wn.upload(wn_full.data() + lo, (size_t)Wl);
+  d_wn_full.upload(wn_full);
+  if (M == 0) return;
+  // The file's order o[L][Nt][M][W] goes up slab by slab -- a bounded number of (layer,
+  // temperature) planes through one pinned host buffer and one device staging buffer
+  // (256 MB, BARTRT_INIT_SLAB_BYTES) -- and is re-laid out on the device with each
+  // wavenumber's molecules contiguous (kernels.hpp, "Table layout"): peak memory during
+  // init is the table + one slab, on the device and on the host.
+  const size_t n = (size_t)L * Nt * M * Wl;
+  const long planes = (long)L * Nt;
+  const size_t plane_doubles = (size_t)M * Wl;
+  size_t slab_bytes = (size_t)256 << 20;
+  if (const char *e = std::getenv("BARTRT_INIT_SLAB_BYTES")) slab_bytes = std::max<size_t>(1, std::strtoull(e, nullptr, 10));
+  const long per = std::max<long>(1, std::min<long>(planes, (long)(slab_bytes / (plane_doubles * sizeof(double)))));
+  auto upload = [&](double *dst) {
+    PinBuf<double> h;
+    DevBuf<double> d_stage;
+    h.reserve((size_t)per * plane_doubles);
+    d_stage.reserve((size_t)per * plane_doubles);
+    for (long p0 = 0; p0 < planes; p0 += per) {
+      const long np = std::min(per, planes - p0);
+      read_opacity_rows(cfg["opacityfile"], oh, lo, hi, p0 * M, np * M, h);
+      HIPCHK(hipMemcpyAsync(d_stage, h, (size_t)np * plane_doubles * sizeof(double), hipMemcpyHostToDevice, stream));
+      HIPCHK(launch_grid_transpose(d_stage, dst + (size_t)p0 * plane_doubles, np, M, Wl, stream));
+      HIPCHK(hipStreamSynchronize(stream));   // the slab buffers are reused
     }
-  }
-  // CIA: resample on the local grid (zero outside the file) and lay out, per table, nt-1
-  // pair planes [W][2] = (alpha_j, alpha_j+1) per wavenumber: one 16-byte load per table and
-  // layer (kernels.hpp, "Table layout").  `cia_interp` (BARTRT_CIA_INTERP):
-  // spline (default: the reading of the reference believed in) -- natural cubic splines in wavenumber
-  // and temperature -- or linear in both;
-  // the temperature spline's second derivatives then ride as one more table per file, whose
-  // weights prep_body fills with the spline's curvature terms, so every RT kernel serves it.
-  std::vector<double> cia_planes, cia_temp;
-  PrepArgs &pa = prep;
-  {
-    std::string v = cfg_has(cfg, "cia_interp") ? cfg["cia_interp"] : "spline";
-    if (const char *ev = std::getenv("BARTRT_CIA_INTERP")) if (*ev) v = ev;
-    if (v != "linear" && v != "spline") throw IoError{"cia_interp: '" + v + "' is neither linear nor spline"};
-    cia_spline = v == "spline";
-  }
-  // second derivatives of the natural cubic spline through (x, y), n points (n < 3: zero)
-  auto spline_y2 = [](const double *x, const double *y, size_t n, size_t stride, double *y2) {
-    for (size_t i = 0; i < n; i++) y2[i * stride] = 0.0;
-    if (n < 3) return;
-    std::vector<double> u(n, 0.0);
-    for (size_t i = 1; i + 1 < n; i++) {
-      const double sig = (x[i] - x[i - 1]) / (x[i + 1] - x[i - 1]);
-      const double p = sig * y2[(i - 1) * stride] + 2.0;
-      y2[i * stride] = (sig - 1.0) / p;
-      const double d = (y[(i + 1) * stride] - y[i * stride]) / (x[i + 1] - x[i]) -
-                       (y[i * stride] - y[(i - 1) * stride]) / (x[i] - x[i - 1]);
-      u[i] = (6.0 * d / (x[i + 1] - x[i - 1]) - sig * u[i - 1]) / p;
-    }
-    for (size_t k = n - 1; k-- > 1;) y2[k * stride] = y2[k * stride] * y2[(k + 1) * stride] + u[k];
   };
-  if (cfg_has(cfg, "csfile")) {
-    auto files = split_file_list(cfg["csfile"]);
-    if ((int)files.size() * (cia_spline ? 2 : 1) > kMaxCia)
-      throw IoError{cia_spline ? "csfile: too many cross-section files for cia_interp spline (two table slots each)"
-                               : "csfile: too many cross-section files"};
-    for (auto &fn : files) {
-      Cia c = read_cia(fn);
-      int cc = C++;
-      auto f1 = std::find(atm.species.begin(), atm.species.end(), c.s1);
-      auto f2 = std::find(atm.species.begin(), atm.species.end(), c.s2);
-      if (f1 == atm.species.end() || f2 == atm.species.end())
-        throw IoError{"cross-section file '" + fn + "': species not in the atmosphere file"};
-      pa.cia_s1[cc] = (int)(f1 - atm.species.begin());
-      pa.cia_s2[cc] = (int)(f2 - atm.species.begin());
-      pa.cia_nt[cc] = (int)c.temp.size();
-      pa.cia_toff[cc] = (int)cia_temp.size();
-      pa.cia_kind[cc] = 0;
-      const size_t nw = c.wn.size(), ntc = c.temp.size();
-      // resampled planes [nt][Wl] first, then the (lower, upper) pair planes
-      std::vector<double> planes(ntc * (size_t)Wl), y2w(cia_spline ? nw : 0);
-      for (size_t t = 0; t < ntc; t++) {
-        const double *al = c.alpha.data() + t * nw;
-        if (cia_spline) spline_y2(c.wn.data(), al, nw, 1, y2w.data());
-        for (int i = 0; i < Wl; i++) {
-          double x = wn_loc[i], v = 0.0;
-          if (x >= c.wn.front() && x <= c.wn.back() && nw > 1) {
-            size_t j = std::upper_bound(c.wn.begin(), c.wn.end(), x) - c.wn.begin();
-            if (j >= nw) j = nw - 1;
-            if (j == 0) j = 1;
-            double x0 = c.wn[j - 1], x1 = c.wn[j];
-            // np.interp form: slope * (x - x0) + y0
-            v = (al[j] - al[j - 1]) / (x1 - x0) * (x - x0) + al[j - 1];
-            if (x == x1) v = al[j];
-            if (cia_spline) {
-              const double h = x1 - x0, a = (x1 - x) / h, b = (x - x0) / h;
-              v = a * al[j - 1] + b * al[j] + ((a * a * a - a) * y2w[j - 1] + (b * b * b - b) * y2w[j]) * (h * h) / 6.0;
-            }
-          } else if (nw == 1 && x == c.wn.front()) {
-            v = al[0];
-          }
-          planes[t * Wl + i] = v;
+  // `shareOpacity` (code/makecfg.py:106-107: BART's worker processes share ONE opacity grid; a bare key in
+  // the cfg makeTransit writes) or BARTRT_SHARE_OPACITY=1: the first process of this (file, device, block)
+  // uploads the grid, the others map its HBM allocation through an IPC handle (share.hpp)
+  if (share_mode < 0) share_mode = resolve_share_mode(cfg, true);
+  if (share_mode == kShareIpc) {
+    kappa_share = TableShare::attach(share_key(cfg["opacityfile"], device, lo, hi), n * sizeof(double), upload);
+    d_kappa = kappa_share->ptr;
+  } else {
+    kappa_own.reserve(n);
+    upload(kappa_own);
+    d_kappa = kappa_own;
+  }
+}
+
+// second derivatives of the natural cubic spline through (x, y), n points (n < 3: zero)
+static void spline_y2(const double *x, const double *y, size_t n, size_t stride, double *y2) {
+  for (size_t i = 0; i < n; i++) y2[i * stride] = 0.0;
+  if (n < 3) return;
+  std::vector<double> u(n, 0.0);
+  for (size_t i = 1; i + 1 < n; i++) {
+    const double sig = (x[i] - x[i - 1]) / (x[i + 1] - x[i - 1]);
+    const double p = sig * y2[(i - 1) * stride] + 2.0;
+    y2[i * stride] = (sig - 1.0) / p;
+    const double d = (y[(i + 1) * stride] - y[i * stride]) / (x[i + 1] - x[i]) -
+                     (y[i * stride] - y[(i - 1) * stride]) / (x[i] - x[i - 1]);
+    u[i] = (6.0 * d / (x[i + 1] - x[i - 1]) - sig * u[i - 1]) / p;
+  }
+  for (size_t k = n - 1; k-- > 1;) y2[k * stride] = y2[k * stride] * y2[(k + 1) * stride] + u[k];
+}
+
+// One cross-section file on the grid wn[0..Wl): planes [nt][Wl], zero outside the file; linear in wavenumber, or
+// the natural cubic spline through the file's samples
+static std::vector<double> cia_on_grid(const Cia &c, const double *wn, int Wl, bool spline) {
+  const size_t nw = c.wn.size(), ntc = c.temp.size();
+  std::vector<double> planes(ntc * (size_t)Wl), y2w(spline ? nw : 0);
+  for (size_t t = 0; t < ntc; t++) {
+    const double *al = c.alpha.data() + t * nw;
+    if (spline) spline_y2(c.wn.data(), al, nw, 1, y2w.data());
+    for (int i = 0; i < Wl; i++) {
+      double x = wn[i], v = 0.0;
+      if (x >= c.wn.front() && x <= c.wn.back() && nw > 1) {
+        size_t j = std::upper_bound(c.wn.begin(), c.wn.end(), x) - c.wn.begin();
+        if (j >= nw) j = nw - 1;
+        if (j == 0) j = 1;
+        double x0 = c.wn[j - 1], x1 = c.wn[j];
+        // np.interp form: slope * (x - x0) + y0
+        v = (al[j] - al[j - 1]) / (x1 - x0) * (x - x0) + al[j - 1];
+        if (x == x1) v = al[j];
+        if (spline) {
+          const double h = x1 - x0, a = (x1 - x) / h, b = (x - x0) / h;
+          v = a * al[j - 1] + b * al[j] + ((a * a * a - a) * y2w[j - 1] + (b * b * b - b) * y2w[j]) * (h * h) / 6.0;
         }
+      } else if (nw == 1 && x == c.wn.front()) {
+        v = al[0];
       }
-      auto push_pairs = [&](const std::vector<double> &pl) {
-        const size_t npair = std::max<size_t>(ntc - 1, 1);
-        for (size_t t = 0; t < npair; t++) {
-          const size_t hi_t = std::min(t + 1, ntc - 1);
-          for (int i = 0; i < Wl; i++) {
-            cia_planes.push_back(pl[t * Wl + i]);
-            cia_planes.push_back(pl[hi_t * Wl + i]);
-          }
-        }
-      };
-      pa.cia_poff[cc] = (int)(cia_planes.size() / ((size_t)2 * Wl));
-      push_pairs(planes);
-      cia_temp.insert(cia_temp.end(), c.temp.begin(), c.temp.end());
-      if (cia_spline) {
-        // the second table of the file: second derivatives in T of the resampled planes
-        const int c2 = C++;
-        pa.cia_s1[c2] = pa.cia_s1[cc]; pa.cia_s2[c2] = pa.cia_s2[cc];
-        pa.cia_nt[c2] = pa.cia_nt[cc];
-        pa.cia_toff[c2] = (int)cia_temp.size();
-        pa.cia_kind[c2] = 1;
-        std::vector<double> y2t(planes.size(), 0.0);
-        for (int i = 0; i < Wl; i++) spline_y2(c.temp.data(), planes.data() + i, ntc, (size_t)Wl, y2t.data() + i);
-        pa.cia_poff[c2] = (int)(cia_planes.size() / ((size_t)2 * Wl));
-        push_pairs(y2t);
-        cia_temp.insert(cia_temp.end(), c.temp.begin(), c.temp.end());
-      }
+      planes[t * Wl + i] = v;
     }
   }
-  d_cia = dev_upload(cia_planes);
+  return planes;
+}
 
+// planes [ntc][Wl] -> appended to out as max(ntc - 1, 1) pair planes [Wl][2] = (plane t, plane t + 1) per wavenumber
+static void push_pair_planes(const std::vector<double> &pl, size_t ntc, int Wl, std::vector<double> &out) {
+  const size_t npair = std::max<size_t>(ntc - 1, 1);
+  for (size_t t = 0; t < npair; t++) {
+    const size_t hi_t = std::min(t + 1, ntc - 1);
+    for (int i = 0; i < Wl; i++) {
+      out.push_back(pl[t * Wl + i]);
+      out.push_back(pl[hi_t * Wl + i]);
+    }
+  }
+}
+
+// Stage 8 (host only): CIA, resampled on the local grid (zero outside the file) and laid out, per table, as nt-1
+// pair planes [W][2] = (alpha_j, alpha_j+1) per wavenumber: one 16-byte load per table and
+// layer (kernels.hpp, "Table layout").  Under `cia_interp spline`
+// the temperature spline's second derivatives ride as one more table per file, whose
+// weights prep_body fills with the spline's curvature terms, so every RT kernel serves it.
+void Engine::resample_cia(std::vector<double> &cia_planes, std::vector<double> &cia_temp) {
+  if (!cfg_has(cfg, "csfile")) return;
+  PrepArgs &pa = prep;
+  const int Wl = W();
+  auto files = split_file_list(cfg["csfile"]);
+  if ((int)files.size() * (cia_spline ? 2 : 1) > kMaxCia)
+    throw IoError{cia_spline ? "csfile: too many cross-section files for cia_interp spline (two table slots each)"
+                             : "csfile: too many cross-section files"};
+  for (auto &fn : files) {
+    Cia c = read_cia(fn);
+    int cc = C++;
+    auto f1 = std::find(atm.species.begin(), atm.species.end(), c.s1);
+    auto f2 = std::find(atm.species.begin(), atm.species.end(), c.s2);
+    if (f1 == atm.species.end() || f2 == atm.species.end())
+      throw IoError{"cross-section file '" + fn + "': species not in the atmosphere file"};
+    pa.cia_s1[cc] = (int)(f1 - atm.species.begin());
+    pa.cia_s2[cc] = (int)(f2 - atm.species.begin());
+    pa.cia_nt[cc] = (int)c.temp.size();
+    pa.cia_toff[cc] = (int)cia_temp.size();
+    pa.cia_kind[cc] = 0;
+    const size_t ntc = c.temp.size();
+    // resampled planes [nt][Wl] first, then the (lower, upper) pair planes
+    const std::vector<double> planes = cia_on_grid(c, wn_full.data() + lo, Wl, cia_spline);
+    pa.cia_poff[cc] = (int)(cia_planes.size() / ((size_t)2 * Wl));
+    push_pair_planes(planes, ntc, Wl, cia_planes);
+    cia_temp.insert(cia_temp.end(), c.temp.begin(), c.temp.end());
+    if (cia_spline) {
+      // the second table of the file: second derivatives in T of the resampled planes
+      const int c2 = C++;
+      pa.cia_s1[c2] = pa.cia_s1[cc]; pa.cia_s2[c2] = pa.cia_s2[cc];
+      pa.cia_nt[c2] = pa.cia_nt[cc];
+      pa.cia_toff[c2] = (int)cia_temp.size();
+      pa.cia_kind[c2] = 1;
+      std::vector<double> y2t(planes.size(), 0.0);
+      for (int i = 0; i < Wl; i++) spline_y2(c.temp.data(), planes.data() + i, ntc, (size_t)Wl, y2t.data() + i);
+      pa.cia_poff[c2] = (int)(cia_planes.size() / ((size_t)2 * Wl));
+      push_pair_planes(y2t, ntc, Wl, cia_planes);
+      cia_temp.insert(cia_temp.end(), c.temp.begin(), c.temp.end());
+    }
+  }
+}
+
+// hydrostatic reference layer (makeatm.py:229-247)
+static void hydrostatic_reference(PrepArgs &pa, const std::vector<double> &press, double refpress) {
+  const int L = (int)press.size();
+  int ix = 0;
+  double best = std::fabs(press[0] - refpress);
+  for (int i = 1; i < L; i++) {
+    double d = std::fabs(press[i] - refpress);
+    if (d < best) { best = d; ix = i; }
+  }
+  pa.ref_idx = ix;
+  pa.ref_exact = press[ix] == refpress;
+  pa.ref_ib = ix < L - 1 ? ix : ix - 1;
+  pa.ref_f = ix < L - 1 ? 0.0 : 1.0;
+  if (L == 1) { pa.ref_ib = 0; pa.ref_f = 0.0; }
+  double lp0 = std::log10(refpress);
+  for (int i = 0; i + 1 < L; i++) {
+    double la = std::log10(press[i]), lb = std::log10(press[i + 1]);
+    if ((lp0 <= la && lp0 >= lb) || (lp0 >= la && lp0 <= lb)) {
+      pa.ref_ib = i;
+      pa.ref_f = (lp0 - la) / (lb - la);
+      break;
+    }
+  }
+  pa.ref_lnp = std::log(refpress / press[ix]);
+}
+
+// Stage 9: the CIA planes and the per-layer constants to HBM; the static part of PrepArgs and RtArgs.
+void Engine::upload_constants(const std::vector<double> &cia_planes, const std::vector<double> &cia_temp) {
+  PrepArgs &pa = prep;
+  const int Wl = W();
+  d_cia.upload(cia_planes);
   std::vector<double> dlnp(std::max(L - 1, 1), 0.0);
   for (int l = 0; l + 1 < L; l++) dlnp[l] = std::log(atm.press[l] / atm.press[l + 1]);
-  d_press = dev_upload(atm.press);
-  d_mass = dev_upload(mass);
-  {
-    std::vector<double> diam(S);
-    for (int s = 0; s < S; s++) diam[s] = mol.diam[mol.find_name(atm.species[s])] * 1e-8;
-    d_diam = dev_upload(diam);
-  }
-
-  // hydrostatic reference layer (makeatm.py:229-247)
-  {
-    int ix = 0;
-    double best = std::fabs(atm.press[0] - refpress);
-    for (int i = 1; i < L; i++) {
-      double d = std::fabs(atm.press[i] - refpress);
-      if (d < best) { best = d; ix = i; }
-    }
-    pa.ref_idx = ix;
-    pa.ref_exact = atm.press[ix] == refpress;
-    pa.ref_ib = ix < L - 1 ? ix : ix - 1;
-    pa.ref_f = ix < L - 1 ? 0.0 : 1.0;
-    if (L == 1) { pa.ref_ib = 0; pa.ref_f = 0.0; }
-    double lp0 = std::log10(refpress);
-    for (int i = 0; i + 1 < L; i++) {
-      double la = std::log10(atm.press[i]), lb = std::log10(atm.press[i + 1]);
-      if ((lp0 <= la && lp0 >= lb) || (lp0 >= la && lp0 <= lb)) {
-        pa.ref_ib = i;
-        pa.ref_f = (lp0 - la) / (lb - la);
-        break;
-      }
-    }
-    pa.ref_lnp = std::log(refpress / atm.press[ix]);
-  }
+  d_press.upload(atm.press);
+  d_mass.upload(mass);
+  std::vector<double> diam(S);
+  for (int s = 0; s < S; s++) diam[s] = mol.diam[mol.find_name(atm.species[s])] * 1e-8;
+  d_diam.upload(diam);
+  hydrostatic_reference(pa, atm.press, refpress);
   pa.L = L; pa.S = S; pa.M = M; pa.Nt = Nt; pa.C = C; pa.W = Wl;
   {
     // prep_profiles' constants in one block (layout: kernels.hpp, PrepArgs::consts)
@@ -523,7 +525,7 @@ void Engine::setup(const TCfg &cfg_in, int shard_rank, int shard_n) {
         const double *g = cia_temp.data() + pa.cia_toff[c];
         blob[at + cia_temp.size() + pa.cia_toff[c] + j] = 1.0 / (g[j + 1] - g[j]);
       }
-    d_prep_consts = dev_upload(blob);
+    d_prep_consts.upload(blob);
   }
   pa.consts = d_prep_consts;
   if (M > kMaxMol) throw IoError{"more opacity-table molecules than the kernels are built for (16)"};
@@ -545,7 +547,11 @@ void Engine::setup(const TCfg &cfg_in, int shard_rank, int shard_n) {
     r.wq[a] = r.wgt[a] * r.invmu[a];
     r.mu[a] = std::cos(angles[a] * kPI / 180.0);
   }
-  if (!have_table && cfg_has(cfg, "linedb")) {
+}
+
+// Stage 10: the line list (an engine without a table), the first workspaces, and the warm-up launches.
+void Engine::start_workspaces() {
+  if (!cfg_has(cfg, "opacityfile") && cfg_has(cfg, "linedb")) {
     lbl_init(*this, cfg["linedb"]);
     const char *m = std::getenv("BARTRT_LBL");
     // measured on the config-5 shape (tools/lbl_bench.py): tiles rarely turn opaque
@@ -554,63 +560,73 @@ void Engine::setup(const TCfg &cfg_in, int shard_rank, int shard_n) {
     // (the fused kernel evaluates the line sums on the output points: no oversampling)
     lbl_eager = !(m && std::string(m) == "lazy") || lbl->dev.osamp > 1 || lbl->dev.voigt_grid;
   }
-  HIPCHK(hipMalloc(&d_tau, sizeof(double) * (size_t)Wl * L));
-  HIPCHK(hipMalloc(&d_last, sizeof(int) * (size_t)Wl));
+  d_tau.reserve((size_t)W() * L);
+  d_last.reserve((size_t)W());
   ensure_walkers(16);
   // The first launch of a kernel loads its code object (the single-wave kernels' translation unit is 10 MB: 20 ms,
   // seen as ONE 20 ms call among the first of a run -- round 5, three worker processes on the chain service).  The
   // atmosphere file's own profile goes through a one-walker and a twelve-walker launch here, once, so that the
   // first MCMC step does not pay it (BARTRT_WARMUP=0: off).  Table path of the eclipse geometry.
-  {
-    const char *wv = std::getenv("BARTRT_WARMUP");
-    if (!(wv && wv[0] == '0') && solution == 0 && !lbl && M > 0) {
-      const int nprof = (S + 1) * L, nw = 12;
-      std::vector<double> hp((size_t)nw * nprof);
-      for (int w = 0; w < nw; w++)
-        for (int l = 0; l < L; l++) {
-          hp[(size_t)w * nprof + l] = atm.temp[l];
-          for (int k = 0; k < S; k++) hp[(size_t)w * nprof + (size_t)(k + 1) * L + l] = atm.abund[(size_t)l * S + k];
-        }
-      HIPCHK(hipMemcpy(d_prof, hp.data(), sizeof(double) * hp.size(), hipMemcpyHostToDevice));
-      run_dev(d_prof, 1, d_spec, d_ok, stream, false);
-      run_dev(d_prof, nw, d_spec, d_ok, stream, false);
-      HIPCHK(hipStreamSynchronize(stream));
-      last_prof = nullptr;
-      last_n = 0;
+  const char *wv = std::getenv("BARTRT_WARMUP");
+  if ((wv && wv[0] == '0') || solution != 0 || lbl || M == 0) return;
+  const int nprof = (S + 1) * L, nw = 12;
+  std::vector<double> hp((size_t)nw * nprof);
+  for (int w = 0; w < nw; w++)
+    for (int l = 0; l < L; l++) {
+      hp[(size_t)w * nprof + l] = atm.temp[l];
+      for (int k = 0; k < S; k++) hp[(size_t)w * nprof + (size_t)(k + 1) * L + l] = atm.abund[(size_t)l * S + k];
     }
-  }
+  HIPCHK(hipMemcpy(d_prof, hp.data(), sizeof(double) * hp.size(), hipMemcpyHostToDevice));
+  run_dev(d_prof, 1, d_spec, rec[0].ok, stream, false);
+  run_dev(d_prof, nw, d_spec, rec[0].ok, stream, false);
+  HIPCHK(hipStreamSynchronize(stream));
+  last_prof = nullptr;
+  last_n = 0;
+}
+
+void Engine::setup(const TCfg &cfg_in, int shard_rank, int shard_n) {
+  cfg = cfg_in;
+  read_settings();
+  generate_missing_opacity_file(shard_rank);
+  read_atmosphere();
+  OpacityHeader oh;
+  read_grid(oh, shard_rank, shard_n);
+  read_geometry();
+  open_device();
+  upload_table(oh);
+  std::vector<double> cia_planes, cia_temp;
+  resample_cia(cia_planes, cia_temp);
+  upload_constants(cia_planes, cia_temp);
+  start_workspaces();
 }
 
 void Engine::ensure_walkers(int n) {
   if (n <= cap_walkers) return;
   int cap = std::max(n, cap_walkers * 2);
   HIPCHK(hipDeviceSynchronize());
-  auto re = [&](auto *&p, size_t count) {
-    if (p) HIPCHK(hipFree(p));
-    p = nullptr;
-    HIPCHK(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(*p)));
-  };
   if (last_prof == d_prof) last_prof = nullptr;
   pf_have_prof = nullptr;   // (prefetched records, if any, are dropped with their buffers' sizes)
   if (cap2) {
-    re(d_coef2, (size_t)cap * L * coef_stride(M, C));
-    re(d_idx2, (size_t)cap * L * idx_stride(C));
-    re(d_kstop2, (size_t)cap);
-    re(d_ok2, (size_t)cap);
+    rec[1].reserve((size_t)cap, L, M, C);
     cap2 = cap;
   }
-  re(d_prof, (size_t)cap * (S + 1) * L);
-  re(d_coef, (size_t)cap * L * coef_stride(M, C));
-  re(d_idx, (size_t)cap * L * idx_stride(C));
-  re(d_kstop, (size_t)cap);
-  re(d_ok, (size_t)cap);
-  re(d_spec, (size_t)cap * W());
-  re(d_rad, (size_t)cap * L);
+  d_prof.reserve((size_t)cap * (S + 1) * L);
+  rec[0].reserve((size_t)cap, L, M, C);
+  d_spec.reserve((size_t)cap * W());
+  d_rad.reserve((size_t)cap * L);
   if (solution == 1) {
-    re(d_rtop, (size_t)cap * L);
-    re(d_ds, (size_t)cap * chord_table_size(L));
+    d_rtop.reserve((size_t)cap * L);
+    d_ds.reserve((size_t)cap * chord_table_size(L));
   }
   cap_walkers = cap;
+}
+
+// the second set of record buffers, as large as the first (nothing is prefetched into it yet)
+void Engine::ensure_second_set() {
+  if (cap2 >= cap_walkers) return;
+  HIPCHK(hipDeviceSynchronize());
+  rec[1].reserve((size_t)cap_walkers, L, M, C);
+  cap2 = cap_walkers;
 }
 
 void Engine::wait(hipStream_t st) {
@@ -628,45 +644,46 @@ void Engine::wait(hipStream_t st) {
 }
 
 void Engine::ensure_pin(size_t bytes) {
-  if (bytes <= h_pin_bytes) return;
-  if (h_pin) HIPCHK(hipHostFree(h_pin));
-  h_pin = nullptr;
+  const size_t n = (bytes + sizeof(double) - 1) / sizeof(double);
+  if (n <= h_pin.count()) return;
   last_prof = nullptr;
-  HIPCHK(hipHostMalloc(&h_pin, bytes, hipHostMallocDefault));
-  h_pin_bytes = bytes;
+  h_pin.reserve(n);
+}
+
+// [n] walkers in chunks of `chunk`.  The walkers' one-shot radius / cloud / scattering overrides are [n][3]:
+// every chunk gets its own rows (run_chunk consumes the pointer it is given, so it is re-armed per chunk).
+// with_ext: the chunk's line-by-line extinction first ([walkers][L][W], lbl_extinction), for run_chunk to read.
+void Engine::run_chunks(const double *d_prof_in, int n, int chunk, double *d_spec_out, unsigned char *d_okp,
+                        hipStream_t st, bool want_tau, bool with_ext) {
+  const int nprof = (S + 1) * L;
+  const double *over = prep_over_once;
+  for (int off = 0; off < n; off += chunk) {
+    const int m = std::min(chunk, n - off);
+    if (with_ext) lbl_extinction(*this, d_prof_in + (size_t)off * nprof, m, st);
+    prep_over_once = over ? over + (size_t)3 * off : nullptr;
+    run_chunk(d_prof_in + (size_t)off * nprof, m, d_spec_out + (size_t)off * W(),
+              (d_okp ? d_okp : rec[0].ok.get()) + off, st, want_tau, with_ext ? lbl->d_ext.get() : nullptr);
+  }
+  prep_over_once = nullptr;
 }
 
 void Engine::run_dev(const double *d_prof_in, int n, double *d_spec_out,
                      unsigned char *d_okp, hipStream_t st, bool want_tau) {
   if (n <= 0) return;
-  // per-walker workspaces (records, flags) are sized by cap_walkers; the
-  // caller's profile and spectrum buffers are used in place
+  // per-walker workspaces (records, flags) are sized by cap_walkers; the caller's profiles and spectra are used in place
   if (n > cap_walkers && d_prof_in != d_prof) ensure_walkers(n);
   if (lbl && solution == 0 && !want_tau && !want_intens && !lbl_eager && integ == 0 && !cut_slant) {
-    // lazy fused path: layers' line sums are evaluated only as deep as the
-    // optical depth requires
+    // lazy fused path: layers' line sums are evaluated only as deep as the optical depth requires
     run_chunk(d_prof_in, n, d_spec_out, d_okp, st, false, nullptr, true);
     return;
   }
   if (lbl) {
-    // eager path (optical-depth / intensity outputs, transit geometry):
-    // [walkers][L][W] extinction first, in bounded chunks.  The walkers' one-shot
-    // radius / cloud / scattering overrides are [n][3]: every chunk gets its own
-    // rows (run_chunk consumes the pointer it is given, so it is re-armed per chunk).
+    // eager path (optical-depth / intensity outputs, transit geometry): [walkers][L][W] extinction first, in chunks
     const size_t per = (size_t)L * W() * sizeof(double);
     size_t cap_bytes = (size_t)2 << 30;
     if (const char *c = std::getenv("BARTRT_LBL_CHUNK_BYTES")) cap_bytes = std::max<size_t>(1, std::strtoull(c, nullptr, 10));
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, cap_bytes / per));
-    const int nprof = (S + 1) * L;
-    const double *over = prep_over_once;
-    for (int off = 0; off < n; off += chunk) {
-      const int m = std::min(chunk, n - off);
-      lbl_extinction(*this, d_prof_in + (size_t)off * nprof, m, st);
-      prep_over_once = over ? over + (size_t)3 * off : nullptr;
-      run_chunk(d_prof_in + (size_t)off * nprof, m, d_spec_out + (size_t)off * W(),
-                (d_okp ? d_okp : d_ok) + off, st, want_tau, lbl->d_ext);
-    }
-    prep_over_once = nullptr;
+    run_chunks(d_prof_in, n, chunk, d_spec_out, d_okp, st, want_tau, true);
     return;
   }
   // `cut slant`, rule 1: the single-wave kernels keep an event log of 100 bytes per (walker, wavenumber) lane
@@ -680,66 +697,44 @@ void Engine::run_dev(const double *d_prof_in, int n, double *d_spec_out,
     const size_t per = std::max<size_t>(1, slant_log_bytes(1, (W() + 63) / 64, 64, A));
     const int chunk = (int)std::max<size_t>(1, cap / per);
     if (n > chunk) {
-      const int nprof = (S + 1) * L;
-      const double *over = prep_over_once;
-      for (int off = 0; off < n; off += chunk) {
-        const int m = std::min(chunk, n - off);
-        prep_over_once = over ? over + (size_t)3 * off : nullptr;
-        run_chunk(d_prof_in + (size_t)off * nprof, m, d_spec_out + (size_t)off * W(), (d_okp ? d_okp : d_ok) + off, st, want_tau, nullptr);
-      }
-      prep_over_once = nullptr;
+      run_chunks(d_prof_in, n, chunk, d_spec_out, d_okp, st, want_tau, false);
       return;
     }
   }
   run_chunk(d_prof_in, n, d_spec_out, d_okp, st, want_tau, nullptr);
 }
 
-void Engine::run_chunk(const double *d_prof_in, int n, double *d_spec_out,
-                       unsigned char *d_okp, hipStream_t st, bool want_tau, const double *d_ext,
-                       bool lbl_fused) {
-  // coefficient workspaces are sized by cap_walkers; the caller's profile and
-  // spectrum buffers are used in place
-  if (n > cap_walkers) ensure_walkers(n);
-  // prefetched preparation: only the plain table path of the eclipse geometry takes part
-  const bool pf_ok = !prep_hook && !prep_over_once && !lbl_fused && !d_ext && solution == 0 && !want_tau &&
-                     !want_intens && !lbl;
+// The prefetch decision of one run_chunk call (prefetched preparation, engine.hpp)
+struct Engine::Prefetch {
+  bool have, want_next;  // the records were prepared by the previous call's RT launch; this one's prepares pf_req_*
+  int bset;         // the record set this call's RT kernel reads (the other one takes the next batch's)
+  PrepSettings now; // the settings the layer records are built from, as they stand for THIS call
+};
+
+Engine::Prefetch Engine::plan_prefetch(bool pf_ok, const double *d_prof_in, int n, const double *d_spec_out,
+                                       const unsigned char *d_okp, hipStream_t st) {
   bool want_next = pf_ok && pf_req_prof && pf_req_n > 0;
   if (want_next && pf_req_n > cap_walkers) {
     // the workspaces have to grow for the named batch: not under a call whose own buffers are the
     // engine's (a host-buffer batch: growing frees what it is about to read and write) -- such a
     // request is dropped, the named batch is prepared by its own call
-    const bool own = d_prof_in == d_prof || d_spec_out == d_spec || d_okp == d_ok;
+    const bool own = d_prof_in == d_prof || d_spec_out == d_spec || d_okp == rec[0].ok;
     if (own) want_next = false;
     else ensure_walkers(pf_req_n);   // (drops prefetched records)
   }
-  // the settings the layer records are built from, as they stand for THIS call: records prefetched
-  // under other settings (a bartrt_set_radius / _cloudtop / _scattering in between) or on another
-  // stream are not used -- the call prepares its own
+  // records prefetched under other settings (a bartrt_set_radius / _cloudtop / _scattering in between) or on
+  // another stream are not used -- the call prepares its own
   const PrepSettings now{refradius, gsurf, cloudtop, scat_value, cloud_rup, cloud_rdown, cloud_ext, has_cloud, scat_flag};
   const bool have = pf_ok && pf_have_prof && pf_have_prof == d_prof_in && pf_have_n == n && pf_have_stream == st &&
                     pf_have_set == now;
-  const int bset = have ? pf_have_buf : 0;        // record buffers this call's RT kernel reads
+  const int bset = have ? pf_have_buf : 0;
   pf_have_prof = nullptr;
-  if (want_next) {
-    if (cap2 < cap_walkers) {   // first request: the second set of record buffers (nothing prefetched yet)
-      HIPCHK(hipDeviceSynchronize());
-      auto re2 = [&](auto *&p, size_t count) {
-        if (p) HIPCHK(hipFree(p));
-        p = nullptr;
-        HIPCHK(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(*p)));
-      };
-      re2(d_coef2, (size_t)cap_walkers * L * coef_stride(M, C));
-      re2(d_idx2, (size_t)cap_walkers * L * idx_stride(C));
-      re2(d_kstop2, (size_t)cap_walkers);
-      re2(d_ok2, (size_t)cap_walkers);
-      cap2 = cap_walkers;
-    }
-  }
-  const bool use_have = have;
-  double *coef_b[2] = {d_coef, d_coef2};
-  idx_t *idx_b[2] = {d_idx, d_idx2};
-  int *kstop_b[2] = {d_kstop, d_kstop2};
-  unsigned char *ok_b[2] = {d_ok, d_ok2};
+  if (want_next) ensure_second_set();   // (first request)
+  return Prefetch{have, want_next, bset, now};
+}
+
+// PrepArgs of one call: the engine's settings as they stand, the records into set `records`
+PrepArgs Engine::prep_args(const double *d_prof_in, int n, unsigned char *d_okp, const RecordSet &records) {
   PrepArgs pa = prep;
   pa.nwalkers = n;
   pa.prof = d_prof_in;
@@ -747,37 +742,42 @@ void Engine::run_chunk(const double *d_prof_in, int n, double *d_spec_out,
   pa.scat_flag = scat_flag; pa.scat_value = scat_value;
   pa.has_cloud = has_cloud; pa.cloudtop = cloudtop;
   pa.cloud_rup = cloud_rup; pa.cloud_rdown = cloud_rdown; pa.cloud_ext = cloud_ext;
-  pa.coef = coef_b[bset]; pa.idx = idx_b[bset]; pa.kstop = kstop_b[bset];
-  pa.ok = d_okp ? d_okp : d_ok;
+  pa.coef = records.coef; pa.idx = records.idx; pa.kstop = records.kstop;
+  pa.ok = d_okp ? d_okp : rec[0].ok.get();
   pa.rad_out = d_rad;
   pa.over = prep_over_once;
-  const bool over_cloud = prep_over_cloud && (prep_over_once || prep_hook);
-  prep_over_once = nullptr;
-  pa.rtop = solution == 1 ? d_rtop : nullptr;
-  pa.ds = solution == 1 ? d_ds : nullptr;
-  // one to four walkers of the plain table path: the RT kernel may prepare them itself (launch_rt_folded, below)
-  const bool try_fold = !use_have && !prep_hook && !want_next && solution == 0 && !lbl && !d_ext && !lbl_fused && !want_tau &&
-                        !want_intens && std::max(n, sel_walkers) <= 4 && integ == 1 && cut_slant && A == 5;
-  if (use_have) {
-    // prepared by the previous call's RT launch; its flags go where this call wants them
-    if (d_okp) HIPCHK(hipMemcpyAsync(d_okp, ok_b[bset], (size_t)n, hipMemcpyDeviceToDevice, st));
-  } else if (prep_hook) HIPCHK(prep_hook(pa, st, prep_hook_ctx));
-  else if (!try_fold) HIPCHK(launch_prep(pa, st));
-  if (solution == 1) HIPCHK(launch_chord_table(pa, st));
+  pa.rtop = solution == 1 ? d_rtop.get() : nullptr;
+  pa.ds = solution == 1 ? d_ds.get() : nullptr;
+  return pa;
+}
 
+// one wave per workgroup at every batch size (measured against 128 and 256 lanes:
+// 2-5 % faster from 64 walkers up, finer turnover of the SIMDs' wave slots)
+static int rt_block() {
+  // A/B runs: 64 (default), 128 or 256 lanes per workgroup
+  static const int b = [] { const char *e = std::getenv("BARTRT_BLOCK"); return e ? std::atoi(e) : 64; }();
+  return (b == 128 || b == 256) ? b : 64;
+}
+
+// RtArgs of one call.  Not a getter: it grows d_intens / d_slog / d_walked when the call needs them (d_slog after a
+// device synchronisation), clears d_walked on st and, when timed, makes the events and records the fused path's first
+RtArgs Engine::rt_args(const PrepArgs &pa, const Prefetch &pf, double *d_spec_out, bool want_tau, const double *d_ext,
+                       bool lbl_fused, bool over_cloud, bool timed, hipStream_t st) {
+  const int n = pa.nwalkers, block = rt_block();
   RtArgs r = rt;
   r.nwalkers = n;
   r.nsel = sel_walkers > n ? sel_walkers : 0;
   if (kernel_by_local) r.Wfull = r.W;
-  r.coef = coef_b[bset]; r.idx = idx_b[bset]; r.kstop = kstop_b[bset];
+  r.coef = pa.coef; r.idx = pa.idx; r.kstop = pa.kstop;
   r.ext = d_ext;
   r.nprep = 0;
-  if (want_next) {
+  if (pf.want_next) {
+    const RecordSet &next = rec[1 - pf.bset];
     PrepArgs pn = pa;      // same engine settings; the next batch's profiles into the other buffer set
     pn.nwalkers = pf_req_n;
     pn.prof = pf_req_prof;
-    pn.coef = coef_b[1 - bset]; pn.idx = idx_b[1 - bset]; pn.kstop = kstop_b[1 - bset];
-    pn.ok = ok_b[1 - bset];
+    pn.coef = next.coef; pn.idx = next.idx; pn.kstop = next.kstop;
+    pn.ok = next.ok;
     pn.over = nullptr;
     pn.rad_out = nullptr;   // (bartrt_get_radius: the radii of the batch this call computes)
     r.nprep = pf_req_n;
@@ -789,20 +789,13 @@ void Engine::run_chunk(const double *d_prof_in, int n, double *d_spec_out,
   r.toomuch = toomuch;
   if (cut_slant) slant_thresholds(r);
   r.spec = d_spec_out;
-  r.tau_out = (want_tau && n == 1) ? d_tau : nullptr;
-  r.last_out = (want_tau && n == 1) ? d_last : nullptr;
+  r.tau_out = (want_tau && n == 1) ? d_tau.get() : nullptr;
+  r.last_out = (want_tau && n == 1) ? d_last.get() : nullptr;
   r.intens_out = nullptr;
   if (want_intens && n == 1 && solution == 0) {
-    if (!d_intens) HIPCHK(hipMalloc(&d_intens, sizeof(double) * (size_t)A * W()));
+    d_intens.reserve((size_t)A * W());
     r.intens_out = d_intens;
   }
-  // one wave per workgroup at every batch size (measured against 128 and 256 lanes:
-  // 2-5 % faster from 64 walkers up, finer turnover of the SIMDs' wave slots)
-  static const int block = [] {
-    const char *e = std::getenv("BARTRT_BLOCK");   // A/B runs: 64 (default), 128 or 256 lanes per workgroup
-    const int b = e ? std::atoi(e) : 64;
-    return (b == 128 || b == 256) ? b : 64;
-  }();
   r.ntiles = (r.W + block - 1) / block;
   r.rtop = d_rtop; r.ds = d_ds;
   r.slog = nullptr;
@@ -810,24 +803,17 @@ void Engine::run_chunk(const double *d_prof_in, int n, double *d_spec_out,
     // the event log of rule 1's single-wave `cut slant` kernels (rt_eclipse_s1s.hpp): 100 bytes per lane
     // (rules 0 / 2 -- rt_eclipse_fast<SLANT> -- keep none)
     const size_t need = slant_log_bytes(n, r.ntiles, block, A);
-    if (need > slog_cap) {
+    if (need > d_slog.count()) {
       HIPCHK(hipDeviceSynchronize());   // (an earlier launch on any stream may still write the old log)
-      if (d_slog) HIPCHK(hipFree(d_slog));
-      d_slog = nullptr;
-      slog_cap = 0;
-      HIPCHK(hipMalloc(&d_slog, need));
-      slog_cap = need;
+      d_slog.reserve(need);
     }
-    r.slog = d_slog;
+    r.slog = d_slog.get();
   }
   r.inv_starrad2 = solution == 1 ? 1.0 / (starrad * starrad) : 0.0;
   r.transparent = transparent ? 1 : 0;
   // Timing: the RT kernel's own dispatch stamps the two events (BARTRT_RT_LAUNCH) -- no marker
   // packets in the stream; only the fused line-by-line path (several kernels) is bracketed
   // by event records.
-  // (a call that launches nothing -- no walkers -- takes no event pair: bartrt_timing_end
-  // would read events no dispatch has stamped)
-  const bool timed = timing && n > 0 && r.W > 0 && (timing_seen++ % timing_stride == 0);
   r.ev_start = r.ev_stop = nullptr;
   if (timed) {
     while ((int)ev.size() < ev_used + 2) {
@@ -842,16 +828,40 @@ void Engine::run_chunk(const double *d_prof_in, int n, double *d_spec_out,
   if (want_walked && solution == 0 && !lbl_fused) {
     // the finest column any eclipse kernel records is ONE wavenumber wide (rt_eclipse_quad with one ray per lane, R = 8)
     const size_t need = (size_t)n * ((size_t)r.W + 64);
-    if (need > walked_cap) {
-      if (d_walked) HIPCHK(hipFree(d_walked));
-      d_walked = nullptr;
-      HIPCHK(hipMalloc(&d_walked, need * sizeof(int)));
-      walked_cap = need;
-    }
+    d_walked.reserve(need);
     HIPCHK(hipMemsetAsync(d_walked, 0, need * sizeof(int), st));
     r.walked_out = d_walked;
     walked_nwalkers = n;
   }
+  return r;
+}
+
+void Engine::run_chunk(const double *d_prof_in, int n, double *d_spec_out,
+                       unsigned char *d_okp, hipStream_t st, bool want_tau, const double *d_ext,
+                       bool lbl_fused) {
+  // coefficient workspaces are sized by cap_walkers; the caller's profile and spectrum buffers are used in place
+  if (n > cap_walkers) ensure_walkers(n);
+  // prefetched preparation: only the plain table path of the eclipse geometry takes part
+  const bool pf_ok = !prep_hook && !prep_over_once && !lbl_fused && !d_ext && solution == 0 && !want_tau &&
+                     !want_intens && !lbl;
+  const Prefetch pf = plan_prefetch(pf_ok, d_prof_in, n, d_spec_out, d_okp, st);
+  const bool use_have = pf.have, want_next = pf.want_next;
+  const PrepArgs pa = prep_args(d_prof_in, n, d_okp, rec[pf.bset]);
+  const bool over_cloud = prep_over_cloud && (prep_over_once || prep_hook);
+  prep_over_once = nullptr;
+  // one to four walkers of the plain table path: the RT kernel may prepare them itself (launch_rt_folded, below)
+  const bool try_fold = !use_have && !prep_hook && !want_next && solution == 0 && !lbl && !d_ext && !lbl_fused && !want_tau &&
+                        !want_intens && std::max(n, sel_walkers) <= 4 && integ == 1 && cut_slant && A == 5;
+  if (use_have) {
+    // prepared by the previous call's RT launch; its flags go where this call wants them
+    if (d_okp) HIPCHK(hipMemcpyAsync(d_okp, rec[pf.bset].ok, (size_t)n, hipMemcpyDeviceToDevice, st));
+  } else if (prep_hook) HIPCHK(prep_hook(pa, st, prep_hook_ctx));
+  else if (!try_fold) HIPCHK(launch_prep(pa, st));
+  if (solution == 1) HIPCHK(launch_chord_table(pa, st));
+
+  // (a call that launches nothing -- no walkers -- takes no event pair: bartrt_timing_end would read unstamped events)
+  const bool timed = timing && n > 0 && rt.W > 0 && (timing_seen++ % timing_stride == 0);
+  const RtArgs r = rt_args(pa, pf, d_spec_out, want_tau, d_ext, lbl_fused, over_cloud, timed, st);
   if (lbl_fused) lbl_rt_eclipse(*this, d_prof_in, n, r, st);
   else if (solution == 1) {
     RtLaunchInfo li;   // (the transit kernels keep no walked-layer record: the name only)
@@ -861,16 +871,16 @@ void Engine::run_chunk(const double *d_prof_in, int n, double *d_spec_out,
   else {
     RtLaunchInfo li;
     bool folded = false;
-    if (try_fold) HIPCHK(launch_rt_folded(r, pa, block, st, &li, &folded));
+    if (try_fold) HIPCHK(launch_rt_folded(r, pa, rt_block(), st, &li, &folded));
     if (!folded) {
       if (try_fold) HIPCHK(launch_prep(pa, st));
       li = RtLaunchInfo{};
-      HIPCHK(launch_rt(r, block, st, &li));
+      HIPCHK(launch_rt(r, rt_block(), st, &li));
     }
     if (want_walked) walked_info = li;
     if (want_next && li.prep_fused) {
-      pf_have_prof = pf_req_prof; pf_have_n = pf_req_n; pf_have_buf = 1 - bset;
-      pf_have_stream = st; pf_have_set = now;
+      pf_have_prof = pf_req_prof; pf_have_n = pf_req_n; pf_have_buf = 1 - pf.bset;
+      pf_have_stream = st; pf_have_set = pf.now;
     }
   }
   pf_req_prof = nullptr;

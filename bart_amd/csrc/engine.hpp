@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 
+#include "devbuf.hpp"
 #include "io.hpp"
 #include "kernels.hpp"
 
@@ -27,8 +28,31 @@ struct TableShare;  // the opacity grid shared between processes (share.hpp)
 struct StepArgs;  // converters around the engine (step.hip)
 struct Lbl;       // line-by-line extinction (lbl.hip)
 struct Comm;      // the ranks' communicator (comm.hpp)
+struct CfState;   // contribution-function tables and workspaces (contrib.hip)
 
-struct Engine {
+// The stream and the timing events, as a base of Engine: a base outlives the members, so every buffer the engine
+// owns (DevBuf / PinBuf members, freed by their own destructors) goes before the events, and the stream goes last.
+struct EngineStream {
+  hipStream_t stream = nullptr;
+  std::vector<hipEvent_t> ev;
+  ~EngineStream();
+};
+
+// One set of layer records as prep_profiles writes them; the engine holds two (prefetched preparation, below)
+struct RecordSet {
+  DevBuf<double> coef;
+  DevBuf<idx_t> idx;
+  DevBuf<int> kstop;
+  DevBuf<unsigned char> ok;
+  void reserve(size_t cap, int L, int M, int C) {   // room for cap walkers
+    coef.reserve(cap * L * coef_stride(M, C));
+    idx.reserve(cap * L * idx_stride(C));
+    kstop.reserve(cap);
+    ok.reserve(cap);
+  }
+};
+
+struct Engine : EngineStream {
   // configuration
   TCfg cfg;
   Atm atm;
@@ -56,36 +80,33 @@ struct Engine {
   bool transparent = false;                              // transit geometry: no opaque core
   int device = 0;
   // device-resident inputs
-  double *d_kappa = nullptr, *d_cia = nullptr, *d_wn = nullptr, *d_wn_full = nullptr;
-  double *d_press = nullptr, *d_mass = nullptr, *d_diam = nullptr;
+  const double *d_kappa = nullptr;    // the table the kernels read: kappa_own's, or kappa_share's mapping
+  DevBuf<double> kappa_own, d_cia, d_wn, d_wn_full, d_press, d_mass, d_diam;
   TableShare *kappa_share = nullptr;  // cfg `shareOpacity`: d_kappa is (or is mapped from) another process's allocation
   int share_mode = -1;                // ShareMode (svc.hpp); -1: resolved from the cfg and the environment by setup()
-  double *d_prep_consts = nullptr;  // PrepArgs::consts
+  DevBuf<double> d_prep_consts;  // PrepArgs::consts
   PrepArgs prep{};  // static part filled at init
   RtArgs rt{};
   // workspaces (grown on demand, never inside a timed launch sequence twice)
   int cap_walkers = 0;
-  double *d_prof = nullptr, *d_coef = nullptr, *d_spec = nullptr;
+  DevBuf<double> d_prof, d_spec;
+  RecordSet rec[2];                   // rec[1]: allocated at the first prefetch request (ensure_second_set)
   const double *last_prof = nullptr;  // profiles of the latest host-buffer call (get_tau, get_intensity)
   int last_n = 0;                     // ... and how many they are
-  idx_t *d_idx = nullptr;
-  int *d_kstop = nullptr;
-  double *d_rtop = nullptr, *d_ds = nullptr;  // transit geometry workspaces
-  double *d_rad = nullptr;     // [cap][L] hydrostatic radii of the last run
-  double *d_intens = nullptr;  // [A][W] of the last single-walker run with want_intens
+  DevBuf<double> d_rtop, d_ds;  // transit geometry workspaces
+  DevBuf<double> d_rad;     // [cap][L] hydrostatic radii of the last run
+  DevBuf<double> d_intens;  // [A][W] of the last single-walker run with want_intens
   bool want_intens = false;
   bool lbl_eager = true;       // full extinction first (default); BARTRT_LBL=lazy: fused kernel
-  unsigned char *d_ok = nullptr;
-  double *d_tau = nullptr;  // [W][L] of the last single-walker run
-  int *d_last = nullptr;
-  double *h_pin = nullptr;  // pinned staging
-  size_t h_pin_bytes = 0;
-  hipStream_t stream = nullptr;
+  DevBuf<double> d_tau;  // [W][L] of the last single-walker run
+  DevBuf<int> d_last;
+  PinBuf<double> h_pin;  // pinned staging
   // Host calls that wait for their result (bartrt_run_transit, bartrt_step_batch): the stream writes a sequence number
   // into a word of pinned host memory behind the kernels and the calling thread polls it -- 5-7 us sooner per call than
   // hipStreamSynchronize wakes up (measured in the chain service: 121 against 128 us per ten-walker call).
   // BARTRT_SYNC=stream: hipStreamSynchronize.
-  unsigned int *h_flag = nullptr, *d_flag = nullptr;
+  PinBuf<unsigned int> h_flag;
+  unsigned int *d_flag = nullptr;   // h_flag as the device addresses it
   unsigned int flag_seq = 0;
   bool sync_poll = true;
   void wait(hipStream_t st);
@@ -100,15 +121,13 @@ struct Engine {
   bool prep_over_cloud = false;
   // diagnostics of the next RT launches: layers walked per (walker, kernel column)
   bool want_walked = false;
-  int *d_walked = nullptr;
-  size_t walked_cap = 0;
+  DevBuf<int> d_walked;
   int walked_nwalkers = 0;
   RtLaunchInfo walked_info{};
   // timing of RT launches
   bool timing = false;
   int timing_stride = 1;     // events bracket every timing_stride-th launch (a pair of event
   long timing_seen = 0;      // records costs the stream ~5 us: bench.py samples)
-  std::vector<hipEvent_t> ev;
   int ev_used = 0;
   // Prefetched preparation (bartrt_prefetch_profiles_dev): the caller names the NEXT batch's
   // profile buffer; the RT launch of the current call prepares that batch's layer records in
@@ -130,42 +149,49 @@ struct Engine {
   };
   hipStream_t pf_have_stream = nullptr;
   PrepSettings pf_have_set{};
-  double *d_coef2 = nullptr;
-  idx_t *d_idx2 = nullptr;
-  int *d_kstop2 = nullptr;
-  unsigned char *d_ok2 = nullptr;
   int cap2 = 0;                          // walkers the second set holds
-  void *d_slog = nullptr;                // `cut slant`: the single-wave kernels' event log (RtArgs::slog)
-  size_t slog_cap = 0;
-  // per-step converters
+  DevBuf<char> d_slog;                   // `cut slant`: the single-wave kernels' event log (RtArgs::slog), in bytes
+  // per-step converters, line-by-line extinction, contribution functions: owned, null until set up
   StepArgs *step = nullptr;
   Lbl *lbl = nullptr;
+  CfState *cf = nullptr;
 
   ~Engine();
   void init(int argc, const char **argv);
   void setup(const TCfg &cfg_in, int shard_rank, int shard_n);
+  // setup()'s stages, in the order it calls them (engine.hip)
+  void read_settings();
+  void generate_missing_opacity_file(int shard_rank);
+  void read_atmosphere();
+  void read_grid(OpacityHeader &oh, int shard_rank, int shard_n);
+  void read_geometry();
+  void open_device();
+  void upload_table(const OpacityHeader &oh);
+  void resample_cia(std::vector<double> &cia_planes, std::vector<double> &cia_temp);
+  void upload_constants(const std::vector<double> &cia_planes, const std::vector<double> &cia_temp);
+  void start_workspaces();
   void ensure_walkers(int n);
+  void ensure_second_set();
   void ensure_pin(size_t bytes);
   // d_prof_in -> d_spec_out ([n][W]); records events when timing
   void run_dev(const double *d_prof_in, int n, double *d_spec_out, unsigned char *d_okp,
                hipStream_t st, bool want_tau);
   void run_chunk(const double *d_prof_in, int n, double *d_spec_out, unsigned char *d_okp,
                  hipStream_t st, bool want_tau, const double *d_ext, bool lbl_fused = false);
+  // run_dev's chunked forms and the parts of run_chunk (engine.hip)
+  void run_chunks(const double *d_prof_in, int n, int chunk, double *d_spec_out, unsigned char *d_okp,
+                  hipStream_t st, bool want_tau, bool with_ext);
+  struct Prefetch;
+  Prefetch plan_prefetch(bool pf_ok, const double *d_prof_in, int n, const double *d_spec_out,
+                         const unsigned char *d_okp, hipStream_t st);
+  PrepArgs prep_args(const double *d_prof_in, int n, unsigned char *d_okp, const RecordSet &records);
+  RtArgs rt_args(const PrepArgs &pa, const Prefetch &pf, double *d_spec_out, bool want_tau, const double *d_ext,
+                 bool lbl_fused, bool over_cloud, bool timed, hipStream_t st);
 
   // bartrt_comm_init: with a communicator the per-step path gathers the ranks' blocks itself (step.hip).  Owned and
   // destroyed by capi.hip (bartrt_comm_free, bartrt_free_memory, a re-bartrt_init) before the engine goes.
   Comm *comm = nullptr;
   unsigned long long ncollectives = 0;  // collectives this engine has issued (kept across bartrt_comm_free)
 };
-
-struct HipError {
-  hipError_t e;
-  const char *what;
-};
-#define HIPCHK(x)                                  \
-  do {                                             \
-    hipError_t _e = (x);                           \
-    if (_e != hipSuccess) throw HipError{_e, #x};  \
-  } while (0)
 
 }  // namespace bartrt

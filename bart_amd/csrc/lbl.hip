@@ -262,15 +262,13 @@ __global__ void voigt_probe(const double *x, const double *y, double *k, long n)
 
 void lbl_voigt_probe(const double *x, const double *y, double *k, long n) {
   if (n <= 0) return;
-  double *d = nullptr;
-  HIPCHK(hipMalloc(&d, sizeof(double) * 3 * n));
+  DevBuf<double> d;
+  d.reserve(3 * (size_t)n);
   HIPCHK(hipMemcpy(d, x, sizeof(double) * n, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(d + n, y, sizeof(double) * n, hipMemcpyHostToDevice));
   voigt_probe<<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(d, d + n, d + 2 * n, n);
-  hipError_t err = hipDeviceSynchronize();
-  if (err == hipSuccess) err = hipMemcpy(k, d + 2 * n, sizeof(double) * n, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  HIPCHK(err);
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(k, d + 2 * n, sizeof(double) * n, hipMemcpyDeviceToHost));
 }
 
 struct StateArgs {
@@ -1150,21 +1148,6 @@ __global__ __launch_bounds__(256) void lbl_rt_eclipse_k(LblDev d, const double *
 }
 
 // ---------------------------------------------------------------------------
-Lbl::~Lbl() {
-  auto fr = [](void *p) { if (p) (void)hipFree(p); };
-  fr(d_nu0); fr(d_elow); fr(d_gf); fr(d_ztab); fr(d_ztemp); fr(d_liso);
-  fr(d_state); fr(d_smax); fr(d_ext); fr(d_bucket); fr(d_dvmax);
-  fr(d_dgrid); fr(d_lgrid); fr(d_ginfo); fr(d_gK); fr(d_goff); fr(d_gsize); fr(d_ptab);
-}
-
-template <class T>
-static T *upv(const std::vector<T> &v) {
-  T *d = nullptr;
-  HIPCHK(hipMalloc(&d, std::max<size_t>(v.size(), 1) * sizeof(T)));
-  if (!v.empty()) HIPCHK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  return d;
-}
-
 void lbl_init(Engine &e, const std::string &paths) {
   Lbl *b = new Lbl();
   delete e.lbl;
@@ -1239,11 +1222,11 @@ void lbl_init(Engine &e, const std::string &paths) {
         bucket.push_back(q == d.nbucket ? d.gend[g] : j);
       }
     }
-    b->d_bucket = upv(bucket);
+    b->d_bucket.upload(bucket);
     d.bucket = b->d_bucket;
   }
-  b->d_nu0 = upv(nu0); b->d_elow = upv(elow); b->d_gf = upv(gf); b->d_liso = upv(liso);
-  b->d_ztab = upv(ztab); b->d_ztemp = upv(ztemp);
+  b->d_nu0.upload(nu0); b->d_elow.upload(elow); b->d_gf.upload(gf); b->d_liso.upload(liso);
+  b->d_ztab.upload(ztab); b->d_ztemp.upload(ztemp);
   d.nu0 = b->d_nu0; d.elow = b->d_elow; d.gf = b->d_gf; d.liso = b->d_liso;
   d.ztab = b->d_ztab; d.ztemp = b->d_ztemp;
   d.nwidth = cfg_num(e.cfg, "nwidth", 20.0);
@@ -1325,7 +1308,7 @@ void lbl_init(Engine &e, const std::string &paths) {
       };
       const std::vector<double> dg = logspace(dmin, dmax, nd, d.dop_ln0, d.dop_dln);
       const std::vector<double> lg = logspace(lmin, lmax, nl, d.lor_ln0, d.lor_dln);
-      b->d_dgrid = upv(dg); b->d_lgrid = upv(lg);
+      b->d_dgrid.upload(dg); b->d_lgrid.upload(lg);
       d.dgrid = b->d_dgrid; d.lgrid = b->d_lgrid;
       d.ndop = nd; d.nlor = nl;
       // at one state an isotope's Doppler widths follow its lines' centres: a factor nu_hi / nu_lo
@@ -1341,16 +1324,11 @@ static void ensure_states(Engine &e, long nstate, bool need_ext) {
   Lbl *b = e.lbl;
   if (nstate <= b->cap_state && (!need_ext || b->d_ext)) return;
   HIPCHK(hipDeviceSynchronize());
-  auto re = [&](double *&p, size_t n) {
-    if (p) HIPCHK(hipFree(p));
-    p = nullptr;
-    HIPCHK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(double)));
-  };
-  if (!b->d_dvmax) HIPCHK(hipMalloc(&b->d_dvmax, sizeof(int)));
+  b->d_dvmax.reserve(1);
   long cap = std::max(nstate, b->cap_state);
-  re(b->d_state, (size_t)cap * (2 + 3 * b->dev.niso));
-  re(b->d_smax, (size_t)cap * b->dev.ngroup);
-  if (need_ext) re(b->d_ext, (size_t)cap * e.W());
+  b->d_state.reserve((size_t)cap * (2 + 3 * b->dev.niso));
+  b->d_smax.reserve((size_t)cap * b->dev.ngroup);
+  if (need_ext) b->d_ext.reserve((size_t)cap * e.W());
   b->cap_state = cap;
 }
 
@@ -1378,15 +1356,10 @@ static void run_states(Engine &e, StateArgs &sa, AccArgs &aa, hipStream_t st) {
     const long ns = sa.nstate;
     if (ns > b->cap_gstate) {
       HIPCHK(hipDeviceSynchronize());
-      auto re = [&](auto *&p, size_t n) {
-        if (p) HIPCHK(hipFree(p));
-        p = nullptr;
-        HIPCHK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(*p)));
-      };
-      re(b->d_ginfo, (size_t)ns * d.niso * 3);
-      re(b->d_gK, (size_t)ns * d.niso * d.dspan);
-      re(b->d_goff, (size_t)ns * d.niso * d.dspan);
-      re(b->d_gsize, (size_t)ns + 1);
+      b->d_ginfo.reserve((size_t)ns * d.niso * 3);
+      b->d_gK.reserve((size_t)ns * d.niso * d.dspan);
+      b->d_goff.reserve((size_t)ns * d.niso * d.dspan);
+      b->d_gsize.reserve((size_t)ns + 1);
       b->cap_gstate = ns;
     }
     hipLaunchKernelGGL(lbl_grid_layout, dim3(sa.nstate), dim3(64), 0, st, d, b->d_state, b->d_ginfo, b->d_gK,
@@ -1398,12 +1371,7 @@ static void run_states(Engine &e, StateArgs &sa, AccArgs &aa, hipStream_t st) {
     HIPCHK(hipMemcpyAsync(&total, b->d_gsize + ns, sizeof(long), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&dvmax, b->d_dvmax, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (total > b->cap_ptab) {
-      if (b->d_ptab) HIPCHK(hipFree(b->d_ptab));
-      b->d_ptab = nullptr;
-      HIPCHK(hipMalloc(&b->d_ptab, std::max<size_t>((size_t)total, 1) * sizeof(double)));
-      b->cap_ptab = total;
-    }
+    if ((size_t)total > b->d_ptab.count()) b->d_ptab.reserve((size_t)total);   // (no profiles at all: no buffer)
     hipLaunchKernelGGL(lbl_grid_profiles, dim3(d.dspan, d.niso, sa.nstate), dim3(256), 0, st, d, b->d_state,
                        b->d_ginfo, b->d_gK, b->d_goff, b->d_gsize, b->d_ptab);
     HIPCHK(hipGetLastError());
@@ -1492,13 +1460,11 @@ void lbl_write_opacity(Engine &e, const std::string &path, const std::vector<dou
     if (it == ids.end()) ids.push_back(id);
   }
   const int M = (int)ids.size();
-  double *d_tg = nullptr, *d_ab = nullptr, *d_out = nullptr;
-  HIPCHK(hipMalloc(&d_tg, sizeof(double) * Nt));
-  HIPCHK(hipMemcpy(d_tg, tgrid.data(), sizeof(double) * Nt, hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&d_ab, sizeof(double) * e.atm.abund.size()));
-  HIPCHK(hipMemcpy(d_ab, e.atm.abund.data(), sizeof(double) * e.atm.abund.size(), hipMemcpyHostToDevice));
+  DevBuf<double> d_tg, d_ab, d_out;
+  d_tg.upload(tgrid);
+  d_ab.upload(e.atm.abund);
   FILE *fp = std::fopen(path.c_str(), "wb");
-  if (!fp) { (void)hipFree(d_tg); (void)hipFree(d_ab); throw IoError{"cannot create opacity file '" + path + "'"}; }
+  if (!fp) throw IoError{"cannot create opacity file '" + path + "'"};
   long dims[4] = {M, Nt, L, W};
   std::fwrite(dims, sizeof(long), 4, fp);
   std::fwrite(ids.data(), sizeof(int), M, fp);
@@ -1508,9 +1474,9 @@ void lbl_write_opacity(Engine &e, const std::string &path, const std::vector<dou
   // layers in slabs so the device buffer stays bounded: [nl][Nt][M][W]
   const int slab = std::max(1, std::min(L, (int)((size_t)256 * 1024 * 1024 / ((size_t)Nt * G * W * 8) + 1)));
   std::vector<double> host((size_t)slab * Nt * G * W), merged(M == G ? 0 : (size_t)slab * Nt * M * W);
-  HIPCHK(hipMalloc(&d_out, host.size() * sizeof(double)));
-  ensure_states(e, (long)slab * Nt, false);
   try {
+    d_out.reserve(host.size());
+    ensure_states(e, (long)slab * Nt, false);
     for (int l0 = 0; l0 < L; l0 += slab) {
       const int nl = std::min(slab, L - l0);
       StateArgs sa{};
@@ -1536,11 +1502,9 @@ void lbl_write_opacity(Engine &e, const std::string &path, const std::vector<dou
     }
   } catch (...) {
     std::fclose(fp); std::remove(path.c_str());
-    (void)hipFree(d_tg); (void)hipFree(d_ab); (void)hipFree(d_out);
     throw;
   }
   std::fclose(fp);
-  (void)hipFree(d_tg); (void)hipFree(d_ab); (void)hipFree(d_out);
 }
 
 }  // namespace bartrt

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "devbuf.hpp"
 #include "io.hpp"
 #include "kernels.hpp"
 
@@ -61,24 +62,23 @@ struct Lbl {
   Tli tli;
   LblDev dev{};
   long nlines = 0;
-  double *d_nu0 = nullptr, *d_elow = nullptr, *d_gf = nullptr, *d_ztab = nullptr, *d_ztemp = nullptr;
-  int *d_liso = nullptr;
-  long *d_bucket = nullptr;
+  DevBuf<double> d_nu0, d_elow, d_gf, d_ztab, d_ztemp;
+  DevBuf<int> d_liso;
+  DevBuf<long> d_bucket;
   // per-call workspaces
-  double *d_state = nullptr;     // [nstate][3*niso + 2]
-  double *d_smax = nullptr;      // [nstate][ngroup]
-  double *d_ext = nullptr;       // [nstate][W] (extinction mode)
-  int *d_dvmax = nullptr;        // largest oversampling factor among the states of a call
+  DevBuf<double> d_state;        // [nstate][3*niso + 2]
+  DevBuf<double> d_smax;         // [nstate][ngroup]
+  DevBuf<double> d_ext;          // [nstate][W] (extinction mode)
+  DevBuf<int> d_dvmax;           // largest oversampling factor among the states of a call
   long cap_state = 0;
   // width-grid mode (LblDev::voigt_grid): the grids, and per call the profile tables
-  double *d_dgrid = nullptr, *d_lgrid = nullptr;
-  int *d_ginfo = nullptr;        // [nstate][niso][3]: Lorentz index, first Doppler index, Doppler indices used
-  int *d_gK = nullptr;           // [nstate][niso][dspan]: reach of profile (isotope, Doppler index), points either side
-  long *d_goff = nullptr;        // [nstate][niso][dspan]: its offset in d_ptab
-  long *d_gsize = nullptr;       // [nstate + 1]: profile doubles per state, then their total
-  double *d_ptab = nullptr;      // the profiles of the call, state after state
-  long cap_gstate = 0, cap_ptab = 0;
-  ~Lbl();
+  DevBuf<double> d_dgrid, d_lgrid;
+  DevBuf<int> d_ginfo;           // [nstate][niso][3]: Lorentz index, first Doppler index, Doppler indices used
+  DevBuf<int> d_gK;              // [nstate][niso][dspan]: reach of profile (isotope, Doppler index), points either side
+  DevBuf<long> d_goff;           // [nstate][niso][dspan]: its offset in d_ptab
+  DevBuf<long> d_gsize;          // [nstate + 1]: profile doubles per state, then their total
+  DevBuf<double> d_ptab;         // the profiles of the call, state after state
+  long cap_gstate = 0;
 };
 
 // Reads the TLI file(s) named by the cfg's `linedb` (comma / blank separated), merges

@@ -22,28 +22,27 @@ struct StepArgs {
   int grad = 0;                // smoothing radius (0 = none)
   double ptop = 0, pbot = 0;
   int pnode[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  double *d_gw = nullptr;
+  DevBuf<double> d_gw;
   // device
   // abund[L][S] base abundances, ratio[L] H2/He of the base abundances, pbar[L]
   // pressure in bar (atm order), in one block (step_profiles stages it as it lies)
-  double *d_consts = nullptr;
+  DevBuf<double> d_consts;
   int imol[16] = {0};                // [nmolfit] species index of each fitted molecule
   unsigned long long metal_mask = 0; // bit s: species s is a metal
-  int *d_idx0 = nullptr, *d_npts = nullptr, *d_woff = nullptr;  // [F]
+  DevBuf<int> d_idx0, d_npts, d_woff;  // [F]
   // [nwin] per window sample: filter weight (x rprs^2 / stellar flux for eclipse)
-  double *d_gwt = nullptr;
+  DevBuf<double> d_gwt;
   // workspaces
   int cap = 0;
-  double *d_prof = nullptr, *d_spec = nullptr;
-  double *d_over = nullptr;             // [cap][3] per-walker overrides for prep (unfused path)
+  DevBuf<double> d_prof, d_spec;
+  DevBuf<double> d_over;                // [cap][3] per-walker overrides for prep (unfused path)
   // carry-over of the reference's worker (BARTfunc.py:318-324): a T(p) model that raises
   // ValueError leaves the chain's previous temperature profile in place.  Off: such a
   // walker is rejected.  On: walker w of a call is chain w; its last generated profile
   // is kept here ([cap][L], zeros before the first one, like the reference's array)
   int carry = 0;
-  double *d_prevT = nullptr;
-  int *d_status = nullptr;
-  ~StepArgs();
+  DevBuf<double> d_prevT;
+  DevBuf<int> d_status;
 };
 
 void step_setup(Engine &e, const double *ptargs5, int tint_thorngren, int pttype,

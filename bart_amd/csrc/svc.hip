@@ -162,8 +162,8 @@ void ChainService::run(const int *slots, int n, int nominal, int scat_flag, bool
     std::memcpy(seg.list(), slots, sizeof(int32_t) * (size_t)n);
     hipLaunchKernelGGL(svc_gather, dim3(n), dim3(256), 0, e->stream, d_prof, d_over, d_list, (int)nprof, e->d_prof, d_over_stage);
     e->prep_over_once = any_over ? d_over_stage : nullptr;
-    e->run_dev(e->d_prof, n, e->d_spec, e->d_ok, e->stream, false);
-    hipLaunchKernelGGL(svc_scatter, dim3((unsigned)((Wl + 255) / 256), n), dim3(256), 0, e->stream, e->d_spec, e->d_ok, d_list, (int)Wl,
+    e->run_dev(e->d_prof, n, e->d_spec, e->rec[0].ok, e->stream, false);
+    hipLaunchKernelGGL(svc_scatter, dim3((unsigned)((Wl + 255) / 256), n), dim3(256), 0, e->stream, e->d_spec, e->rec[0].ok, d_list, (int)Wl,
                        d_spec, d_ok);
     HIPCHK(hipGetLastError());
     wait_done();
@@ -182,10 +182,10 @@ void ChainService::run(const int *slots, int n, int nominal, int scat_flag, bool
       if (any_over) HIPCHK(hipMemcpyAsync(d_over_stage + 3 * (size_t)k, seg.over(s0), sizeof(double) * 3 * (size_t)cnt, hipMemcpyHostToDevice, e->stream));
     });
     if (any_over) e->prep_over_once = d_over_stage;
-    e->run_dev(e->d_prof, n, e->d_spec, e->d_ok, e->stream, false);
+    e->run_dev(e->d_prof, n, e->d_spec, e->rec[0].ok, e->stream, false);
     runs([&](int k, int s0, int cnt) {
       HIPCHK(hipMemcpyAsync(seg.spec(s0), e->d_spec + (size_t)k * Wl, sizeof(double) * (size_t)cnt * Wl, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(hipMemcpyAsync(seg.ok(s0), e->d_ok + k, (size_t)cnt, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(hipMemcpyAsync(seg.ok(s0), e->rec[0].ok + k, (size_t)cnt, hipMemcpyDeviceToHost, e->stream));
     });
     HIPCHK(hipStreamSynchronize(e->stream));
   }
