@@ -12,9 +12,14 @@ bartrt_cf_batch) and returns the band-averaged curves of any number of profiles:
     transmittance(date_dir, atmfile, filters)
                                        drop-in for cf.transmittance(..., plot=False)
 
+    posterior(output_npy, cfg, filters, burnin)
+                                       the curves of a whole MCMC posterior and their percentile envelopes
+                                       (the CF / transmittance panel of bestFit.callTransit's figure)
+
 The batched calls on an initialised engine are ``bart_amd.engine.contribution`` /
-``transmittance`` (host arrays) and ``contribution_dev`` / ``transmittance_dev`` (torch).
-Plots stay out of scope.
+``transmittance`` (host arrays; ``over=`` gives every walker its own radius, cloud top and
+scattering), ``contribution_dev`` / ``transmittance_dev`` (torch) and, from parameter vectors,
+``contribution_from_params`` / ``transmittance_from_params``.  Plots stay out of scope.
 """
 from __future__ import annotations
 
@@ -137,3 +142,125 @@ def transmittance(date_dir, atmfile, filters, fext=".png", plot=False, tcfg=None
     band-averaged exp(-tau) [nfilters, nlayers] in atm layer order (vertical depth on an eclipse engine,
     chord depth on a transit engine).  As cf() otherwise."""
     return _dropin(date_dir, atmfile, filters, plot, tcfg, "transmit")
+
+
+# ---- a whole posterior (code/bestFit.py:429-525) ---------------------------------------------
+# the 1- and 2-sigma levels of bestFit.py:461-465
+PERCENTILES = {"lo1": 15.87, "hi1": 84.13, "lo2": 2.28, "hi2": 97.72}
+
+
+def posterior_samples(output, params, stepsize, burnin, thinning=1, layout=None):
+    """The full parameter vectors of a posterior: ``output`` as MC3 writes output.npy, [nchains, nfree, niter]
+    (free parameters only), or as bart_amd.retrieve writes it, [nchains, nsteps, npars] (all parameters).  The
+    two are told apart by the parameter count against ``stepsize`` (nfree = its non-zero entries, npars = its
+    length); an array that fits both needs ``layout`` = 'mc3' or 'retrieve'.  The first ``burnin`` iterations of
+    every chain are dropped, every ``thinning``-th of the rest is kept, and the chains are stacked one after the
+    other (bestFit.py:436-438).  Free parameters are expanded to full ones as bestFit.callTransit does: entry i
+    comes from the sample where stepsize[i] != 0 and from ``params`` where it is 0 (bestFit.py:449-456).  A
+    negative stepsize (MC3's shared parameter) raises, as the sampler does.  -> [nsamples, npars]."""
+    from .sampler import _check_stepsize
+    stepsize = np.asarray(stepsize, np.double)
+    params = np.asarray(params, np.double)
+    _check_stepsize(stepsize)
+    if params.shape != stepsize.shape or params.ndim != 1:
+        raise ValueError("posterior: params (%d) and stepsize (%d) must be vectors of one length"
+                         % (params.size, stepsize.size))
+    data = np.asarray(output, np.double)
+    if data.ndim != 3:
+        raise ValueError("posterior: output.npy must be three-dimensional, not %s" % (data.shape,))
+    free = np.nonzero(stepsize != 0.0)[0]
+    npars, nfree = stepsize.size, free.size
+    is_mc3, is_own = data.shape[1] == nfree, data.shape[2] == npars
+    if layout is None:
+        if is_mc3 and is_own:
+            raise ValueError("posterior: an array of shape %s is both [nchains, nfree, niter] and [nchains, nsteps, "
+                             "npars] for %d free of %d parameters; say layout='mc3' or layout='retrieve'"
+                             % (data.shape, nfree, npars))
+        if not (is_mc3 or is_own):
+            raise ValueError("posterior: an array of shape %s is neither [nchains, nfree = %d, niter] nor [nchains, "
+                             "nsteps, npars = %d]" % (data.shape, nfree, npars))
+        layout = "mc3" if is_mc3 else "retrieve"
+    if layout not in ("mc3", "retrieve") or not {"mc3": is_mc3, "retrieve": is_own}[layout]:
+        raise ValueError("posterior: layout %r does not fit an array of shape %s" % (layout, data.shape))
+    burnin, thinning = int(burnin), int(thinning)
+    if burnin < 0 or thinning < 1:
+        raise ValueError("posterior: burnin >= 0 and thinning >= 1")
+    if layout == "mc3":
+        kept = data[:, :, burnin::thinning].transpose(0, 2, 1).reshape(-1, nfree)    # chain after chain
+        full = np.tile(params, (kept.shape[0], 1))
+        full[:, free] = kept
+    else:
+        full = data[:, burnin::thinning, :].reshape(-1, npars).copy()
+        full[:, stepsize == 0.0] = params[stepsize == 0.0]
+    if full.shape[0] == 0:
+        raise ValueError("posterior: no sample is left after a burn-in of %d iterations" % burnin)
+    return np.ascontiguousarray(full)
+
+
+def _mcmc_vectors(cfg):
+    """``params`` and ``stepsize`` of the [MCMC] section."""
+    import configparser
+    cp = configparser.ConfigParser()
+    cp.optionxform = str
+    if not cp.read([cfg]):
+        raise FileNotFoundError(cfg)
+    d = dict(cp.items("MCMC"))
+    for key in ("params", "stepsize"):
+        if not d.get(key):
+            raise ValueError("posterior: %s has no `%s` in its [MCMC] section" % (cfg, key))
+    return (np.array([float(x) for x in d["params"].split()]), np.array([float(x) for x in d["stepsize"].split()]))
+
+
+def _run_samples(cfg, samples, filters, kind, chunk):
+    """Worker, step and CF set up from the [MCMC] configuration as BARTfunc.Worker does; the samples in chunks.
+    -> (band [nsamples, nfilters, L], status [nsamples], kind)."""
+    from . import BARTfunc, engine
+    wcfg = BARTfunc.WorkerConfig.from_cfg(cfg)
+    if kind is None:
+        kind = "transmittance" if wcfg.solution == "transit" else "contribution"     # BART.py:637-644
+    if kind not in ("contribution", "transmittance"):
+        raise ValueError("posterior: kind is 'contribution' or 'transmittance'")
+    w = BARTfunc.Worker(wcfg, carry=False)
+    try:
+        win = filter_windows(w.specwn, list(filters if filters is not None else wcfg.filters))
+        bands, stats = [], []
+        for off in range(0, len(samples), chunk):
+            p = samples[off:off + chunk]
+            if kind == "contribution":
+                b, st = engine.contribution_from_params(p, win, normalize=False)
+            else:
+                b, st = engine.transmittance_from_params(p, win)
+            bands.append(b)
+            stats.append(st)
+        return np.concatenate(bands), np.concatenate(stats), kind
+    finally:
+        w.close()
+
+
+def posterior(output_npy, cfg, filters, burnin, thinning=1, kind=None, chunk=4096, layout=None):
+    """The band-averaged contribution functions or transmittance of every sample of an MCMC posterior, and their
+    envelopes: what bestFit.callTransit (code/bestFit.py:429-525) draws beside the T(p) envelopes, for the whole
+    posterior instead of the best fit.  ``output_npy``: the output.npy of MC3 or of bart_amd.retrieve (a path or the
+    array; posterior_samples); ``cfg``: the run's configuration, whose [MCMC] section gives ``params`` /
+    ``stepsize`` and everything BARTfunc.Worker reads; ``filters``: filter files (None: the cfg's).  ``kind``:
+    'contribution' or 'transmittance'; default contribution for eclipse / direct, transmittance for transit
+    (BART.py:637-644).  The engine is initialised on the cfg's ``tconfig`` and freed afterwards -- an engine this
+    process had is replaced.  Every sample runs under its own radius, cloud top and scattering where the cfg fits
+    them.  -> dict: ``samples`` [n, npars] (full parameters), ``band`` [n, nfilters, L] (atm layer order; NaN rows
+    for rejected samples), ``status`` [n] (0, 1 temperature, 2 abundance), ``kind``, and over the accepted samples
+    ``median``, ``lo1``, ``hi1``, ``lo2``, ``hi2`` [nfilters, L] (the 15.87 / 84.13 / 2.28 / 97.72 percentiles of
+    bestFit.py:461-465; NaN when no sample was accepted).  No plots."""
+    params, stepsize = _mcmc_vectors(cfg)
+    data = np.load(output_npy) if isinstance(output_npy, (str, bytes, os.PathLike)) else output_npy
+    samples = posterior_samples(data, params, stepsize, burnin, thinning, layout)
+    band, status, kind = _run_samples(cfg, samples, filters, kind, max(1, int(chunk)))
+    out = {"samples": samples, "band": band, "status": status, "kind": kind}
+    good = band[status == 0]
+    if len(good):
+        out["median"] = np.median(good, axis=0)
+        for k, q in PERCENTILES.items():
+            out[k] = np.percentile(good, q, axis=0)
+    else:
+        for k in ("median", *PERCENTILES):
+            out[k] = np.full(band.shape[1:], np.nan)
+    return out

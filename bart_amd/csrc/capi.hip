@@ -783,6 +783,65 @@ int bartrt_cf_batch_dev(const double *d_prof, int nwalkers, int kind, double *d_
   });
 }
 
+int bartrt_cf_batch_over(const double *prof, int nwalkers, int nprof, const double *over, int kind, double *band,
+                         double *full, unsigned char *ok) {
+  NEED_ENGINE();
+  Engine *e = g_eng;
+  if (int rc = cf_check_kind(e, kind, "cf_batch_over")) return rc;
+  if (!prof || !band || nwalkers < 0) return fail(BARTRT_EINVAL, "cf_batch_over: null buffer");
+  if (nprof != (e->S + 1) * e->L) return fail(BARTRT_EINVAL, "cf_batch_over: profile length must be (nspecies+1)*nlayers");
+  return guarded([&] {
+    cf_run_host(*e, prof, nwalkers, kind, band, full, ok, over);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_cf_batch_over_dev(const double *d_prof, int nwalkers, const double *d_over, int kind, double *d_band,
+                             double *d_full, unsigned char *d_ok, void *stream) {
+  NEED_ENGINE();
+  Engine *e = g_eng;
+  if (int rc = cf_check_kind(e, kind, "cf_batch_over_dev")) return rc;
+  if (!d_prof || !d_band || nwalkers < 0) return fail(BARTRT_EINVAL, "cf_batch_over_dev: null buffer");
+  return guarded([&] {
+    cf_run_dev(*e, d_prof, nwalkers, kind, d_band, d_full, d_ok, stream ? (hipStream_t)stream : e->stream, d_over);
+    return BARTRT_OK;
+  });
+}
+
+// the parameter front end: the engine limits of cf_batch, then the step's setup and parameter count
+static int cf_check_params(const Engine *e, int kind, int npars, const char *who) {
+  if (int rc = cf_unsupported(e, who)) return rc;
+  if (!e->step) return fail(BARTRT_EINVAL, std::string(who) + ": call bartrt_step_setup first");
+  if (int rc = cf_check_kind(e, kind, who)) return rc;
+  if (npars != step_npars(*e))
+    return fail(BARTRT_EINVAL, std::string(who) + ": npars must be nPT + (radius, cloud top, scattering parameters "
+                                                  "declared with step_set_extras) + nmolfit");
+  return BARTRT_OK;
+}
+
+int bartrt_cf_params(const double *params, int nwalkers, int npars, int kind, double *band, double *full, int *status) {
+  NEED_ENGINE();
+  Engine *e = g_eng;
+  if (int rc = cf_check_params(e, kind, npars, "cf_params")) return rc;
+  if (!params || !band || nwalkers < 0) return fail(BARTRT_EINVAL, "cf_params: null buffer");
+  return guarded([&] {
+    cf_params_host(*e, params, nwalkers, npars, kind, band, full, status);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_cf_params_dev(const double *d_params, int nwalkers, int npars, int kind, double *d_band, double *d_full,
+                         int *d_status, void *stream) {
+  NEED_ENGINE();
+  Engine *e = g_eng;
+  if (int rc = cf_check_params(e, kind, npars, "cf_params_dev")) return rc;
+  if (!d_params || !d_band || nwalkers < 0) return fail(BARTRT_EINVAL, "cf_params_dev: null buffer");
+  return guarded([&] {
+    cf_params_dev(*e, d_params, nwalkers, npars, kind, d_band, d_full, d_status, stream ? (hipStream_t)stream : e->stream);
+    return BARTRT_OK;
+  });
+}
+
 // ---- per-step converters (step.hip) ------------------------------------
 int bartrt_step_setup(const double *ptargs5, int tint_thorngren, int pttype,
                       double tmin, double tmax,

@@ -16,11 +16,16 @@
 //                     filter's weights h_i resp_i (h = 1/2 at the window's ends), two cross-lane butterflies add the
 //                     quarters, and one partial per (walker, tile, filter, layer) goes to a workspace.
 //  cf_finish          sums each filter's partials in tile order, divides by trapz(resp).
+// Posterior samples (bartrt_cf_batch_over, bartrt_cf_params): the layer records are prepared under each walker's own
+// reference radius, cloud top and Rayleigh value (PrepArgs::over, the per-step path's mechanism); from parameter
+// vectors the step's converter (step_convert_dev) writes profiles, statuses and those overrides into this module's
+// workspaces first.  The CF kernels themselves do not know: they read records, chord tables and deck layers.
 // Every sum has a fixed order and no atomics: the bits do not depend on the batch a walker is in.  Not part of the
 // per-step hot path: no kernel table, no run-time instantiation; molecule and CIA counts are run-time parameters.
 #include "contrib.hpp"
 #include "integ.hpp"
 #include "kernels.hpp"
+#include "step.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -205,6 +210,32 @@ __global__ __launch_bounds__(256) void cf_finish(const double *part, int nwalker
   band[((size_t)w * nf + f) * L + (L - 1 - k)] = ok[w] ? s / trapz[f] : __builtin_nan("");
 }
 
+// Per-walker settings as the caller states them (what bartrt_set_radius / _set_cloudtop take: km, log10 bar) -> as
+// prep_profiles reads them (cm, barye); NaN ("the engine's setting") stays NaN.  The device-buffer call's conversion:
+// 10^x is the device's pow here and the host's in the setters and in the host-buffer call (over_units below) -- the
+// two may differ in the last bit, which matters only to a cloud top that is a layer's pressure to the bit.
+__global__ __launch_bounds__(256) void cf_over_units(const double *in, double *out, int n3) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= n3) return;
+  const int c = t % 3;
+  const double v = in[t];
+  out[t] = c == 0 ? v * 1e5 : (c == 1 ? pow(10.0, v) * 1e6 : v);
+}
+
+// After the preparation: a sample the step's converter rejected (status, optional) and a walker whose own radius
+// (over, optional, prep_profiles' units) is not a positive finite number -- bartrt_set_radius refuses such a value --
+// are flagged like a profile the preparation cannot evaluate.
+__global__ __launch_bounds__(256) void cf_mask(const int *status, const double *over, unsigned char *ok, int n) {
+  const int w = blockIdx.x * 256 + threadIdx.x;
+  if (w >= n) return;
+  bool bad = status && status[w] != 0;
+  if (over) {
+    const double r = over[3 * (size_t)w];
+    bad = bad || (r == r && !(r > 0.0 && r < 1e300));
+  }
+  if (bad) ok[w] = 0;
+}
+
 }  // namespace
 
 // ---- host state of one engine (Engine::cf; made by cf_setup): the per-walker workspaces of one chunk of walkers ----
@@ -212,6 +243,11 @@ struct CfWork {
   int cap = 0;
   RecordSet rec;
   DevBuf<double> d_rtop, d_ds, d_part;
+  // per-walker overrides in prep_profiles' units [cap_over][3]; the parameter front end's profiles [cap_par][nprof]
+  // and statuses
+  int cap_over = 0, cap_par = 0;
+  DevBuf<double> d_over, d_prof;
+  DevBuf<int> d_status;
   DevBuf<char> d_stage;               // staging of the host-buffer call
   hipStream_t last_stream = nullptr;  // the workspaces' latest user
 };
@@ -230,11 +266,13 @@ size_t workspace_cap() {
   return c && *c ? std::max<size_t>(1, std::strtoull(c, nullptr, 10)) : (size_t)256 << 20;
 }
 
-size_t per_walker_bytes(const Engine &e) {
+size_t per_walker_bytes(const Engine &e, bool over = false, bool params = false) {
   const CfState &g = *e.cf;
   size_t b = sizeof(double) * (size_t)g.nent * e.L + sizeof(double) * (size_t)e.L * coef_stride(e.M, e.C) +
              sizeof(idx_t) * (size_t)e.L * idx_stride(e.C) + sizeof(int) + 1;
   if (e.solution == 1) b += sizeof(double) * ((size_t)e.L + chord_table_size(e.L));
+  if (over || params) b += sizeof(double) * 3;
+  if (params) b += sizeof(double) * (size_t)(e.S + 1) * e.L + sizeof(int);
   return b;
 }
 
@@ -244,17 +282,29 @@ void claim(CfState &g, hipStream_t st) {
   g.last_stream = st;
 }
 
-void ensure_cap(const Engine &e, int n) {
+void ensure_cap(const Engine &e, int n, bool over = false, bool params = false) {
   CfState &g = *e.cf;
-  if (n <= g.cap) return;
+  over = over || params;
+  if (n <= g.cap && (!over || n <= g.cap_over) && (!params || n <= g.cap_par)) return;
   HIPCHK(hipDeviceSynchronize());   // (an earlier launch on any stream may still use the old buffers)
-  g.rec.reserve((size_t)n, e.L, e.M, e.C);
-  g.d_part.reserve((size_t)n * g.nent * e.L);
-  if (e.solution == 1) {
-    g.d_rtop.reserve((size_t)n * e.L);
-    g.d_ds.reserve((size_t)n * chord_table_size(e.L));
+  if (n > g.cap) {
+    g.rec.reserve((size_t)n, e.L, e.M, e.C);
+    g.d_part.reserve((size_t)n * g.nent * e.L);
+    if (e.solution == 1) {
+      g.d_rtop.reserve((size_t)n * e.L);
+      g.d_ds.reserve((size_t)n * chord_table_size(e.L));
+    }
+    g.cap = n;
   }
-  g.cap = n;
+  if (over && n > g.cap_over) {
+    g.d_over.reserve((size_t)n * 3);
+    g.cap_over = n;
+  }
+  if (params && n > g.cap_par) {
+    g.d_prof.reserve((size_t)n * (e.S + 1) * e.L);
+    g.d_status.reserve((size_t)n);
+    g.cap_par = n;
+  }
 }
 
 void check_ready(const Engine &e, int kind) {
@@ -269,19 +319,27 @@ void allow_lds(K kernel, size_t bytes) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
 }
 
-// one chunk: m walkers whose flags go to okp
+// one chunk: m walkers whose flags go to okp.  d_over (optional): the walkers' overrides in prep_profiles' units,
+// their radii checked on the device if check_radius (the host-buffer call has checked them already);
+// d_status (optional): the converter's verdicts -- a rejected sample's flag is cleared
 void run_chunk(Engine &e, const double *d_prof, int m, int kind, double *d_band, double *d_full, unsigned char *okp,
-               hipStream_t st) {
+               hipStream_t st, const double *d_over = nullptr, const int *d_status = nullptr, bool check_radius = false) {
   const CfState &g = *e.cf;
   // the layer records under the engine's settings, as run_transit_batch builds them, into this module's buffers
-  // (no radii output, no per-walker overrides: the engine's own state is left as it was)
+  // (no radii output, only the caller's own per-walker overrides: the engine's own state is left as it was)
   PrepArgs pa = e.prep_args(d_prof, m, okp, g.rec);
   pa.rad_out = nullptr;
-  pa.over = nullptr;
+  pa.over = d_over;
   pa.rtop = e.solution == 1 ? g.d_rtop.get() : nullptr;
   pa.ds = e.solution == 1 ? g.d_ds.get() : nullptr;
   HIPCHK(launch_prep(pa, st));
+  // (transit: the radii the preparation wrote are the walker's own -- hydrostatic from ITS reference radius -- and so
+  // is the chord table filled from them)
   if (e.solution == 1) HIPCHK(launch_chord_table(pa, st));
+  if (d_status || (d_over && check_radius)) {
+    hipLaunchKernelGGL(cf_mask, dim3((m + 255) / 256), dim3(256), 0, st, d_status, check_radius ? d_over : nullptr, okp, m);
+    HIPCHK(hipGetLastError());
+  }
 
   CfArgs a{};
   a.L = e.L; a.M = e.M; a.C = e.C; a.W = e.W(); a.nwalkers = m; a.ntiles = g.ntiles; a.kind = kind; a.nent = g.nent;
@@ -389,58 +447,157 @@ void cf_setup(Engine &e, int nf, const int *idx0, const int *npts, const double 
 
 int cf_nfilters(const Engine &e) { return e.cf ? e.cf->nf : 0; }
 
+namespace {
+
+// the caller's overrides of walkers [0, m) (device, public units) -> g.d_over
+const double *convert_over(CfState &g, const double *d_over, int m, hipStream_t st) {
+  hipLaunchKernelGGL(cf_over_units, dim3((3 * m + 255) / 256), dim3(256), 0, st, d_over, g.d_over.get(), 3 * m);
+  HIPCHK(hipGetLastError());
+  return g.d_over;
+}
+
+int chunk_of(size_t n, size_t per) { return (int)std::max<size_t>(1, std::min<size_t>(n, workspace_cap() / per)); }
+
+}  // namespace
+
 void cf_run_dev(Engine &e, const double *d_prof, int n, int kind, double *d_band, double *d_full, unsigned char *d_ok,
-                hipStream_t st) {
+                hipStream_t st, const double *d_over) {
   check_ready(e, kind);
   if (n <= 0) return;
   CfState &g = *e.cf;
   const int nprof = (e.S + 1) * e.L;
-  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, workspace_cap() / per_walker_bytes(e)));
-  ensure_cap(e, chunk);
+  const int chunk = chunk_of((size_t)n, per_walker_bytes(e, d_over != nullptr));
+  ensure_cap(e, chunk, d_over != nullptr);
   claim(g, st);
   for (int off = 0; off < n; off += chunk) {
     const int m = std::min(chunk, n - off);
+    const double *ov = d_over ? convert_over(g, d_over + (size_t)3 * off, m, st) : nullptr;
     run_chunk(e, d_prof + (size_t)off * nprof, m, kind, d_band + (size_t)off * g.nf * e.L,
-              d_full ? d_full + (size_t)off * e.W() * e.L : nullptr, d_ok ? d_ok + off : g.rec.ok.get(), st);
+              d_full ? d_full + (size_t)off * e.W() * e.L : nullptr, d_ok ? d_ok + off : g.rec.ok.get(), st, ov, nullptr,
+              true);
   }
 }
 
-void cf_run_host(Engine &e, const double *prof, int n, int kind, double *band, double *full, unsigned char *ok) {
+void cf_params_dev(Engine &e, const double *d_params, int n, int npars, int kind, double *d_band, double *d_full,
+                   int *d_status, hipStream_t st) {
   check_ready(e, kind);
+  if (!e.step) throw std::invalid_argument("cf: call bartrt_step_setup first");
   if (n <= 0) return;
   CfState &g = *e.cf;
-  const int nprof = (e.S + 1) * e.L;
-  const size_t bprof = sizeof(double) * nprof, bband = sizeof(double) * (size_t)g.nf * e.L,
-               bfull = full ? sizeof(double) * (size_t)e.W() * e.L : 0;
-  // the staging buffers and the workspaces of a chunk share the cap
-  const size_t per = per_walker_bytes(e) + bprof + bband + bfull + 1;
-  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, workspace_cap() / per));
-  ensure_cap(e, chunk);
-  const size_t need = (size_t)chunk * (bprof + bband + bfull) + chunk;
+  const int chunk = chunk_of((size_t)n, per_walker_bytes(e, true, true));
+  ensure_cap(e, chunk, true, true);
+  claim(g, st);
+  for (int off = 0; off < n; off += chunk) {
+    const int m = std::min(chunk, n - off);
+    int *status = d_status ? d_status + off : g.d_status.get();
+    step_convert_dev(e, d_params + (size_t)off * npars, m, npars, g.d_prof, status, g.d_over, st);
+    run_chunk(e, g.d_prof, m, kind, d_band + (size_t)off * g.nf * e.L,
+              d_full ? d_full + (size_t)off * e.W() * e.L : nullptr, g.rec.ok, st, g.d_over, status, true);
+  }
+}
+
+namespace {
+
+// The host-buffer calls stage their rows chunk by chunk in one allocation: consecutive arrays of `chunk` rows each.
+// The staging buffers and the workspaces of a chunk share the cap.
+struct Staging {
+  char *base = nullptr;
+  size_t at = 0;
+  int chunk = 0;
+  template <class T> T *take(size_t bytes_per_row) {
+    T *p = reinterpret_cast<T *>(base + at);
+    at += (size_t)chunk * bytes_per_row;
+    return p;
+  }
+};
+
+Staging stage_for(Engine &e, int n, size_t row_bytes, bool over, bool params) {
+  CfState &g = *e.cf;
+  Staging s;
+  s.chunk = chunk_of((size_t)n, per_walker_bytes(e, over, params) + row_bytes);
+  ensure_cap(e, s.chunk, over, params);
+  const size_t need = (size_t)s.chunk * row_bytes;
   if (need > g.d_stage.count()) {
     HIPCHK(hipDeviceSynchronize());
     g.d_stage.reserve(need);
   }
+  claim(g, e.stream);
+  s.base = g.d_stage;
+  return s;
+}
+
+// the setters' own conversions (capi.hip), on the host: km -> cm, log10 bar -> barye; NaN stays NaN
+void over_units(const double *in, double *out, size_t n) {
+  for (size_t w = 0; w < n; w++) {
+    out[3 * w] = in[3 * w] * 1e5;
+    out[3 * w + 1] = std::pow(10.0, in[3 * w + 1]) * 1e6;
+    out[3 * w + 2] = in[3 * w + 2];
+  }
+}
+
+}  // namespace
+
+void cf_run_host(Engine &e, const double *prof, int n, int kind, double *band, double *full, unsigned char *ok,
+                 const double *over) {
+  check_ready(e, kind);
+  if (n <= 0) return;
+  if (over)
+    for (int w = 0; w < n; w++) {   // (as bartrt_set_radius)
+      const double r = over[3 * (size_t)w];
+      if (r == r && !(r > 0 && r < 1e295))
+        throw std::invalid_argument("cf: walker " + std::to_string(w) + "'s radius must be positive");
+    }
+  CfState &g = *e.cf;
+  const size_t nprof = (size_t)(e.S + 1) * e.L;
+  const size_t bprof = sizeof(double) * nprof, bband = sizeof(double) * (size_t)g.nf * e.L,
+               bfull = full ? sizeof(double) * (size_t)e.W() * e.L : 0;
+  Staging s = stage_for(e, n, bprof + bband + bfull + 1, over != nullptr, false);
+  double *dp = s.take<double>(bprof), *db = s.take<double>(bband), *df = full ? s.take<double>(bfull) : nullptr;
+  unsigned char *dok = s.take<unsigned char>(1);
   hipStream_t st = e.stream;
-  claim(g, st);
-  char *base = g.d_stage;
-  double *dp = reinterpret_cast<double *>(base);
-  double *db = reinterpret_cast<double *>(base + (size_t)chunk * bprof);
-  double *df = full ? reinterpret_cast<double *>(base + (size_t)chunk * (bprof + bband)) : nullptr;
-  unsigned char *dok = reinterpret_cast<unsigned char *>(base + (size_t)chunk * (bprof + bband + bfull));
-  std::vector<unsigned char> hok(chunk);
-  for (int off = 0; off < n; off += chunk) {
-    const int m = std::min(chunk, n - off);
+  std::vector<unsigned char> hok(s.chunk);
+  std::vector<double> hov(over ? (size_t)3 * s.chunk : 0);
+  for (int off = 0; off < n; off += s.chunk) {
+    const int m = std::min(s.chunk, n - off);
     HIPCHK(hipMemcpyAsync(dp, prof + (size_t)off * nprof, bprof * m, hipMemcpyHostToDevice, st));
-    run_chunk(e, dp, m, kind, db, df, dok, st);
+    if (over) {
+      // converted here with the setters' arithmetic, so a walker's deck is the layer the setter would give it
+      over_units(over + (size_t)3 * off, hov.data(), (size_t)m);
+      HIPCHK(hipMemcpyAsync(g.d_over, hov.data(), sizeof(double) * 3 * m, hipMemcpyHostToDevice, st));
+    }
+    run_chunk(e, dp, m, kind, db, df, dok, st, over ? g.d_over.get() : nullptr);
     HIPCHK(hipMemcpyAsync(band + (size_t)off * g.nf * e.L, db, bband * m, hipMemcpyDeviceToHost, st));
     if (full) HIPCHK(hipMemcpyAsync(full + (size_t)off * e.W() * e.L, df, bfull * m, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(hok.data(), dok, (size_t)m, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipStreamSynchronize(st));   // (hov and hok are free again)
     if (ok) std::copy(hok.begin(), hok.begin() + m, ok + off);
     else
       for (int w = 0; w < m; w++)
         if (!hok[w]) throw std::invalid_argument("cf: profile " + std::to_string(off + w) + " holds a non-finite or non-positive temperature");
+  }
+}
+
+void cf_params_host(Engine &e, const double *params, int n, int npars, int kind, double *band, double *full,
+                    int *status) {
+  check_ready(e, kind);
+  if (!e.step) throw std::invalid_argument("cf: call bartrt_step_setup first");
+  if (n <= 0) return;
+  CfState &g = *e.cf;
+  const size_t bpar = sizeof(double) * (size_t)npars, bband = sizeof(double) * (size_t)g.nf * e.L,
+               bfull = full ? sizeof(double) * (size_t)e.W() * e.L : 0;
+  Staging s = stage_for(e, n, bpar + bband + bfull + sizeof(int), true, true);
+  double *dp = s.take<double>(bpar), *db = s.take<double>(bband), *df = full ? s.take<double>(bfull) : nullptr;
+  int *dst = s.take<int>(sizeof(int));
+  hipStream_t st = e.stream;
+  for (int off = 0; off < n; off += s.chunk) {
+    const int m = std::min(s.chunk, n - off);
+    HIPCHK(hipMemcpyAsync(dp, params + (size_t)off * npars, bpar * m, hipMemcpyHostToDevice, st));
+    step_convert_dev(e, dp, m, npars, g.d_prof, dst, g.d_over, st);
+    run_chunk(e, g.d_prof, m, kind, db, df, g.rec.ok, st, g.d_over, dst, true);
+    HIPCHK(hipMemcpyAsync(band + (size_t)off * g.nf * e.L, db, bband * m, hipMemcpyDeviceToHost, st));
+    if (full) HIPCHK(hipMemcpyAsync(full + (size_t)off * e.W() * e.L, df, bfull * m, hipMemcpyDeviceToHost, st));
+    if (status) HIPCHK(hipMemcpyAsync(status + off, dst, sizeof(int) * m, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));   // (a rejected sample is reported, not an error)
   }
 }
 

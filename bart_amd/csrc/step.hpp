@@ -56,6 +56,14 @@ void step_ensure(Engine &e, int n);
 // params[n][npars] -> prof[n][(S+1)][L], status[n]
 void step_profiles_dev(Engine &e, const double *d_params, int n, int npars, double *d_prof,
                        int *d_status, hipStream_t st);
+// The same converter for the contribution-function front end (contrib.hip): params[n][npars] -> prof[n][(S+1)][L],
+// status[n] (0, 1 temperature, 2 abundance) and over[n][3], each walker's reference radius (cm), cloud-top pressure
+// (barye) and Rayleigh value as prep_profiles takes them (PrepArgs::over; NaN in a slot step_set_extras did not
+// declare).  Samples are independent: the carry-over of step_set_carry is not applied.  Touches no engine state (no
+// workspace of the step, no override request for the next preparation launch).
+void step_convert_dev(Engine &e, const double *d_params, int n, int npars, double *d_prof, int *d_status,
+                      double *d_over, hipStream_t st);
+int step_npars(const Engine &e);   // nPT + declared extras + nmolfit (step_setup done)
 // full-grid spectra [n][Wfull] -> bandflux[n][F]; may flip status to 3 (energy)
 // status_out (optional, device-accessible): final status per walker
 void step_bandflux_dev(Engine &e, const double *d_spec_full, int n, int *d_status,

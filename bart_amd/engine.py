@@ -513,66 +513,151 @@ def cf_setup(filters) -> int:
     return _cf_nfilters
 
 
-def _cf_batch(profiles, filters, kind, full, want_ok):
+def _cf_over(over, n):
+    """over [nwalkers, 3] = (radius km, log10 cloud-top bar, Rayleigh value) per walker, NaN = the engine-wide
+    setting (include/bartrt.h, bartrt_cf_batch_over) -> contiguous float64 [n, 3]."""
+    o = np.ascontiguousarray(over, np.double)
+    if o.shape != (n, 3):
+        raise ValueError("over must have shape (nwalkers, 3) = (%d, 3), not %s" % (n, o.shape))
+    return o
+
+
+def _cf_batch(profiles, filters, kind, full, want_ok, over=None):
     prof = np.ascontiguousarray(profiles, np.double).reshape(-1, nprof())
     nf = cf_setup(filters)
     n, L, W = prof.shape[0], nlayers(), trm.get_no_samples()
     band = np.zeros((n, nf, L))
     fout = np.zeros((n, W, L)) if full else None
     ok = np.zeros(n, np.uint8)
-    _check(trm.lib().bartrt_cf_batch(_ptr(prof), n, prof.shape[1], kind, _ptr(band),
-                                     _ptr(fout) if full else None, _ptr(ok) if want_ok else None))
+    if over is None:
+        _check(trm.lib().bartrt_cf_batch(_ptr(prof), n, prof.shape[1], kind, _ptr(band),
+                                         _ptr(fout) if full else None, _ptr(ok) if want_ok else None))
+    else:
+        _check(trm.lib().bartrt_cf_batch_over(_ptr(prof), n, prof.shape[1], _ptr(_cf_over(over, n)), kind, _ptr(band),
+                                              _ptr(fout) if full else None, _ptr(ok) if want_ok else None))
     return band, fout, ok
 
 
-def contribution(profiles, filters, normalize=True, full=False, want_ok=False):
+def contribution(profiles, filters, normalize=True, full=False, want_ok=False, over=None):
     """Band-averaged contribution functions of a batch (cf.cf's result per walker; eclipse geometry):
     profiles [nwalkers, (S+1)*L] as run_batch, filters as cf_setup ->
     filt_cf [nwalkers, nfilters, L] in atm layer order, then (normalize) filt_cf_norm of the same shape,
     then (full) the per-wavenumber values [nwalkers, W, L], then (want_ok) the walkers' flags -- without
     want_ok a non-finite profile raises; with it, that walker's rows are NaN.  A single array is returned
-    bare, several as a tuple."""
+    bare, several as a tuple.  ``over`` [nwalkers, 3]: every walker's own reference radius (km), log10 cloud-top
+    pressure (bar) and Rayleigh value, NaN = the engine-wide setting (bartrt_cf_batch_over)."""
     from .cf import normalize as _norm
-    band, fout, ok = _cf_batch(profiles, filters, CF_CONTRIB, full, want_ok)
+    band, fout, ok = _cf_batch(profiles, filters, CF_CONTRIB, full, want_ok, over)
     out = [band] + ([_norm(band)] if normalize else []) + ([fout] if full else []) + ([ok] if want_ok else [])
     return out[0] if len(out) == 1 else tuple(out)
 
 
-def transmittance(profiles, filters, full=False, want_ok=False):
+def transmittance(profiles, filters, full=False, want_ok=False, over=None):
     """Band-averaged transmittance exp(-tau) of a batch (cf.transmittance's result per walker; vertical depth
     on an eclipse engine, chord depth on a transit engine): [nwalkers, nfilters, L] in atm layer order,
-    then (full) [nwalkers, W, L], then (want_ok) the flags, as contribution()."""
-    band, fout, ok = _cf_batch(profiles, filters, CF_TRANSMIT, full, want_ok)
+    then (full) [nwalkers, W, L], then (want_ok) the flags, as contribution(); ``over`` as there."""
+    band, fout, ok = _cf_batch(profiles, filters, CF_TRANSMIT, full, want_ok, over)
     out = [band] + ([fout] if full else []) + ([ok] if want_ok else [])
     return out[0] if len(out) == 1 else tuple(out)
 
 
-def _cf_batch_dev(d_prof, kind, full, d_ok, stream):
+def _cf_dev_outputs(n, full, device):
+    import torch
+    if not _cf_nfilters:
+        raise trm.TransitError("the device forms of the contribution-function calls: call engine.cf_setup(filters) first")
+    band = torch.empty((n, _cf_nfilters, nlayers()), dtype=torch.float64, device=device)
+    fout = torch.empty((n, trm.get_no_samples(), nlayers()), dtype=torch.float64, device=device) if full else None
+    return band, fout
+
+
+def _cf_batch_dev(d_prof, kind, full, d_ok, stream, d_over=None):
     import torch
     assert d_prof.is_cuda and d_prof.dtype == torch.float64 and d_prof.is_contiguous()
-    n, L = d_prof.shape[0], nlayers()
-    if not _cf_nfilters:
-        raise trm.TransitError("contribution_dev / transmittance_dev: call engine.cf_setup(filters) first")
-    nf = _cf_nfilters
-    band = torch.empty((n, nf, L), dtype=torch.float64, device=d_prof.device)
-    fout = torch.empty((n, trm.get_no_samples(), L), dtype=torch.float64, device=d_prof.device) if full else None
+    n = d_prof.shape[0]
+    band, fout = _cf_dev_outputs(n, full, d_prof.device)
     if d_ok is not None:
         assert d_ok.is_cuda and d_ok.dtype == torch.uint8 and d_ok.numel() >= n
-    _check(trm.lib().bartrt_cf_batch_dev(
-        C.c_void_p(d_prof.data_ptr()), n, kind, C.c_void_p(band.data_ptr()),
-        C.c_void_p(fout.data_ptr()) if full else None, C.c_void_p(d_ok.data_ptr()) if d_ok is not None else None,
-        _stream_ptr(stream)))
+    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    if d_over is None:
+        _check(trm.lib().bartrt_cf_batch_dev(vp(d_prof), n, kind, vp(band), vp(fout), vp(d_ok), _stream_ptr(stream)))
+    else:
+        assert d_over.is_cuda and d_over.dtype == torch.float64 and d_over.is_contiguous() and tuple(d_over.shape) == (n, 3)
+        _check(trm.lib().bartrt_cf_batch_over_dev(vp(d_prof), n, vp(d_over), kind, vp(band), vp(fout), vp(d_ok),
+                                                  _stream_ptr(stream)))
     return (band, fout) if full else band
 
 
-def contribution_dev(d_prof, full=False, d_ok=None, stream=None):
+def contribution_dev(d_prof, full=False, d_ok=None, stream=None, over=None):
     """Device form of contribution() for the filters of the latest cf_setup: d_prof a float64 CUDA tensor
     [nwalkers, (S+1)*L] (run_batch_dev's input, e.g. from bartrt_step_profiles_dev) -> band tensor
     [nwalkers, nfilters, L] (atm layer order; not normalised), and [nwalkers, W, L] with ``full``.
-    Asynchronous on torch's current stream; d_ok (uint8 [nwalkers]) receives the flags (flagged rows: NaN)."""
-    return _cf_batch_dev(d_prof, CF_CONTRIB, full, d_ok, stream)
+    Asynchronous on torch's current stream; d_ok (uint8 [nwalkers]) receives the flags (flagged rows: NaN);
+    ``over``: a float64 CUDA tensor [nwalkers, 3] as contribution()'s."""
+    return _cf_batch_dev(d_prof, CF_CONTRIB, full, d_ok, stream, over)
 
 
-def transmittance_dev(d_prof, full=False, d_ok=None, stream=None):
+def transmittance_dev(d_prof, full=False, d_ok=None, stream=None, over=None):
     """Device form of transmittance(), as contribution_dev."""
-    return _cf_batch_dev(d_prof, CF_TRANSMIT, full, d_ok, stream)
+    return _cf_batch_dev(d_prof, CF_TRANSMIT, full, d_ok, stream, over)
+
+
+# ---- parameters in: a posterior's samples (include/bartrt.h, bartrt_cf_params) ----------------
+def _cf_params(params, filters, kind, full):
+    p = np.ascontiguousarray(params, np.double)
+    p = p.reshape(-1, p.shape[-1])
+    nf = cf_setup(filters)
+    n, L, W = p.shape[0], nlayers(), trm.get_no_samples()
+    band = np.zeros((n, nf, L))
+    fout = np.zeros((n, W, L)) if full else None
+    status = np.zeros(n, np.int32)
+    _check(trm.lib().bartrt_cf_params(_ptr(p), n, p.shape[1], kind, _ptr(band), _ptr(fout) if full else None,
+                                      _ptr(status)))
+    return band, fout, status
+
+
+def contribution_from_params(params, filters, normalize=True, full=False):
+    """Band-averaged contribution functions of parameter vectors [nwalkers, npars] as step_batch takes them (after
+    step_setup; eclipse geometry): T(p), abundances and the radius / cloud-top / Rayleigh slots declared with
+    step_set_extras are each sample's own.  -> (filt_cf [nwalkers, nfilters, L], then (normalize) filt_cf_norm, then
+    (full) [nwalkers, W, L], status [nwalkers]): status 0, 1 (temperature), 2 (abundance) as step_batch reports it; a
+    rejected sample's rows are NaN."""
+    from .cf import normalize as _norm
+    band, fout, status = _cf_params(params, filters, CF_CONTRIB, full)
+    if normalize:
+        # (filt_cf_norm of the accepted samples; a rejected sample's rows stay NaN without a warning)
+        norm = np.full_like(band, np.nan)
+        good = status == 0
+        if good.any():
+            norm[good] = _norm(band[good])
+    return tuple([band] + ([norm] if normalize else []) + ([fout] if full else []) + [status])
+
+
+def transmittance_from_params(params, filters, full=False):
+    """Band-averaged transmittance of parameter vectors, as contribution_from_params (any geometry):
+    -> (band [nwalkers, nfilters, L], then (full) [nwalkers, W, L], status)."""
+    band, fout, status = _cf_params(params, filters, CF_TRANSMIT, full)
+    return tuple([band] + ([fout] if full else []) + [status])
+
+
+def _cf_params_dev(d_params, kind, full, stream):
+    import torch
+    assert d_params.is_cuda and d_params.dtype == torch.float64 and d_params.is_contiguous() and d_params.dim() == 2
+    n, npars = d_params.shape
+    band, fout = _cf_dev_outputs(n, full, d_params.device)
+    status = torch.empty(n, dtype=torch.int32, device=d_params.device)
+    _check(trm.lib().bartrt_cf_params_dev(
+        C.c_void_p(d_params.data_ptr()), n, npars, kind, C.c_void_p(band.data_ptr()),
+        C.c_void_p(fout.data_ptr()) if full else None, C.c_void_p(status.data_ptr()), _stream_ptr(stream)))
+    return (band, fout, status) if full else (band, status)
+
+
+def contribution_from_params_dev(d_params, full=False, stream=None):
+    """Device form of contribution_from_params for the filters of the latest cf_setup: a float64 CUDA tensor
+    [nwalkers, npars] -> (band, status) tensors (band not normalised), (band, full, status) with ``full``.
+    Asynchronous on torch's current stream."""
+    return _cf_params_dev(d_params, CF_CONTRIB, full, stream)
+
+
+def transmittance_from_params_dev(d_params, full=False, stream=None):
+    """Device form of transmittance_from_params, as contribution_from_params_dev."""
+    return _cf_params_dev(d_params, CF_TRANSMIT, full, stream)

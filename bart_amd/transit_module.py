@@ -113,6 +113,10 @@ def lib():
         L.bartrt_cf_setup.argtypes = [i, p, p, p]
         L.bartrt_cf_batch.argtypes = [p, i, i, i, p, p, p]
         L.bartrt_cf_batch_dev.argtypes = [p, i, i, p, p, p, p]
+        L.bartrt_cf_batch_over.argtypes = [p, i, i, p, i, p, p, p]
+        L.bartrt_cf_batch_over_dev.argtypes = [p, i, p, i, p, p, p, p]
+        L.bartrt_cf_params.argtypes = [p, i, i, i, p, p, p]
+        L.bartrt_cf_params_dev.argtypes = [p, i, i, i, p, p, p, p]
         L.bartrt_algorithmic_bytes.argtypes = [i]
         L.bartrt_algorithmic_bytes.restype = d
         _lib = L

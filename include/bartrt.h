@@ -386,14 +386,49 @@ int bartrt_get_intensity_of(int walker, double *intens, int nangles, int nwave);
  * bartrt_cf_batch_dev: the same on device buffers, asynchronous on `stream` (NULL: the
  * engine's own); d_ok may be NULL.
  *
- * The engine-wide setters (radius, cloud top, scattering) apply as to run_transit_batch;
- * there are no per-walker radius / cloud / scattering parameters inside one batch.  A call
+ * The engine-wide setters (radius, cloud top, scattering) apply as to run_transit_batch.  A call
  * leaves the engine's other state alone: the profile behind bartrt_get_tau /
  * _get_intensity, a pending bartrt_prefetch_profiles_dev request, the timing and
  * walked-layer records, bartrt_get_radius.  Results are bit-identical from run to run and
  * do not depend on which other walkers share the call.  Internally the walkers go in chunks
  * whose workspace stays under BARTRT_CF_WORKSPACE_BYTES (default 256 MiB).
- * BARTRT_ENOTSUP: line-by-line engines, sharded engines (--shard), chain-service clients. */
+ * BARTRT_ENOTSUP: line-by-line engines, sharded engines (--shard), chain-service clients.
+ *
+ * bartrt_cf_batch_over / _over_dev: the same with every walker under its OWN settings -- a
+ * posterior's samples, whose radius, cloud top and scattering are fitted parameters
+ * (BARTfunc.py:350-360).  over[nwalkers][3] = {reference radius in km, log10(cloud-top pressure /
+ * bar), Rayleigh value}: what bartrt_set_radius, bartrt_set_cloudtop and
+ * bartrt_set_scattering(1, value) take.  NaN in a slot = the engine-wide setting for that walker
+ * (no cloud top where none is set); a cloud top above the top layer puts the deck on the top
+ * layer, as the setter does; the Rayleigh value acts under scattering flag 1 only (flag 2, the
+ * polarisability flavour, has no value).  A radius that is not a positive finite number: the host
+ * form refuses the call (BARTRT_EINVAL, as bartrt_set_radius does); the _dev form, which cannot
+ * look, flags that walker (ok[w] = 0, NaN band rows) and computes the others.  The host form
+ * converts the units on the host with the setters' own arithmetic: a walker gets exactly the deck
+ * layer the setter would give it.  The _dev form converts on the device, whose 10^x may differ
+ * from the host's in the last bit -- visible only for a cloud top that equals a layer's pressure to
+ * the bit.  A transit engine's chord depths are those of the walker's own hydrostatic
+ * radii.  over == NULL: bartrt_cf_batch's launches, arguments and bits.  The promises above hold:
+ * a walker's result depends on its profile and its three values only -- not on the other walkers
+ * or their settings, not on the chunking -- and nothing else of the engine changes.
+ *
+ * bartrt_cf_params / _params_dev: parameters in.  params[nwalkers][npars] as bartrt_step_batch
+ * takes them (after bartrt_step_setup and bartrt_cf_setup; BARTRT_EINVAL without either or with
+ * another npars) go through the step's own converter -- T(p) model, abundance scaling and
+ * renormalisation, bounds -- and the slots declared with bartrt_step_set_extras become the
+ * walker's overrides; then as bartrt_cf_batch_over.  The rows of an MC3 output, expanded to full
+ * parameter vectors, are this call's input (bart_amd.cf.posterior).
+ *   status[w]   0, 1 (temperature) or 2 (abundance), exactly what bartrt_step_batch reports for
+ *               the row; 3 (energy balance) is never raised: no spectrum is computed.  May be NULL.
+ *   rejected    a sample with status != 0 has NaN in its band rows (its rows of `full` are
+ *               undefined); it does not fail the call.
+ *   carry       bartrt_step_set_carry has no effect: samples are independent, a parameter set
+ *               the T(p) model rejects gets status 1.
+ *   scattering  with flag 2 the Rayleigh slot is present and unused, as in the step.
+ *   radius      a radius slot that is not a positive finite number leaves status as the step
+ *               reports it and NaN in the sample's band rows (the step converts the slots on the
+ *               device as well: cloud tops are the step's own, bit for bit).
+ * The engine limits and BARTRT_ENOTSUP cases of bartrt_cf_batch apply unchanged. */
 #define BARTRT_CF_CONTRIB  0
 #define BARTRT_CF_TRANSMIT 1
 int bartrt_cf_setup(int nfilters, const int *idx0, const int *npts, const double *resp);
@@ -401,6 +436,14 @@ int bartrt_cf_batch(const double *prof, int nwalkers, int nprof, int kind,
                     double *band, double *full, unsigned char *ok);
 int bartrt_cf_batch_dev(const double *d_prof, int nwalkers, int kind,
                         double *d_band, double *d_full, unsigned char *d_ok, void *stream);
+int bartrt_cf_batch_over(const double *prof, int nwalkers, int nprof, const double *over, int kind,
+                         double *band, double *full, unsigned char *ok);
+int bartrt_cf_batch_over_dev(const double *d_prof, int nwalkers, const double *d_over, int kind,
+                             double *d_band, double *d_full, unsigned char *d_ok, void *stream);
+int bartrt_cf_params(const double *params, int nwalkers, int npars, int kind,
+                     double *band, double *full, int *status);
+int bartrt_cf_params_dev(const double *d_params, int nwalkers, int npars, int kind,
+                         double *d_band, double *d_full, int *d_status, void *stream);
 
 /* Line-by-line engines only (cfg has `linedb`, no `opacityfile`): the Voigt
  * extinction of one profile, ext[nlayers][nwave_local] in cm-1, atm layer order. */
