@@ -634,6 +634,14 @@ int bartrt_voigt(const double *x, const double *y, double *k, long n) {
   });
 }
 
+int bartrt_expint_e2(const double *x, double *out, long n) {
+  if (n < 0 || (n > 0 && (!x || !out))) return fail(BARTRT_EINVAL, "bartrt_expint_e2: bad arguments");
+  return guarded([&] {
+    step_expint_e2_probe(x, out, n);
+    return BARTRT_OK;
+  });
+}
+
 int bartrt_timing_begin(void) { return bartrt_timing_begin_sampled(1); }
 
 int bartrt_timing_begin_sampled(int stride) {

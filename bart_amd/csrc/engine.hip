@@ -2,6 +2,8 @@
 // drives the kernels.  One engine per process (one process per GPU).
 #include "engine.hpp"
 #include "lbl.hpp"
+#include "lds.hpp"
+#include "prep.hpp"
 #include "contrib.hpp"
 #include "share.hpp"
 #include "step.hpp"
@@ -531,6 +533,12 @@ void Engine::upload_constants(const std::vector<double> &cia_planes, const std::
   if (M > kMaxMol) throw IoError{"more opacity-table molecules than the kernels are built for (16)"};
   for (int m = 0; m < M; m++) pa.opmol[m] = opmol[m];
   pa.ncia_temps = (int)cia_temp.size();
+  // the preparation keeps a walker's whole column in LDS (prep.hpp): what cannot fit is refused here, not at the first run
+  const size_t prep_lds = sizeof(double) * prep_lds_doubles(L, S, Nt, pa.ncia_temps);
+  if (prep_lds > kLdsMax)
+    throw IoError{"the column's preparation does not fit in LDS: L = " + std::to_string(L) + " layers and S = " +
+                  std::to_string(S) + " species need " + std::to_string(prep_lds) + " bytes of the " +
+                  std::to_string(kLdsMax) + " a workgroup has"};
   pa.iH2 = iH2; pa.iHe = iHe;
 
   RtArgs &r = rt;
@@ -714,6 +722,12 @@ struct Engine::Prefetch {
 Engine::Prefetch Engine::plan_prefetch(bool pf_ok, const double *d_prof_in, int n, const double *d_spec_out,
                                        const unsigned char *d_okp, hipStream_t st) {
   bool want_next = pf_ok && pf_req_prof && pf_req_n > 0;
+  // the RT launch that carries the next batch's preparation asks for the larger of the two jobs' LDS plus what its form
+  // adds (rt_eclipse.hpp, SpecLaunch: a double per layer in the 16-row forms, the 8.5 kB hand-off ring of
+  // rt_eclipse_split) and is not opted in above the 64 kB default (lds.hpp): on a column whose preparation needs that
+  // much the request is dropped, the named batch is prepared by its own call
+  const size_t pf_lds = sizeof(double) * prep_lds_doubles(L, S, Nt, prep.ncia_temps) + std::max<size_t>(9 * 1024, sizeof(double) * L);
+  if (want_next && pf_lds > kLdsDefault) want_next = false;
   if (want_next && pf_req_n > cap_walkers) {
     // the workspaces have to grow for the named batch: not under a call whose own buffers are the
     // engine's (a host-buffer batch: growing frees what it is about to read and write) -- such a

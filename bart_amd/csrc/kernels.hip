@@ -19,6 +19,7 @@
 // the transit geometry (transit_geom.hip) is where MFMA fits.
 #include "integ.hpp"
 #include "kernels.hpp"
+#include "lds.hpp"
 #include "prep.hpp"
 
 #include <cmath>
@@ -209,6 +210,9 @@ hipError_t launch_grid_transpose(const double *src, double *dst, long planes, in
 hipError_t launch_prep(const PrepArgs &a, hipStream_t st) {
   if (a.nwalkers <= 0) return hipSuccess;
   const size_t sh = sizeof(double) * prep_lds_doubles(a.L, a.S, a.Nt, a.ncia_temps);
+  // (deep columns with many species pass the 64 kB default; Engine::setup has refused what cannot fit at all)
+  static size_t allowed = kLdsDefault;
+  if (hipError_t e = allow_lds(prep_profiles, sh, allowed); e != hipSuccess) return e;
   // (256 lanes: two per layer in the record loop up to 128 layers, prep_body)
   hipLaunchKernelGGL(prep_profiles, dim3(a.nwalkers), dim3(256), sh, st, a);
   return hipGetLastError();

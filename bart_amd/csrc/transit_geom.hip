@@ -27,6 +27,7 @@
 // `toomuch` cut is a ballot over the 16 lanes of a row, and the sum over chords
 // a 16-lane reduction at the very end.
 #include "kernels.hpp"
+#include "lds.hpp"
 
 #include <cstdlib>
 
@@ -297,16 +298,6 @@ hipError_t launch_chord_table(const PrepArgs &a, hipStream_t st) {
   hipLaunchKernelGGL(chord_table_fill, dim3((a.L + 15) / 16, a.nwalkers), dim3(256), 0, st, a.L,
                      a.rtop, a.ds);
   return hipGetLastError();
-}
-
-// dynamic LDS above the 64 kB default has to be opted into, once per kernel
-template <class K>
-static hipError_t allow_lds(K kernel, size_t bytes, size_t &allowed) {
-  if (bytes <= allowed) return hipSuccess;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e == hipSuccess) allowed = bytes;
-  return e;
 }
 
 hipError_t launch_transit(const RtArgs &a, hipStream_t st, RtLaunchInfo *info) {

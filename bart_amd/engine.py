@@ -110,6 +110,15 @@ def voigt(x: np.ndarray, y: np.ndarray) -> np.ndarray:
     return k.reshape(x.shape)
 
 
+def expint_e2(x: np.ndarray) -> np.ndarray:
+    """E_2(x) as the "line" T(p) model's kernels evaluate it (diagnostics; no engine needed)."""
+    x = np.asarray(x, np.double)
+    xs = np.ascontiguousarray(x).ravel()
+    out = np.empty_like(xs)
+    _check(trm.lib().bartrt_expint_e2(_ptr(xs), _ptr(out), xs.size))
+    return out.reshape(x.shape)
+
+
 # ---- device-resident (torch tensors own the memory) ----------------------
 def _stream_ptr(stream=None):
     """The HIP stream the library is to enqueue on: torch's current stream.  torch's DEFAULT stream

@@ -454,6 +454,10 @@ int bartrt_get_lbl_extinction(const double *prof, int nprof, double *ext,
  * K(x, y) = Re w(x + i y) (x >= 0: distance from the line centre in Doppler widths
  * / sqrt(ln 2); y > 0: Lorentz / Doppler width ratio) on n host (x, y) pairs. */
 int bartrt_voigt(const double *x, const double *y, double *k, long n);
+/* Diagnostics, no engine needed: the exponential integral E_2(x) as the "line" T(p)
+ * model's kernels evaluate it (csrc/step.hip, expint_e2) on n host values:
+ * x >= 0; 1.0 at 0, 0.0 beyond 709.78 and at +inf, NaN for NaN. */
+int bartrt_expint_e2(const double *x, double *out, long n);
 
 /* HIP-event timing of the RT kernel launches (bench.py's roofline leg).
  * begin resets; end returns accumulated device ms and launch count. */
