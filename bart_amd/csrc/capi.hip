@@ -345,8 +345,8 @@ int bartrt_get_share(int *shared, int *owner) {
 int bartrt_prefetch_profiles_dev(const double *d_prof_next, int nwalkers) {
   NEED_ENGINE();
   if (nwalkers < 0 || (nwalkers > 0 && !d_prof_next)) return fail(BARTRT_EINVAL, "prefetch_profiles_dev: null buffer");
-  g_eng->pf_req_prof = nwalkers > 0 ? d_prof_next : nullptr;
-  g_eng->pf_req_n = nwalkers;
+  g_eng->pending.next_prof = nwalkers > 0 ? d_prof_next : nullptr;
+  g_eng->pending.next_n = nwalkers;
   return BARTRT_OK;
 }
 
@@ -422,9 +422,6 @@ int bartrt_get_pressure(double *out, int n) {
   return BARTRT_OK;
 }
 
-// host-buffer calls up to this size skip the staging copies (see below)
-static constexpr size_t kZeroCopyBytes = 512 * 1024;
-
 // trm.run_transit of a chain-service client: the profile goes into this process's slot, the dispatcher of the
 // owning process launches it together with the other workers' (svc_core.hpp); a batch from ONE client is posted
 // profile by profile (the batched callers own their engine: bart_amd.engine initialises with --no-service)
@@ -454,46 +451,8 @@ int bartrt_run_transit_batch(const double *prof, int nwalkers, int nprof,
   const int Wl = e->W();
   if (nwave != Wl && nwave != e->Wfull)
     return fail(BARTRT_EINVAL, "run_transit: nwave must equal get_no_samples() (or the shard size)");
-  if (nwalkers == 0) return BARTRT_OK;
   return guarded([&] {
-    e->ensure_walkers(nwalkers);
-    const size_t pb = sizeof(double) * (size_t)nwalkers * nprof;
-    const size_t sb = sizeof(double) * (size_t)nwalkers * Wl;
-    e->ensure_pin(pb + sb + nwalkers);
-    std::memcpy(e->h_pin, prof, pb);
-    double *hs = e->h_pin + (size_t)nwalkers * nprof;
-    unsigned char *hok = reinterpret_cast<unsigned char *>(hs + (size_t)nwalkers * Wl);
-    if (pb + sb <= kZeroCopyBytes) {
-      // a walker or a few: the kernels read the profiles from, and write the
-      // spectra to, the pinned host buffer themselves (three copy operations
-      // cost more than the kernels at this size)
-      void *dev = nullptr;
-      HIPCHK(hipHostGetDevicePointer(&dev, e->h_pin, 0));
-      double *dp = static_cast<double *>(dev);
-      e->run_dev(dp, nwalkers, dp + (size_t)nwalkers * nprof,
-                 reinterpret_cast<unsigned char *>(dp + (size_t)nwalkers * nprof + (size_t)nwalkers * Wl),
-                 e->stream, false);
-      e->last_prof = dp;   // stays valid until the next host-buffer call
-      e->last_n = nwalkers;
-    } else {
-      e->last_prof = e->d_prof;
-      e->last_n = nwalkers;
-      HIPCHK(hipMemcpyAsync(e->d_prof, e->h_pin, pb, hipMemcpyHostToDevice, e->stream));
-      e->run_dev(e->d_prof, nwalkers, e->d_spec, e->rec[0].ok, e->stream, false);
-      HIPCHK(hipMemcpyAsync(hs, e->d_spec, sb, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(hipMemcpyAsync(hok, e->rec[0].ok, nwalkers, hipMemcpyDeviceToHost, e->stream));
-    }
-    e->wait(e->stream);
-    const size_t off = nwave == Wl ? 0 : (size_t)e->lo;
-    for (int w = 0; w < nwalkers; w++)
-      std::memcpy(spec + (size_t)w * nwave + off, hs + (size_t)w * Wl, sizeof(double) * Wl);
-    if (ok) {
-      std::memcpy(ok, hok, nwalkers);
-    } else {
-      // no flag array to report through (the reference-shaped single call): refuse loudly
-      for (int w = 0; w < nwalkers; w++)
-        if (!hok[w]) throw std::invalid_argument("run_transit: the profile holds a non-finite or non-positive temperature");
-    }
+    e->run_host(prof, nwalkers, nprof, spec, nwave, ok);
     return BARTRT_OK;
   });
 }
@@ -510,9 +469,8 @@ int bartrt_run_transit_batch_dev(const double *d_prof, int nwalkers, double *d_s
     hipStream_t st = stream ? (hipStream_t)stream : g_eng->stream;
     // device-buffer calls keep no profile: the optical-depth / intensity getters must not fall
     // back on an older host-buffer call's
-    g_eng->last_prof = nullptr;
-    g_eng->last_n = 0;
-    g_eng->run_dev(d_prof, nwalkers, d_spec, d_ok, st, false);
+    g_eng->forget_profiles();
+    g_eng->run(RunRequest(d_prof, nwalkers, d_spec, d_ok, st));
     return BARTRT_OK;
   });
 }
@@ -534,7 +492,9 @@ int bartrt_get_tau_of(int walker, double *tau, int *last, int nwave, int nlayers
     return fail(BARTRT_EINVAL, "get_tau: shape must be [local samples][nlayers]");
   return guarded([&] {
     // re-run that profile of the latest host-buffer call with the optical-depth output enabled
-    e->run_dev(latest_profile(e, walker, "get_tau"), 1, e->d_spec, e->rec[0].ok, e->stream, true);
+    RunRequest rq(latest_profile(e, walker, "get_tau"), 1, e->d_spec, e->rec[0].ok, e->stream);
+    rq.want_tau = true;
+    e->run(rq);
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipMemcpy(tau, e->d_tau, sizeof(double) * (size_t)nwave * nlayers, hipMemcpyDeviceToHost));
     if (last) HIPCHK(hipMemcpy(last, e->d_last, sizeof(int) * (size_t)nwave, hipMemcpyDeviceToHost));
@@ -598,12 +558,9 @@ int bartrt_get_intensity_of(int walker, double *intens, int nangles, int nwave) 
   if (e->solution != 0) return fail(BARTRT_EINVAL, "get_intensity: eclipse geometry only");
   if (!intens || nangles != e->A || nwave != e->W()) return fail(BARTRT_EINVAL, "get_intensity: bad shape");
   return guarded([&] {
-    const double *prof = latest_profile(e, walker, "get_intensity");
-    e->want_intens = true;
-    try {
-      e->run_dev(prof, 1, e->d_spec, e->rec[0].ok, e->stream, false);
-    } catch (...) { e->want_intens = false; throw; }
-    e->want_intens = false;
+    RunRequest rq(latest_profile(e, walker, "get_intensity"), 1, e->d_spec, e->rec[0].ok, e->stream);
+    rq.want_intens = true;
+    e->run(rq);
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipMemcpy(intens, e->d_intens, sizeof(double) * (size_t)nangles * nwave, hipMemcpyDeviceToHost));
     return BARTRT_OK;

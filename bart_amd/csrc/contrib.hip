@@ -327,7 +327,7 @@ void run_chunk(Engine &e, const double *d_prof, int m, int kind, double *d_band,
   const CfState &g = *e.cf;
   // the layer records under the engine's settings, as run_transit_batch builds them, into this module's buffers
   // (no radii output, only the caller's own per-walker overrides: the engine's own state is left as it was)
-  PrepArgs pa = e.prep_args(d_prof, m, okp, g.rec);
+  PrepArgs pa = e.prep_args(RunRequest(d_prof, m, nullptr, okp, st), g.rec);
   pa.rad_out = nullptr;
   pa.over = d_over;
   pa.rtop = e.solution == 1 ? g.d_rtop.get() : nullptr;

@@ -14,6 +14,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <stdexcept>
 
 #include <sys/stat.h>
 #include <unistd.h>
@@ -585,11 +586,10 @@ void Engine::start_workspaces() {
       for (int k = 0; k < S; k++) hp[(size_t)w * nprof + (size_t)(k + 1) * L + l] = atm.abund[(size_t)l * S + k];
     }
   HIPCHK(hipMemcpy(d_prof, hp.data(), sizeof(double) * hp.size(), hipMemcpyHostToDevice));
-  run_dev(d_prof, 1, d_spec, rec[0].ok, stream, false);
-  run_dev(d_prof, nw, d_spec, rec[0].ok, stream, false);
+  run(RunRequest(d_prof, 1, d_spec, rec[0].ok, stream));
+  run(RunRequest(d_prof, nw, d_spec, rec[0].ok, stream));
   HIPCHK(hipStreamSynchronize(stream));
-  last_prof = nullptr;
-  last_n = 0;
+  forget_profiles();
 }
 
 void Engine::setup(const TCfg &cfg_in, int shard_rank, int shard_n) {
@@ -612,8 +612,8 @@ void Engine::ensure_walkers(int n) {
   if (n <= cap_walkers) return;
   int cap = std::max(n, cap_walkers * 2);
   HIPCHK(hipDeviceSynchronize());
-  if (last_prof == d_prof) last_prof = nullptr;
-  pf_have_prof = nullptr;   // (prefetched records, if any, are dropped with their buffers' sizes)
+  if (last_prof == d_prof) forget_profiles();
+  pf_have_prof = nullptr;  // (prefetched records, if any, are dropped with their buffers' sizes)
   if (cap2) {
     rec[1].reserve((size_t)cap, L, M, C);
     cap2 = cap;
@@ -654,35 +654,50 @@ void Engine::wait(hipStream_t st) {
 void Engine::ensure_pin(size_t bytes) {
   const size_t n = (bytes + sizeof(double) - 1) / sizeof(double);
   if (n <= h_pin.count()) return;
-  last_prof = nullptr;
+  forget_profiles();
   h_pin.reserve(n);
 }
 
-// [n] walkers in chunks of `chunk`.  The walkers' one-shot radius / cloud / scattering overrides are [n][3]:
-// every chunk gets its own rows (run_chunk consumes the pointer it is given, so it is re-armed per chunk).
+// The walkers of rq in chunks of `chunk`: every chunk is a request of its own rows -- profiles, spectra, flags and
+// overrides ([n][3]) -- and the first carries the prefetch request.
 // with_ext: the chunk's line-by-line extinction first ([walkers][L][W], lbl_extinction), for run_chunk to read.
-void Engine::run_chunks(const double *d_prof_in, int n, int chunk, double *d_spec_out, unsigned char *d_okp,
-                        hipStream_t st, bool want_tau, bool with_ext) {
+void Engine::run_chunks(const RunRequest &rq, int chunk, bool with_ext) {
   const int nprof = (S + 1) * L;
-  const double *over = prep_over_once;
-  for (int off = 0; off < n; off += chunk) {
-    const int m = std::min(chunk, n - off);
-    if (with_ext) lbl_extinction(*this, d_prof_in + (size_t)off * nprof, m, st);
-    prep_over_once = over ? over + (size_t)3 * off : nullptr;
-    run_chunk(d_prof_in + (size_t)off * nprof, m, d_spec_out + (size_t)off * W(),
-              (d_okp ? d_okp : rec[0].ok.get()) + off, st, want_tau, with_ext ? lbl->d_ext.get() : nullptr);
+  RunRequest c = rq;
+  if (!c.ok) c.ok = rec[0].ok;
+  for (int off = 0; off < rq.n; off += chunk) {
+    c.n = std::min(chunk, rq.n - off);
+    if (with_ext) {
+      lbl_extinction(*this, c.prof, c.n, c.stream);
+      c.d_ext = lbl->d_ext;
+    }
+    run_chunk(c);
+    c.prof += (size_t)c.n * nprof;
+    c.spec += (size_t)c.n * W();
+    c.ok += c.n;
+    if (c.over) c.over += (size_t)3 * c.n;
+    c.next_prof = nullptr;
+    c.next_n = 0;
   }
-  prep_over_once = nullptr;
 }
 
-void Engine::run_dev(const double *d_prof_in, int n, double *d_spec_out,
-                     unsigned char *d_okp, hipStream_t st, bool want_tau) {
-  if (n <= 0) return;
+void Engine::run(const RunRequest &asked) {
+  if (asked.n <= 0) return;
+  // what earlier calls left for this one moves into the request here and nowhere else, before anything can throw
+  // (a request with overrides or a preparation of its own -- the chain service, the fused step -- keeps those)
+  RunRequest rq = asked;
+  const Pending left = pending;
+  pending = Pending{};
+  if (!rq.over && !rq.prep_hook) { rq.over = left.over; rq.over_cloud = left.over_cloud; }
+  rq.next_prof = left.next_prof;
+  rq.next_n = left.next_n;
+  const int n = rq.n;
   // per-walker workspaces (records, flags) are sized by cap_walkers; the caller's profiles and spectra are used in place
-  if (n > cap_walkers && d_prof_in != d_prof) ensure_walkers(n);
-  if (lbl && solution == 0 && !want_tau && !want_intens && !lbl_eager && integ == 0 && !cut_slant) {
+  if (n > cap_walkers && rq.prof != d_prof) ensure_walkers(n);
+  if (lbl && solution == 0 && !rq.want_tau && !rq.want_intens && !lbl_eager && integ == 0 && !cut_slant) {
     // lazy fused path: layers' line sums are evaluated only as deep as the optical depth requires
-    run_chunk(d_prof_in, n, d_spec_out, d_okp, st, false, nullptr, true);
+    rq.lbl_fused = true;
+    run_chunk(rq);
     return;
   }
   if (lbl) {
@@ -691,13 +706,13 @@ void Engine::run_dev(const double *d_prof_in, int n, double *d_spec_out,
     size_t cap_bytes = (size_t)2 << 30;
     if (const char *c = std::getenv("BARTRT_LBL_CHUNK_BYTES")) cap_bytes = std::max<size_t>(1, std::strtoull(c, nullptr, 10));
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, cap_bytes / per));
-    run_chunks(d_prof_in, n, chunk, d_spec_out, d_okp, st, want_tau, true);
+    run_chunks(rq, chunk, true);
     return;
   }
   // `cut slant`, rule 1: the single-wave kernels keep an event log of 100 bytes per (walker, wavenumber) lane
   // (RtArgs::slog) -- 1 MB per walker at W = 1e4.  A batch whose log would pass BARTRT_SLOG_CAP_BYTES (1 GiB) goes
   // out in chunks of walkers (results are per walker: the same bits either way).
-  if (cut_slant && integ == 1 && solution == 0 && !prep_hook) {   // (the fused per-step launch addresses its batch whole)
+  if (cut_slant && integ == 1 && solution == 0 && !rq.prep_hook) {   // (the fused per-step launch addresses its batch whole)
     static const size_t cap = [] {
       const char *c = std::getenv("BARTRT_SLOG_CAP_BYTES");
       return c && *c ? std::max<size_t>(1, std::strtoull(c, nullptr, 10)) : (size_t)1 << 30;
@@ -705,41 +720,81 @@ void Engine::run_dev(const double *d_prof_in, int n, double *d_spec_out,
     const size_t per = std::max<size_t>(1, slant_log_bytes(1, (W() + 63) / 64, 64, A));
     const int chunk = (int)std::max<size_t>(1, cap / per);
     if (n > chunk) {
-      run_chunks(d_prof_in, n, chunk, d_spec_out, d_okp, st, want_tau, false);
+      run_chunks(rq, chunk, false);
       return;
     }
   }
-  run_chunk(d_prof_in, n, d_spec_out, d_okp, st, want_tau, nullptr);
+  run_chunk(rq);
+}
+
+// host-buffer calls up to this size skip the staging copies (run_host)
+static constexpr size_t kZeroCopyBytes = 512 * 1024;
+
+void Engine::run_host(const double *prof, int n, int nprof, double *spec, int nwave, unsigned char *ok) {
+  if (n <= 0) return;
+  const int Wl = W();
+  ensure_walkers(n);
+  const size_t pb = sizeof(double) * (size_t)n * nprof;
+  const size_t sb = sizeof(double) * (size_t)n * Wl;
+  ensure_pin(pb + sb + n);
+  std::memcpy(h_pin, prof, pb);
+  double *hs = h_pin + (size_t)n * nprof;
+  unsigned char *hok = reinterpret_cast<unsigned char *>(hs + (size_t)n * Wl);
+  if (pb + sb <= kZeroCopyBytes) {
+    // a walker or a few: the kernels read the profiles from, and write the spectra to, the pinned host buffer
+    // themselves (three copy operations cost more than the kernels at this size)
+    void *dev = nullptr;
+    HIPCHK(hipHostGetDevicePointer(&dev, h_pin, 0));
+    double *dp = static_cast<double *>(dev), *ds = dp + (size_t)n * nprof;
+    run(RunRequest(dp, n, ds, reinterpret_cast<unsigned char *>(ds + (size_t)n * Wl), stream));
+    remember_profiles(dp, n);   // stays valid until the next host-buffer call
+  } else {
+    remember_profiles(d_prof, n);
+    HIPCHK(hipMemcpyAsync(d_prof, h_pin, pb, hipMemcpyHostToDevice, stream));
+    run(RunRequest(d_prof, n, d_spec, rec[0].ok, stream));
+    HIPCHK(hipMemcpyAsync(hs, d_spec, sb, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(hok, rec[0].ok, n, hipMemcpyDeviceToHost, stream));
+  }
+  wait(stream);
+  const size_t off = nwave == Wl ? 0 : (size_t)lo;
+  for (int w = 0; w < n; w++) std::memcpy(spec + (size_t)w * nwave + off, hs + (size_t)w * Wl, sizeof(double) * Wl);
+  if (ok) {
+    std::memcpy(ok, hok, n);
+  } else {
+    // no flag array to report through (the reference-shaped single call): refuse loudly
+    for (int w = 0; w < n; w++)
+      if (!hok[w]) throw std::invalid_argument("run_transit: the profile holds a non-finite or non-positive temperature");
+  }
 }
 
 // The prefetch decision of one run_chunk call (prefetched preparation, engine.hpp)
 struct Engine::Prefetch {
-  bool have, want_next;  // the records were prepared by the previous call's RT launch; this one's prepares pf_req_*
+  bool have, want_next;  // the records were prepared by the previous call's RT launch; this one's prepares rq.next_*
   int bset;         // the record set this call's RT kernel reads (the other one takes the next batch's)
   PrepSettings now; // the settings the layer records are built from, as they stand for THIS call
 };
 
-Engine::Prefetch Engine::plan_prefetch(bool pf_ok, const double *d_prof_in, int n, const double *d_spec_out,
-                                       const unsigned char *d_okp, hipStream_t st) {
-  bool want_next = pf_ok && pf_req_prof && pf_req_n > 0;
+Engine::Prefetch Engine::plan_prefetch(bool pf_ok, const RunRequest &rq) {
+  bool want_next = pf_ok && rq.next_prof && rq.next_n > 0;
   // the RT launch that carries the next batch's preparation asks for the larger of the two jobs' LDS plus what its form
   // adds (rt_eclipse.hpp, SpecLaunch: a double per layer in the 16-row forms, the 8.5 kB hand-off ring of
   // rt_eclipse_split) and is not opted in above the 64 kB default (lds.hpp): on a column whose preparation needs that
   // much the request is dropped, the named batch is prepared by its own call
   const size_t pf_lds = sizeof(double) * prep_lds_doubles(L, S, Nt, prep.ncia_temps) + std::max<size_t>(9 * 1024, sizeof(double) * L);
   if (want_next && pf_lds > kLdsDefault) want_next = false;
-  if (want_next && pf_req_n > cap_walkers) {
+  if (want_next && rq.next_n > cap_walkers) {
     // the workspaces have to grow for the named batch: not under a call whose own buffers are the
     // engine's (a host-buffer batch: growing frees what it is about to read and write) -- such a
     // request is dropped, the named batch is prepared by its own call
-    const bool own = d_prof_in == d_prof || d_spec_out == d_spec || d_okp == rec[0].ok;
+    const bool own = rq.prof == d_prof || rq.spec == d_spec || rq.ok == rec[0].ok;
     if (own) want_next = false;
-    else ensure_walkers(pf_req_n);   // (drops prefetched records)
+    else ensure_walkers(rq.next_n);   // (drops prefetched records)
   }
   // records prefetched under other settings (a bartrt_set_radius / _cloudtop / _scattering in between) or on
   // another stream are not used -- the call prepares its own
-  const PrepSettings now{refradius, gsurf, cloudtop, scat_value, cloud_rup, cloud_rdown, cloud_ext, has_cloud, scat_flag};
-  const bool have = pf_ok && pf_have_prof && pf_have_prof == d_prof_in && pf_have_n == n && pf_have_stream == st &&
+  const PrepSettings now{refradius, gsurf, cloudtop, scat_value, cloud_rup, cloud_rdown, cloud_ext, has_cloud,
+                         rq.scat_flag >= 0 ? rq.scat_flag : scat_flag};
+  const bool have = pf_ok && pf_have_prof && pf_have_prof == rq.prof && pf_have_n == rq.n && pf_have_stream == rq.stream &&
                     pf_have_set == now;
   const int bset = have ? pf_have_buf : 0;
   pf_have_prof = nullptr;
@@ -747,19 +802,20 @@ Engine::Prefetch Engine::plan_prefetch(bool pf_ok, const double *d_prof_in, int 
   return Prefetch{have, want_next, bset, now};
 }
 
-// PrepArgs of one call: the engine's settings as they stand, the records into set `records`
-PrepArgs Engine::prep_args(const double *d_prof_in, int n, unsigned char *d_okp, const RecordSet &records) {
+// PrepArgs of one call: the engine's settings as they stand (the request's scattering flag, if it has one), the
+// request's overrides, the records into set `records`
+PrepArgs Engine::prep_args(const RunRequest &rq, const RecordSet &records) {
   PrepArgs pa = prep;
-  pa.nwalkers = n;
-  pa.prof = d_prof_in;
+  pa.nwalkers = rq.n;
+  pa.prof = rq.prof;
   pa.gsurf = gsurf; pa.refradius = refradius;
-  pa.scat_flag = scat_flag; pa.scat_value = scat_value;
+  pa.scat_flag = rq.scat_flag >= 0 ? rq.scat_flag : scat_flag; pa.scat_value = scat_value;
   pa.has_cloud = has_cloud; pa.cloudtop = cloudtop;
   pa.cloud_rup = cloud_rup; pa.cloud_rdown = cloud_rdown; pa.cloud_ext = cloud_ext;
   pa.coef = records.coef; pa.idx = records.idx; pa.kstop = records.kstop;
-  pa.ok = d_okp ? d_okp : rec[0].ok.get();
+  pa.ok = rq.ok ? rq.ok : rec[0].ok.get();
   pa.rad_out = d_rad;
-  pa.over = prep_over_once;
+  pa.over = rq.over;
   pa.rtop = solution == 1 ? d_rtop.get() : nullptr;
   pa.ds = solution == 1 ? d_ds.get() : nullptr;
   return pa;
@@ -774,46 +830,46 @@ static int rt_block() {
 }
 
 // RtArgs of one call.  Not a getter: it grows d_intens / d_slog / d_walked when the call needs them (d_slog after a
-// device synchronisation), clears d_walked on st and, when timed, makes the events and records the fused path's first
-RtArgs Engine::rt_args(const PrepArgs &pa, const Prefetch &pf, double *d_spec_out, bool want_tau, const double *d_ext,
-                       bool lbl_fused, bool over_cloud, bool timed, hipStream_t st) {
-  const int n = pa.nwalkers, block = rt_block();
+// device synchronisation), clears d_walked on the stream and, when timed, makes the events and records the fused
+// path's first.  eclipse_rt: the launch is launch_rt's (run_chunk)
+RtArgs Engine::rt_args(const RunRequest &rq, const PrepArgs &pa, const Prefetch &pf, bool eclipse_rt, bool timed) {
+  const int n = rq.n, block = rt_block();
   RtArgs r = rt;
   r.nwalkers = n;
-  r.nsel = sel_walkers > n ? sel_walkers : 0;
+  r.nsel = rq.sel_walkers > n ? rq.sel_walkers : 0;
   if (kernel_by_local) r.Wfull = r.W;
   r.coef = pa.coef; r.idx = pa.idx; r.kstop = pa.kstop;
-  r.ext = d_ext;
+  r.ext = rq.d_ext;
   r.nprep = 0;
   if (pf.want_next) {
     const RecordSet &next = rec[1 - pf.bset];
     PrepArgs pn = pa;      // same engine settings; the next batch's profiles into the other buffer set
-    pn.nwalkers = pf_req_n;
-    pn.prof = pf_req_prof;
+    pn.nwalkers = rq.next_n;
+    pn.prof = rq.next_prof;
     pn.coef = next.coef; pn.idx = next.idx; pn.kstop = next.kstop;
     pn.ok = next.ok;
     pn.over = nullptr;
     pn.rad_out = nullptr;   // (bartrt_get_radius: the radii of the batch this call computes)
-    r.nprep = pf_req_n;
+    r.nprep = rq.next_n;
     r.prep_next = pn;
   }
-  r.cloud_on = has_cloud || over_cloud;
+  r.cloud_on = has_cloud || (rq.over_cloud && (rq.over || rq.prep_hook));
   r.integ = integ;
   r.cut_slant = cut_slant ? 1 : 0;
   r.toomuch = toomuch;
   if (cut_slant) slant_thresholds(r);
-  r.spec = d_spec_out;
-  r.tau_out = (want_tau && n == 1) ? d_tau.get() : nullptr;
-  r.last_out = (want_tau && n == 1) ? d_last.get() : nullptr;
+  r.spec = rq.spec;
+  r.tau_out = (rq.want_tau && n == 1) ? d_tau.get() : nullptr;
+  r.last_out = (rq.want_tau && n == 1) ? d_last.get() : nullptr;
   r.intens_out = nullptr;
-  if (want_intens && n == 1 && solution == 0) {
+  if (rq.want_intens && n == 1 && eclipse_rt) {
     d_intens.reserve((size_t)A * W());
     r.intens_out = d_intens;
   }
   r.ntiles = (r.W + block - 1) / block;
   r.rtop = d_rtop; r.ds = d_ds;
   r.slog = nullptr;
-  if (cut_slant && integ == 1 && solution == 0 && !lbl_fused) {
+  if (cut_slant && integ == 1 && eclipse_rt) {
     // the event log of rule 1's single-wave `cut slant` kernels (rt_eclipse_s1s.hpp): 100 bytes per lane
     // (rules 0 / 2 -- rt_eclipse_fast<SLANT> -- keep none)
     const size_t need = slant_log_bytes(n, r.ntiles, block, A);
@@ -835,48 +891,50 @@ RtArgs Engine::rt_args(const PrepArgs &pa, const Prefetch &pf, double *d_spec_ou
       HIPCHK(hipEventCreate(&e));
       ev.push_back(e);
     }
-    if (lbl_fused) HIPCHK(hipEventRecord(ev[ev_used], st));
+    if (rq.lbl_fused) HIPCHK(hipEventRecord(ev[ev_used], rq.stream));
     else { r.ev_start = ev[ev_used]; r.ev_stop = ev[ev_used + 1]; }
   }
   r.walked_out = nullptr;
-  if (want_walked && solution == 0 && !lbl_fused) {
+  if (want_walked && eclipse_rt) {
     // the finest column any eclipse kernel records is ONE wavenumber wide (rt_eclipse_quad with one ray per lane, R = 8)
     const size_t need = (size_t)n * ((size_t)r.W + 64);
     d_walked.reserve(need);
-    HIPCHK(hipMemsetAsync(d_walked, 0, need * sizeof(int), st));
+    HIPCHK(hipMemsetAsync(d_walked, 0, need * sizeof(int), rq.stream));
     r.walked_out = d_walked;
     walked_nwalkers = n;
   }
   return r;
 }
 
-void Engine::run_chunk(const double *d_prof_in, int n, double *d_spec_out,
-                       unsigned char *d_okp, hipStream_t st, bool want_tau, const double *d_ext,
-                       bool lbl_fused) {
+void Engine::run_chunk(const RunRequest &rq) {
+  const int n = rq.n;
+  hipStream_t st = rq.stream;
   // coefficient workspaces are sized by cap_walkers; the caller's profile and spectrum buffers are used in place
   if (n > cap_walkers) ensure_walkers(n);
-  // prefetched preparation: only the plain table path of the eclipse geometry takes part
-  const bool pf_ok = !prep_hook && !prep_over_once && !lbl_fused && !d_ext && solution == 0 && !want_tau &&
-                     !want_intens && !lbl;
-  const Prefetch pf = plan_prefetch(pf_ok, d_prof_in, n, d_spec_out, d_okp, st);
+  // What kind of launch this is, worked out once.  eclipse_rt: launch_rt's, from the table or from a chunk's
+  // line-by-line extinction (not the lazy fused kernel, not the transit geometry).  plain: ... of the table path with
+  // the engine's own preparation and spectra as its only output.  Only a plain launch may have its walkers prepared
+  // by the RT kernel itself, and only one without overrides takes part in the prefetched preparation.
+  const bool eclipse_rt = solution == 0 && !rq.lbl_fused;
+  const bool plain = eclipse_rt && !lbl && !rq.d_ext && !rq.prep_hook && !rq.want_tau && !rq.want_intens;
+  const bool pf_ok = plain && !rq.over;
+  const Prefetch pf = plan_prefetch(pf_ok, rq);
   const bool use_have = pf.have, want_next = pf.want_next;
-  const PrepArgs pa = prep_args(d_prof_in, n, d_okp, rec[pf.bset]);
-  const bool over_cloud = prep_over_cloud && (prep_over_once || prep_hook);
-  prep_over_once = nullptr;
-  // one to four walkers of the plain table path: the RT kernel may prepare them itself (launch_rt_folded, below)
-  const bool try_fold = !use_have && !prep_hook && !want_next && solution == 0 && !lbl && !d_ext && !lbl_fused && !want_tau &&
-                        !want_intens && std::max(n, sel_walkers) <= 4 && integ == 1 && cut_slant && A == 5;
+  const PrepArgs pa = prep_args(rq, rec[pf.bset]);
+  // one to four walkers: the RT kernel may prepare them itself (launch_rt_folded, below)
+  const bool try_fold = plain && !use_have && !want_next && std::max(n, rq.sel_walkers) <= 4 && integ == 1 && cut_slant &&
+                        A == 5;
   if (use_have) {
     // prepared by the previous call's RT launch; its flags go where this call wants them
-    if (d_okp) HIPCHK(hipMemcpyAsync(d_okp, rec[pf.bset].ok, (size_t)n, hipMemcpyDeviceToDevice, st));
-  } else if (prep_hook) HIPCHK(prep_hook(pa, st, prep_hook_ctx));
+    if (rq.ok) HIPCHK(hipMemcpyAsync(rq.ok, rec[pf.bset].ok, (size_t)n, hipMemcpyDeviceToDevice, st));
+  } else if (rq.prep_hook) HIPCHK(rq.prep_hook(pa, st, rq.prep_hook_ctx));
   else if (!try_fold) HIPCHK(launch_prep(pa, st));
   if (solution == 1) HIPCHK(launch_chord_table(pa, st));
 
   // (a call that launches nothing -- no walkers -- takes no event pair: bartrt_timing_end would read unstamped events)
   const bool timed = timing && n > 0 && rt.W > 0 && (timing_seen++ % timing_stride == 0);
-  const RtArgs r = rt_args(pa, pf, d_spec_out, want_tau, d_ext, lbl_fused, over_cloud, timed, st);
-  if (lbl_fused) lbl_rt_eclipse(*this, d_prof_in, n, r, st);
+  const RtArgs r = rt_args(rq, pa, pf, eclipse_rt, timed);
+  if (rq.lbl_fused) lbl_rt_eclipse(*this, rq.prof, n, r, st);
   else if (solution == 1) {
     RtLaunchInfo li;   // (the transit kernels keep no walked-layer record: the name only)
     HIPCHK(launch_transit(r, st, &li));
@@ -893,14 +951,12 @@ void Engine::run_chunk(const double *d_prof_in, int n, double *d_spec_out,
     }
     if (want_walked) walked_info = li;
     if (want_next && li.prep_fused) {
-      pf_have_prof = pf_req_prof; pf_have_n = pf_req_n; pf_have_buf = 1 - pf.bset;
+      pf_have_prof = rq.next_prof; pf_have_n = rq.next_n; pf_have_buf = 1 - pf.bset;
       pf_have_stream = st; pf_have_set = pf.now;
     }
   }
-  pf_req_prof = nullptr;
-  pf_req_n = 0;
   if (timed) {
-    if (lbl_fused) HIPCHK(hipEventRecord(ev[ev_used + 1], st));
+    if (rq.lbl_fused) HIPCHK(hipEventRecord(ev[ev_used + 1], st));
     ev_used += 2;
   }
 }

@@ -52,6 +52,34 @@ struct RecordSet {
   }
 };
 
+// Everything ONE launch is asked to do (Engine::run).  It travels by const reference from the entry point through the
+// chunking down to run_chunk; the engine keeps nothing of it, so no caller has anything to clear afterwards.
+struct RunRequest {
+  const double *prof;         // [n][(S+1) L] profiles, where the device reads them
+  int n;                      // walkers
+  double *spec;               // [n][W] spectra
+  unsigned char *ok;          // [n] flags; null: the engine's own (rec[0].ok)
+  hipStream_t stream;
+  bool want_tau = false;      // single walker: optical depths and last layers into d_tau / d_last
+  bool want_intens = false;   // single walker, eclipse geometry: intensities per angle into d_intens
+  // per-walker radius / cloud-top / scattering overrides [n][3] for the prep launch (NaN: the engine's own value);
+  // over_cloud: a cloud top is among them (or among a hook's), so the RT kernels add the deck's surface term
+  const double *over = nullptr;
+  bool over_cloud = false;
+  int sel_walkers = 0;        // > 0: the walker count the kernel variant is chosen for instead of the batch's own (RtArgs::nsel)
+  int scat_flag = -1;         // the scattering flag of this launch alone; -1: the engine's
+  // when set, run_chunk calls it instead of launch_prep (the per-step path fuses T(p) + abundances into that launch, step.hip)
+  hipError_t (*prep_hook)(const PrepArgs &, hipStream_t, void *) = nullptr;
+  void *prep_hook_ctx = nullptr;
+  // filled in by run() and run_chunks(), not by callers: the batch named for the call after this one (Engine::Pending),
+  // and the line-by-line forms -- the chunk's extinction [n][L][W], or the lazy fused kernel
+  const double *next_prof = nullptr, *d_ext = nullptr;
+  int next_n = 0;
+  bool lbl_fused = false;
+  RunRequest(const double *prof_, int n_, double *spec_, unsigned char *ok_, hipStream_t st)
+      : prof(prof_), n(n_), spec(spec_), ok(ok_), stream(st) {}
+};
+
 struct Engine : EngineStream {
   // configuration
   TCfg cfg;
@@ -72,7 +100,6 @@ struct Engine : EngineStream {
   // kernel's latency floor, 52 us; spectra agree with the unsharded run's to 4e-16) or by the WHOLE grid's (false: cfg
   // `kernel_by whole` / BARTRT_KERNEL_BY=whole / bartrt_set_kernel_by -- the blocks then are the unsharded run's bits)
   bool kernel_by_local = true;
-  int sel_walkers = 0;    // > 0: the walker count the kernel variant is chosen for instead of the batch's own (RtArgs::nsel)
   bool cia_spline = false; // cfg `cia_interp spline` / BARTRT_CIA_INTERP: natural cubic splines in wavenumber and T (C20)
   double starrad = 0;     // cm, transit geometry
   double scat_value = 0, cloudtop = 0;
@@ -91,12 +118,16 @@ struct Engine : EngineStream {
   int cap_walkers = 0;
   DevBuf<double> d_prof, d_spec;
   RecordSet rec[2];                   // rec[1]: allocated at the first prefetch request (ensure_second_set)
-  const double *last_prof = nullptr;  // profiles of the latest host-buffer call (get_tau, get_intensity)
-  int last_n = 0;                     // ... and how many they are
+  // The profiles of the latest host-buffer call, which the optical-depth / intensity getters re-run.  They lie in d_prof
+  // or in h_pin, and are forgotten when that memory no longer holds them: d_prof regrown (ensure_walkers), h_pin regrown
+  // (ensure_pin), h_pin filled with parameters instead (step_run_host); a device-buffer call keeps nothing.
+  const double *last_prof = nullptr;
+  int last_n = 0;
+  void remember_profiles(const double *p, int n) { last_prof = p; last_n = n; }
+  void forget_profiles() { last_prof = nullptr; last_n = 0; }
   DevBuf<double> d_rtop, d_ds;  // transit geometry workspaces
   DevBuf<double> d_rad;     // [cap][L] hydrostatic radii of the last run
   DevBuf<double> d_intens;  // [A][W] of the last single-walker run with want_intens
-  bool want_intens = false;
   bool lbl_eager = true;       // full extinction first (default); BARTRT_LBL=lazy: fused kernel
   DevBuf<double> d_tau;  // [W][L] of the last single-walker run
   DevBuf<int> d_last;
@@ -110,15 +141,15 @@ struct Engine : EngineStream {
   unsigned int flag_seq = 0;
   bool sync_poll = true;
   void wait(hipStream_t st);
-  // when set, run_chunk calls this instead of launch_prep (the per-step path
-  // fuses T(p) + abundances into the same launch, step.hip)
-  hipError_t (*prep_hook)(const PrepArgs &, hipStream_t, void *) = nullptr;
-  void *prep_hook_ctx = nullptr;
-  // per-walker radius / cloud / scattering overrides for the NEXT prep launch only
-  // (set by step_profiles_dev, consumed by run_chunk); prep_over_cloud: a cloud-top
-  // parameter is among them, so the RT kernels add the deck's surface term
-  const double *prep_over_once = nullptr;
-  bool prep_over_cloud = false;
+  // What two calls of the C ABI leave for a later run: bartrt_step_profiles_dev the walkers' overrides, for the NEXT
+  // run (whichever it is); bartrt_prefetch_profiles_dev the batch of the run AFTER the next (prefetched preparation,
+  // below).  Written by those two, taken -- and cleared -- in one place, the head of run().
+  struct Pending {
+    const double *over = nullptr;       // RunRequest::over, ::over_cloud
+    bool over_cloud = false;
+    const double *next_prof = nullptr;  // RunRequest::next_prof, ::next_n
+    int next_n = 0;
+  } pending;
   // diagnostics of the next RT launches: layers walked per (walker, kernel column)
   bool want_walked = false;
   DevBuf<int> d_walked;
@@ -133,8 +164,6 @@ struct Engine : EngineStream {
   // profile buffer; the RT launch of the current call prepares that batch's layer records in
   // extra workgroups (RtArgs::nprep) into the second set of record buffers, and the next
   // call -- if it is for that buffer -- starts on its RT kernel directly.
-  const double *pf_req_prof = nullptr;   // requested for the call after the next run
-  int pf_req_n = 0;
   const double *pf_have_prof = nullptr;  // records of this batch are in buffer set pf_have_buf
   int pf_have_n = 0, pf_have_buf = 0;
   // ... built on this stream under these settings (everything of PrepArgs a setter can change)
@@ -173,20 +202,18 @@ struct Engine : EngineStream {
   void ensure_walkers(int n);
   void ensure_second_set();
   void ensure_pin(size_t bytes);
-  // d_prof_in -> d_spec_out ([n][W]); records events when timing
-  void run_dev(const double *d_prof_in, int n, double *d_spec_out, unsigned char *d_okp,
-               hipStream_t st, bool want_tau);
-  void run_chunk(const double *d_prof_in, int n, double *d_spec_out, unsigned char *d_okp,
-                 hipStream_t st, bool want_tau, const double *d_ext, bool lbl_fused = false);
-  // run_dev's chunked forms and the parts of run_chunk (engine.hip)
-  void run_chunks(const double *d_prof_in, int n, int chunk, double *d_spec_out, unsigned char *d_okp,
-                  hipStream_t st, bool want_tau, bool with_ext);
+  // rq.prof -> rq.spec ([n][W]) on rq.stream, with what `pending` holds; records events when timing
+  void run(const RunRequest &rq);
+  // host buffers: prof [n][nprof] -> spec [n][nwave] (nwave the block's samples, or the whole grid's: the block goes
+  // to its place in each row), flags to ok; without a flag array a walker that is not ok throws
+  void run_host(const double *prof, int n, int nprof, double *spec, int nwave, unsigned char *ok);
+  // run's chunked form and the parts of run_chunk (engine.hip)
+  void run_chunks(const RunRequest &rq, int chunk, bool with_ext);
+  void run_chunk(const RunRequest &rq);
   struct Prefetch;
-  Prefetch plan_prefetch(bool pf_ok, const double *d_prof_in, int n, const double *d_spec_out,
-                         const unsigned char *d_okp, hipStream_t st);
-  PrepArgs prep_args(const double *d_prof_in, int n, unsigned char *d_okp, const RecordSet &records);
-  RtArgs rt_args(const PrepArgs &pa, const Prefetch &pf, double *d_spec_out, bool want_tau, const double *d_ext,
-                 bool lbl_fused, bool over_cloud, bool timed, hipStream_t st);
+  Prefetch plan_prefetch(bool pf_ok, const RunRequest &rq);
+  PrepArgs prep_args(const RunRequest &rq, const RecordSet &records);
+  RtArgs rt_args(const RunRequest &rq, const PrepArgs &pa, const Prefetch &pf, bool eclipse_rt, bool timed);
 
   // bartrt_comm_init: with a communicator the per-step path gathers the ranks' blocks itself (step.hip).  Owned and
   // destroyed by capi.hip (bartrt_comm_free, bartrt_free_memory, a re-bartrt_init) before the engine goes.

@@ -139,30 +139,30 @@ void ChainService::run(const int *slots, int n, int nominal, int scat_flag, bool
   Engine *e = eng;
   const svc::Header *h = seg.hdr();
   const size_t nprof = (size_t)h->nprof, Wl = (size_t)h->Wl;
-  const int flag0 = e->scat_flag;
-  struct Restore { Engine *e; int f; ~Restore() { e->scat_flag = f; e->prep_over_once = nullptr; e->sel_walkers = 0; } } restore{e, flag0};
-  if (scat_flag >= 0) e->scat_flag = scat_flag;
   e->ensure_walkers(n);
-  e->last_prof = nullptr;
-  e->last_n = 0;
-  e->prep_over_cloud = any_cloud;
-  // the kernel of the full batch whatever posted together (svc_core.hpp, Backend::run)
-  e->sel_walkers = nominal > n ? nominal : n;
+  e->forget_profiles();
+  // one launch under the round's scattering flag and overrides (`over`: where the posted ones lie, used if any_over)
+  auto launch = [&](const double *prof, double *spec, unsigned char *ok, const double *over) {
+    RunRequest rq(prof, n, spec, ok, e->stream);
+    rq.scat_flag = scat_flag;
+    rq.over = any_over ? over : nullptr;
+    rq.over_cloud = any_cloud;
+    rq.sel_walkers = nominal > n ? nominal : n;   // the kernel of the full batch whatever posted together (svc_core.hpp, Backend::run)
+    e->run(rq);
+  };
   const int first = slots[0];
   bool consecutive = true;
   for (int k = 1; k < n; k++) consecutive &= slots[k] == slots[k - 1] + 1;
   if (registered && consecutive) {
-    e->prep_over_once = any_over ? d_over + 3 * (size_t)first : nullptr;
     const bool direct = sizeof(double) * (size_t)n * Wl <= direct_spec_bytes;
-    e->run_dev(d_prof + (size_t)first * nprof, n, direct ? d_spec + (size_t)first * Wl : e->d_spec, d_ok + first, e->stream, false);
+    launch(d_prof + (size_t)first * nprof, direct ? d_spec + (size_t)first * Wl : e->d_spec, d_ok + first, d_over + 3 * (size_t)first);
     if (!direct)
       HIPCHK(hipMemcpyAsync(seg.spec(first), e->d_spec, sizeof(double) * (size_t)n * Wl, hipMemcpyDeviceToHost, e->stream));
     wait_done();
   } else if (registered) {
     std::memcpy(seg.list(), slots, sizeof(int32_t) * (size_t)n);
     hipLaunchKernelGGL(svc_gather, dim3(n), dim3(256), 0, e->stream, d_prof, d_over, d_list, (int)nprof, e->d_prof, d_over_stage);
-    e->prep_over_once = any_over ? d_over_stage : nullptr;
-    e->run_dev(e->d_prof, n, e->d_spec, e->rec[0].ok, e->stream, false);
+    launch(e->d_prof, e->d_spec, e->rec[0].ok, d_over_stage);
     hipLaunchKernelGGL(svc_scatter, dim3((unsigned)((Wl + 255) / 256), n), dim3(256), 0, e->stream, e->d_spec, e->rec[0].ok, d_list, (int)Wl,
                        d_spec, d_ok);
     HIPCHK(hipGetLastError());
@@ -181,8 +181,7 @@ void ChainService::run(const int *slots, int n, int nominal, int scat_flag, bool
       HIPCHK(hipMemcpyAsync(e->d_prof + (size_t)k * nprof, seg.prof(s0), sizeof(double) * (size_t)cnt * nprof, hipMemcpyHostToDevice, e->stream));
       if (any_over) HIPCHK(hipMemcpyAsync(d_over_stage + 3 * (size_t)k, seg.over(s0), sizeof(double) * 3 * (size_t)cnt, hipMemcpyHostToDevice, e->stream));
     });
-    if (any_over) e->prep_over_once = d_over_stage;
-    e->run_dev(e->d_prof, n, e->d_spec, e->rec[0].ok, e->stream, false);
+    launch(e->d_prof, e->d_spec, e->rec[0].ok, d_over_stage);
     runs([&](int k, int s0, int cnt) {
       HIPCHK(hipMemcpyAsync(seg.spec(s0), e->d_spec + (size_t)k * Wl, sizeof(double) * (size_t)cnt * Wl, hipMemcpyDeviceToHost, e->stream));
       HIPCHK(hipMemcpyAsync(seg.ok(s0), e->rec[0].ok + k, (size_t)cnt, hipMemcpyDeviceToHost, e->stream));
