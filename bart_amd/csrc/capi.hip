@@ -10,6 +10,7 @@
 #include "lbl.hpp"
 #include "share.hpp"
 #include "step.hpp"
+#include "rt_launch.hpp"
 #include "rtc.hpp"
 #include "svc.hpp"
 
@@ -686,6 +687,19 @@ int bartrt_rtc_compile(const char *expr, int ilp, long *code_bytes) {
   const long n = rtc_compile_only(expr, ilp != 0, why);
   if (code_bytes) *code_bytes = n;
   return n < 0 ? fail(BARTRT_ENOTSUP, why) : BARTRT_OK;
+}
+
+const char *bartrt_kernel_choice(int nmol, long columns) {
+  return kernel_variant_name(slant_simpson_choice(nmol, columns < 0 ? 0 : columns).variant);
+}
+
+int bartrt_kernel_inventory(char *buf, int buflen) {
+  std::string s;
+  if (!kernel_inventory(s)) return fail(BARTRT_ENOTSUP, "kernel_inventory: a unit lists " + s + " and the ahead-of-time lookup does not reach it");
+  if (!buf || buflen < 0 || s.size() + 1 > (size_t)buflen)
+    return fail(BARTRT_EINVAL, "kernel_inventory: buffer too small, " + std::to_string(s.size() + 1) + " bytes needed");
+  std::memcpy(buf, s.c_str(), s.size() + 1);
+  return BARTRT_OK;
 }
 
 double bartrt_algorithmic_bytes(int nwalkers) {

@@ -777,7 +777,7 @@ struct Engine::Prefetch {
 Engine::Prefetch Engine::plan_prefetch(bool pf_ok, const RunRequest &rq) {
   bool want_next = pf_ok && rq.next_prof && rq.next_n > 0;
   // the RT launch that carries the next batch's preparation asks for the larger of the two jobs' LDS plus what its form
-  // adds (rt_eclipse.hpp, SpecLaunch: a double per layer in the 16-row forms, the 8.5 kB hand-off ring of
+  // adds (rt_launch.hpp, SpecLaunch: a double per layer in the 16-row forms, the 8.5 kB hand-off ring of
   // rt_eclipse_split) and is not opted in above the 64 kB default (lds.hpp): on a column whose preparation needs that
   // much the request is dropped, the named batch is prepared by its own call
   const size_t pf_lds = sizeof(double) * prep_lds_doubles(L, S, Nt, prep.ncia_temps) + std::max<size_t>(9 * 1024, sizeof(double) * L);

@@ -11,7 +11,7 @@
 //                    angle / molecule / CIA counts; also carries the line-by-line
 //                    extinction and the tau / per-angle outputs.
 //  rt_eclipse_fast / _split / _quad: the same walk specialised at compile time
-//                    (rt_eclipse.hpp, one translation unit per integration rule:
+//                    (rt_eclipse.hpp; launchers: rt_launch.hpp; one translation unit per integration rule:
 //                    rt_eclipse_i0.hip, _i1.hip, _i2.hip).
 //
 // The walker's coefficient records are staged in LDS once per workgroup and

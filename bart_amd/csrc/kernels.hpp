@@ -291,7 +291,7 @@ struct RtLaunchInfo {
 };
 
 #ifndef __HIPCC_RTC__
-// BARTRT_KERNEL (A/B runs, tests): the eclipse kernel form forced on the launches it can serve (rt_eclipse.hpp,
+// BARTRT_KERNEL (A/B runs, tests): the eclipse kernel form forced on the launches it can serve (rt_launch.hpp,
 // launch_rt_spec) -- generic | mono | mono_occ | mono_ilp | split | quad | octo | hexa | r32 | adj8 | adj16
 enum class KernelMode { kDefault, kGeneric, kMono, kMonoOcc, kMonoIlp, kSplit, kQuad, kOcto, kHexa, kR32, kAdj8, kAdj16 };
 // parsed once per process (kernels.hip); an unknown value is reported on stderr and the default choice applies

@@ -1,7 +1,16 @@
-// Specialised eclipse kernels under integration rule 0 (integ.hpp): the template
-// definitions are in rt_eclipse.hpp; one translation unit per rule keeps the
-// build parallel.
-#include "rt_eclipse.hpp"
+// Integration rule 0 (integ.hpp) under the default schedule, five ray angles: the layer-parallel kernel of `cut slant` with
+// one ray per lane and of `cut vertical`, the producer / consumer pair and the single-wave kernel of `cut vertical` --
+// and the rule's launcher (launch_rt_spec<0>, rt_launch.hpp; one translation unit per rule keeps the build parallel).
+#include "rt_launch.hpp"
+
+#define BARTRT_QUAD_RAYS(MM, CC) BARTRT_K(quad, 5, MM, CC, false, 8, 0, true) BARTRT_K(quad, 5, MM, CC, false, 4, 0, true)
+#define BARTRT_QUAD(MM, CC) \
+  BARTRT_K(quad, 5, MM, CC, true, 8, 0) BARTRT_K(quad, 5, MM, CC, true, 4, 0) BARTRT_K(quad, 5, MM, CC, false, 8, 0) BARTRT_K(quad, 5, MM, CC, false, 4, 0)
+#define BARTRT_SPLIT(MM, CC) BARTRT_K(split, 5, MM, CC, true, 0) BARTRT_K(split, 5, MM, CC, false, 0)
+#define BARTRT_FAST(MM, CC) BARTRT_K(fast, 5, MM, CC, true, 0) BARTRT_K(fast, 5, MM, CC, false, 0)
+#define BARTRT_UNIT i0
+#define BARTRT_UNIT_KERNELS BARTRT_MC_LIST(BARTRT_QUAD_RAYS) BARTRT_MC_LIST(BARTRT_QUAD) BARTRT_MC_LIST(BARTRT_SPLIT) BARTRT_MC_LIST(BARTRT_FAST)
+#include "rt_eclipse_unit.inc"
 
 namespace bartrt {
 template bool launch_rt_spec<0>(const RtArgs &, int, hipStream_t, KernelMode, bool, bool, hipError_t &,

@@ -1,27 +1,10 @@
-// Instantiations of rt_eclipse_qadj (rt_eclipse_qadj.hpp) and their launcher, in a translation unit of their own.
+// rt_eclipse_qadj (rt_eclipse_qadj.hpp: rule 1 / `cut slant`, a column's rows on adjacent lanes) for five ray angles,
+// R = 16 and 8, under the default schedule.
 #include "rt_eclipse_qadj.hpp"
+#include "rt_launch.hpp"
 
-#include <cstdlib>
-
-namespace bartrt {
-
-bool launch_rt_qadj(const RtArgs &b, bool sq, int rows, int nblocks, size_t sh, hipStream_t st, hipError_t &err) {
-  if (b.A != 5) return false;
-#define BARTRT_QADJ(MM, CC)                                                                                       \
-  if (b.M == MM && b.C == CC) {                                                                                   \
-    if (rows == 16) {                                                                                             \
-      if (sq) BARTRT_RT_LAUNCH((rt_eclipse_qadj<5, MM, CC, true, 16>), dim3(nblocks), dim3(256), sh, st, b);      \
-      else BARTRT_RT_LAUNCH((rt_eclipse_qadj<5, MM, CC, false, 16>), dim3(nblocks), dim3(256), sh, st, b);        \
-    } else {                                                                                                      \
-      if (sq) BARTRT_RT_LAUNCH((rt_eclipse_qadj<5, MM, CC, true, 8>), dim3(nblocks), dim3(256), sh, st, b);       \
-      else BARTRT_RT_LAUNCH((rt_eclipse_qadj<5, MM, CC, false, 8>), dim3(nblocks), dim3(256), sh, st, b);         \
-    }                                                                                                             \
-    err = hipGetLastError();                                                                                      \
-    return true;                                                                                                  \
-  }
-  BARTRT_QADJ_LIST(BARTRT_QADJ)
-#undef BARTRT_QADJ
-  return false;
-}
-
-}  // namespace bartrt
+#define BARTRT_QADJ(MM, CC) \
+  BARTRT_K(qadj, 5, MM, CC, true, 16) BARTRT_K(qadj, 5, MM, CC, false, 16) BARTRT_K(qadj, 5, MM, CC, true, 8) BARTRT_K(qadj, 5, MM, CC, false, 8)
+#define BARTRT_UNIT qadj
+#define BARTRT_UNIT_KERNELS BARTRT_QADJ_LIST(BARTRT_QADJ)
+#include "rt_eclipse_unit.inc"

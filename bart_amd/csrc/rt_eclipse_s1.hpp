@@ -337,10 +337,6 @@ void rt_eclipse_simpson(RtArgs p) {
     p.walked_out[(size_t)w * p.ntiles + tile] = (kw < kend + 1 ? kw : kend + 1);
 }
 
-// the ILP-scheduled build (rt_eclipse_i1_ilp.hip), and the line-by-line hand-off
-#ifndef __HIPCC_RTC__
-bool launch_rt_simpson_ilp(const RtArgs &b, bool sq, int block, int nblocks, size_t sh, hipStream_t st, hipError_t &err);
-bool launch_rt_simpson_ext(const RtArgs &b, bool sq, int block, int nblocks, size_t sh, hipStream_t st, hipError_t &err);
-#endif
+// (built in rt_eclipse_i1_ilp.hip -- the ILP schedule -- with and without the line-by-line hand-off)
 
 }  // namespace bartrt

@@ -461,7 +461,7 @@ void rt_eclipse_simpson_slant(RtArgs p) {
     p.walked_out[(size_t)w * p.ntiles + tile] = (kw < kend + 1 ? kw : kend + 1);
 }
 
-// the builds (rt_eclipse_i1s_ilp.hip): ray grids of five angles and of the other sizes, the line-by-line hand-off
-// (the launchers are declared with the other specialised kernels' in rt_eclipse.hpp)
+// (built in rt_eclipse_slant_ilp.hip: five angles, the line-by-line hand-off, the tau / intensity outputs; other ray-grid
+// sizes in rt_eclipse_angles.hip)
 
 }  // namespace bartrt

@@ -495,6 +495,14 @@ def walked_end():
     return out, wpc.value, name.value.decode()
 
 
+def kernel_inventory() -> list[tuple[str, bool, str]]:
+    """The eclipse kernels the library holds ahead of time: (template-id, max-ILP run-time build, object) each.  No GPU,
+    no engine."""
+    buf = C.create_string_buffer(1 << 18)
+    _check(trm.lib().bartrt_kernel_inventory(buf, len(buf)))
+    return [(e, i == "1", o) for e, i, o in (line.split("\t") for line in buf.value.decode().splitlines())]
+
+
 def algorithmic_bytes(nwalkers: int) -> float:
     return trm.lib().bartrt_algorithmic_bytes(int(nwalkers))
 

@@ -64,6 +64,7 @@ def lib():
         L.bartrt_build_id.restype = C.c_char_p
         L.bartrt_kernel_choice.restype = C.c_char_p
         L.bartrt_kernel_choice.argtypes = [i, C.c_long]
+        L.bartrt_kernel_inventory.argtypes = [C.c_char_p, i]
         L.bartrt_init.argtypes = [i, C.POINTER(C.c_char_p)]
         L.bartrt_get_waveno_arr.argtypes = [p, i]
         L.bartrt_set_radius.argtypes = [d]

@@ -332,6 +332,12 @@ const char *bartrt_build_id(void);
  * step of the layer-parallel walk), "adj8" / "adj16" (rows on adjacent lanes).  Needs no GPU and
  * no engine; the returned string is static. */
 const char *bartrt_kernel_choice(int nmol, long columns);
+/* The eclipse kernels the library holds ahead of time, one line each: the kernel's template-id in
+ * namespace bartrt with every argument spelled out (the text the run-time compiler is given for a
+ * shape that is NOT here), a tab, 1 / 0 -- whether a run-time build of it gets the max-ILP
+ * scheduling option --, a tab, the object that holds it.  Needs no GPU and no engine.
+ * BARTRT_EINVAL if `buf` is too small; bartrt_last_error() then names the size needed. */
+int bartrt_kernel_inventory(char *buf, int buflen);
 int bartrt_get_nlayers(void);
 int bartrt_get_nspecies(void);
 int bartrt_get_nprof(void);                 /* (S+1)*L */

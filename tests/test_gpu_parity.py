@@ -179,7 +179,7 @@ def wide_cases(tmp_path_factory):
 
 
 def forced_kernel(mode, integ, cut, single_wave=True):
-    """The kernel BARTRT_KERNEL=mode launches under rule `integ` and `cut` (RtLaunchInfo::kernel, csrc/rt_eclipse.hpp).
+    """The kernel BARTRT_KERNEL=mode launches under rule `integ` and `cut` (RtLaunchInfo::kernel, csrc/rt_launch.hpp).
     single_wave: the shape has single-wave builds (at most 20 table loads per layer, 2 M + 2 C; wider shapes leave
     those forms to the generic kernel)."""
     if mode == "generic" or (mode.startswith("mono") and not single_wave):

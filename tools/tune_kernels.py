@@ -171,7 +171,7 @@ def write_inc(table, record, grids):
 // launch's 64-sample columns (walkers the variant is chosen for x ceil(samples / 64)) and the number of table molecules.
 // GENERATED by tools/tune_kernels.py from launch times measured on an MI355X -- every variant forced in turn
 // (BARTRT_KERNEL) on each tuning grid and walker count; the figures behind each boundary are in the JSON record named
-// below.  Do not edit by hand: re-run the tool (rt_eclipse.hpp reads the table through slant_simpson_choice()).
+// below.  Do not edit by hand: re-run the tool (rt_launch.hpp reads the table through slant_simpson_choice()).
 //   record: %s
 //   tuned on (samples, table molecules, layers): %s
 // An entry {max_columns, variant, fallback} serves columns <= max_columns; `fallback` is what runs where the adjacent-rows
