@@ -211,17 +211,35 @@ def _mcmc_vectors(cfg):
     return (np.array([float(x) for x in d["params"].split()]), np.array([float(x) for x in d["stepsize"].split()]))
 
 
-def _run_samples(cfg, samples, filters, kind, chunk):
+def _sharding(shard, group):
+    """The (rank, count) of this process's wavenumber block: ``shard`` as Worker / engine.init take it, else
+    BARTRT_GPUS = G > 1 over the G ranks of the process group (BARTfunc.main's convention), else None."""
+    if shard is not None:
+        return (int(shard[0]), int(shard[1]))
+    ngpu = int(os.environ.get("BARTRT_GPUS", "1"))
+    if ngpu <= 1:
+        return None
+    import torch.distributed as dist
+    if not dist.is_initialized() or dist.get_world_size(group) != ngpu:
+        raise ValueError("posterior: BARTRT_GPUS = %d needs a torch process group of that many ranks" % ngpu)
+    return (dist.get_rank(group), ngpu)
+
+
+def _run_samples(cfg, samples, filters, kind, chunk, shard=None, device=None, group=None):
     """Worker, step and CF set up from the [MCMC] configuration as BARTfunc.Worker does; the samples in chunks.
-    -> (band [nsamples, nfilters, L], status [nsamples], kind)."""
+    -> (band [nsamples, nfilters, L], status [nsamples], kind).  ``shard`` (rank, count) with count > 1: the engine
+    holds its wavenumber block, the library's communicator is attached over ``group`` (engine.comm_init) and every
+    rank, making the same calls, gets the same rows."""
     from . import BARTfunc, engine
     wcfg = BARTfunc.WorkerConfig.from_cfg(cfg)
     if kind is None:
         kind = "transmittance" if wcfg.solution == "transit" else "contribution"     # BART.py:637-644
     if kind not in ("contribution", "transmittance"):
         raise ValueError("posterior: kind is 'contribution' or 'transmittance'")
-    w = BARTfunc.Worker(wcfg, carry=False)
+    w = BARTfunc.Worker(wcfg, shard=shard, device=device, group=group, carry=False)
     try:
+        if shard is not None and shard[1] > 1:
+            engine.comm_init(group)
         win = filter_windows(w.specwn, list(filters if filters is not None else wcfg.filters))
         bands, stats = [], []
         for off in range(0, len(samples), chunk):
@@ -237,7 +255,8 @@ def _run_samples(cfg, samples, filters, kind, chunk):
         w.close()
 
 
-def posterior(output_npy, cfg, filters, burnin, thinning=1, kind=None, chunk=4096, layout=None):
+def posterior(output_npy, cfg, filters, burnin, thinning=1, kind=None, chunk=4096, layout=None, shard=None,
+              device=None, group=None):
     """The band-averaged contribution functions or transmittance of every sample of an MCMC posterior, and their
     envelopes: what bestFit.callTransit (code/bestFit.py:429-525) draws beside the T(p) envelopes, for the whole
     posterior instead of the best fit.  ``output_npy``: the output.npy of MC3 or of bart_amd.retrieve (a path or the
@@ -249,11 +268,16 @@ def posterior(output_npy, cfg, filters, burnin, thinning=1, kind=None, chunk=409
     them.  -> dict: ``samples`` [n, npars] (full parameters), ``band`` [n, nfilters, L] (atm layer order; NaN rows
     for rejected samples), ``status`` [n] (0, 1 temperature, 2 abundance), ``kind``, and over the accepted samples
     ``median``, ``lo1``, ``hi1``, ``lo2``, ``hi2`` [nfilters, L] (the 15.87 / 84.13 / 2.28 / 97.72 percentiles of
-    bestFit.py:461-465; NaN when no sample was accepted).  No plots."""
+    bestFit.py:461-465; NaN when no sample was accepted).  No plots.
+    ``shard`` = (rank, count), ``device``, ``group``: the sharding BARTfunc.Worker and engine.init take (or
+    BARTRT_GPUS = G over a torch process group of G ranks) -- each rank's engine holds one wavenumber block, every
+    rank calls posterior with the same arguments and returns the same curves and envelopes."""
     params, stepsize = _mcmc_vectors(cfg)
     data = np.load(output_npy) if isinstance(output_npy, (str, bytes, os.PathLike)) else output_npy
     samples = posterior_samples(data, params, stepsize, burnin, thinning, layout)
-    band, status, kind = _run_samples(cfg, samples, filters, kind, max(1, int(chunk)))
+    shard = _sharding(shard, group)
+    extra = {} if shard is None and device is None else {"shard": shard, "device": device, "group": group}
+    band, status, kind = _run_samples(cfg, samples, filters, kind, max(1, int(chunk)), **extra)
     out = {"samples": samples, "band": band, "status": status, "kind": kind}
     good = band[status == 0]
     if len(good):

@@ -710,26 +710,38 @@ double bartrt_algorithmic_bytes(int nwalkers) {
 }
 
 // ---- contribution functions / band transmittance (contrib.hip) ----------
-// what the batched post-processing does not serve: line-by-line engines, sharded engines (a service client never
-// gets here: NEED_ENGINE answers it with BARTRT_ENOTSUP)
-static int cf_unsupported(const Engine *e, const char *who) {
+// what the batched post-processing does not serve: line-by-line engines, and -- the calls that combine the ranks'
+// sums themselves (blocks false) -- sharded engines without a communicator, the rule the step follows (a service
+// client never gets here: NEED_ENGINE answers it with BARTRT_ENOTSUP)
+static int cf_unsupported(const Engine *e, const char *who, bool blocks = false) {
   if (e->lbl) return fail(BARTRT_ENOTSUP, std::string(who) + ": line-by-line engines are not supported");
-  if (e->lo != 0 || e->hi != e->Wfull) return fail(BARTRT_ENOTSUP, std::string(who) + ": sharded engines are not supported");
+  if (!blocks && !e->comm && (e->lo != 0 || e->hi != e->Wfull))
+    return fail(BARTRT_ENOTSUP, std::string(who) + ": sharded engines are not supported without a communicator "
+                                                   "(bartrt_comm_init; or bartrt_cf_setup_block / _partials_dev / _combine_dev)");
   return BARTRT_OK;
 }
 
-int bartrt_cf_setup(int nfilters, const int *idx0, const int *npts, const double *resp) {
-  NEED_ENGINE();
-  if (int rc = cf_unsupported(g_eng, "cf_setup")) return rc;
-  if (nfilters < 1 || !idx0 || !npts || !resp) return fail(BARTRT_EINVAL, "cf_setup: null buffer or no filters");
+static int cf_setup_any(int nfilters, const int *idx0, const int *npts, const double *resp, const char *who, bool blocks) {
+  if (int rc = cf_unsupported(g_eng, who, blocks)) return rc;
+  if (nfilters < 1 || !idx0 || !npts || !resp) return fail(BARTRT_EINVAL, std::string(who) + ": null buffer or no filters");
   return guarded([&] {
     cf_setup(*g_eng, nfilters, idx0, npts, resp);
     return BARTRT_OK;
   });
 }
 
-static int cf_check_kind(const Engine *e, int kind, const char *who) {
-  if (int rc = cf_unsupported(e, who)) return rc;
+int bartrt_cf_setup(int nfilters, const int *idx0, const int *npts, const double *resp) {
+  NEED_ENGINE();
+  return cf_setup_any(nfilters, idx0, npts, resp, "cf_setup", false);
+}
+
+int bartrt_cf_setup_block(int nfilters, const int *idx0, const int *npts, const double *resp) {
+  NEED_ENGINE();
+  return cf_setup_any(nfilters, idx0, npts, resp, "cf_setup_block", true);
+}
+
+static int cf_check_kind(const Engine *e, int kind, const char *who, bool blocks = false) {
+  if (int rc = cf_unsupported(e, who, blocks)) return rc;
   if (kind != BARTRT_CF_CONTRIB && kind != BARTRT_CF_TRANSMIT)
     return fail(BARTRT_EINVAL, std::string(who) + ": kind must be BARTRT_CF_CONTRIB or BARTRT_CF_TRANSMIT");
   if (kind == BARTRT_CF_CONTRIB && e->solution != 0)
@@ -783,6 +795,31 @@ int bartrt_cf_batch_over_dev(const double *d_prof, int nwalkers, const double *d
   if (!d_prof || !d_band || nwalkers < 0) return fail(BARTRT_EINVAL, "cf_batch_over_dev: null buffer");
   return guarded([&] {
     cf_run_dev(*e, d_prof, nwalkers, kind, d_band, d_full, d_ok, stream ? (hipStream_t)stream : e->stream, d_over);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_cf_partials_dev(const double *d_prof, int nwalkers, int kind, const double *d_over, double *d_part,
+                           double *d_full, unsigned char *d_ok, void *stream) {
+  NEED_ENGINE();
+  Engine *e = g_eng;
+  if (int rc = cf_check_kind(e, kind, "cf_partials_dev", true)) return rc;
+  if (!d_prof || !d_part || nwalkers < 0) return fail(BARTRT_EINVAL, "cf_partials_dev: null buffer");
+  return guarded([&] {
+    cf_partials_dev(*e, d_prof, nwalkers, kind, d_over, d_part, d_full, d_ok, stream ? (hipStream_t)stream : e->stream);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_cf_combine_dev(const double *d_slots, int nranks, int nwalkers, const unsigned char *d_ok, double *d_band,
+                          void *stream) {
+  NEED_ENGINE();
+  Engine *e = g_eng;
+  if (int rc = cf_unsupported(e, "cf_combine_dev", true)) return rc;
+  if (cf_nfilters(*e) == 0) return fail(BARTRT_EINVAL, "cf_combine_dev: call bartrt_cf_setup first");
+  if (!d_slots || !d_band || nwalkers < 0) return fail(BARTRT_EINVAL, "cf_combine_dev: null buffer");
+  return guarded([&] {
+    cf_combine_dev(*e, d_slots, nranks, nwalkers, d_ok, d_band, stream ? (hipStream_t)stream : e->stream);
     return BARTRT_OK;
   });
 }

@@ -15,19 +15,29 @@
 //                     that overlaps the tile, lane (j, q) sums layer j over the 16 wavenumbers of quarter q with the
 //                     filter's weights h_i resp_i (h = 1/2 at the window's ends), two cross-lane butterflies add the
 //                     quarters, and one partial per (walker, tile, filter, layer) goes to a workspace.
-//  cf_finish          sums each filter's partials in tile order, divides by trapz(resp).
+//  cf_block_sums      sums each filter's partials in tile order: this engine's part of the band sum, one value per
+//                     (walker, filter, layer), layers from the top, not yet divided.
+//  cf_combine         adds the ranks' parts in rank order, divides by trapz(resp), writes atm layer order.
+// An engine on a wavenumber block [lo, hi) (--shard r n) does the same on its own samples: lane i of tile t is grid
+// sample lo + 64 t + i, as the RT kernels' columns count, and cf_setup clips each window to the block -- the half
+// weights stay at the window's true ends, whichever rank holds them, and trapz(resp) is the whole window's.  With a
+// communicator (bartrt_comm_init) the parts go into this rank's slot of its receive buffer, ONE in-place all-gather
+// per chunk fills the others, and cf_combine reads the slots where they lie; without one the only slot is a
+// workspace of this module.  One rank: 0 + (the tile-order sum) is that sum, so the bits are those of a single pass.
 // Posterior samples (bartrt_cf_batch_over, bartrt_cf_params): the layer records are prepared under each walker's own
 // reference radius, cloud top and Rayleigh value (PrepArgs::over, the per-step path's mechanism); from parameter
 // vectors the step's converter (step_convert_dev) writes profiles, statuses and those overrides into this module's
 // workspaces first.  The CF kernels themselves do not know: they read records, chord tables and deck layers.
 // Every sum has a fixed order and no atomics: the bits do not depend on the batch a walker is in.  Not part of the
 // per-step hot path: no kernel table, no run-time instantiation; molecule and CIA counts are run-time parameters.
+#include "comm.hpp"
 #include "contrib.hpp"
 #include "integ.hpp"
 #include "kernels.hpp"
 #include "step.hpp"
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <memory>
@@ -195,11 +205,10 @@ __global__ __launch_bounds__(64) void cf_transit(CfArgs p) {
   }
 }
 
-// band[w][f][L - 1 - k] = sum over the filter's entries (tile order) of part[w][e][k] / trapz(resp_f); NaN for a
-// walker whose profile prep_profiles flagged
-__global__ __launch_bounds__(256) void cf_finish(const double *part, int nwalkers, int nf, int nent, int L,
-                                                 const int *f_ptr, const int *f_ent, const double *trapz,
-                                                 const unsigned char *ok, double *band) {
+// sums[w][f][k] = sum over the filter's entries on this engine's block (tile order) of part[w][e][k]; 0 for a
+// filter without a sample here.  Layers from the top, not divided.
+__global__ __launch_bounds__(256) void cf_block_sums(const double *part, int nwalkers, int nf, int nent, int L,
+                                                     const int *f_ptr, const int *f_ent, double *sums) {
   const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (t >= (size_t)nwalkers * nf * L) return;
   const int k = (int)(t % L);
@@ -207,7 +216,21 @@ __global__ __launch_bounds__(256) void cf_finish(const double *part, int nwalker
   const int w = (int)(t / ((size_t)L * nf));
   double s = 0.0;
   for (int j = f_ptr[f]; j < f_ptr[f + 1]; j++) s += part[((size_t)w * nent + f_ent[j]) * L + k];
-  band[((size_t)w * nf + f) * L + (L - 1 - k)] = ok[w] ? s / trapz[f] : __builtin_nan("");
+  sums[t] = s;
+}
+
+// band[w][f][L - 1 - k] = (sum over the ranks' slots, rank order, of slots[r][w][f][k]) / trapz(resp_f); NaN for a
+// walker whose profile prep_profiles flagged (ok null: none is).  `slot` doubles from one rank's part to the next's.
+__global__ __launch_bounds__(256) void cf_combine(const double *slots, int nranks, size_t slot, int nwalkers, int nf,
+                                                  int L, const double *trapz, const unsigned char *ok, double *band) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)nwalkers * nf * L) return;
+  const int k = (int)(t % L);
+  const int f = (int)((t / L) % nf);
+  const int w = (int)(t / ((size_t)L * nf));
+  double s = 0.0;
+  for (int r = 0; r < nranks; r++) s += slots[(size_t)r * slot + t];
+  band[((size_t)w * nf + f) * L + (L - 1 - k)] = !ok || ok[w] ? s / trapz[f] : __builtin_nan("");
 }
 
 // Per-walker settings as the caller states them (what bartrt_set_radius / _set_cloudtop take: km, log10 bar) -> as
@@ -243,6 +266,7 @@ struct CfWork {
   int cap = 0;
   RecordSet rec;
   DevBuf<double> d_rtop, d_ds, d_part;
+  DevBuf<double> d_sums;              // [cap][nf][L]: the block's band sums where no receive buffer takes them
   // per-walker overrides in prep_profiles' units [cap_over][3]; the parameter front end's profiles [cap_par][nprof]
   // and statuses
   int cap_over = 0, cap_par = 0;
@@ -253,6 +277,7 @@ struct CfWork {
 };
 struct CfState : CfWork {   // ... and the filter tables
   int nf = 0, ntiles = 0, nent = 0;
+  int nent_bound = 0;   // at least any block's entry count, from the windows alone: the same on every rank
   DevBuf<int> d_tile_ptr, d_f_ptr, d_f_ent;
   DevBuf<double> d_wt, d_trapz, d_rdlp;
 };
@@ -268,7 +293,8 @@ size_t workspace_cap() {
 
 size_t per_walker_bytes(const Engine &e, bool over = false, bool params = false) {
   const CfState &g = *e.cf;
-  size_t b = sizeof(double) * (size_t)g.nent * e.L + sizeof(double) * (size_t)e.L * coef_stride(e.M, e.C) +
+  // (nothing here depends on the engine's block: ranks that make the same call cut it into the same chunks)
+  size_t b = sizeof(double) * ((size_t)g.nent_bound + g.nf) * e.L + sizeof(double) * (size_t)e.L * coef_stride(e.M, e.C) +
              sizeof(idx_t) * (size_t)e.L * idx_stride(e.C) + sizeof(int) + 1;
   if (e.solution == 1) b += sizeof(double) * ((size_t)e.L + chord_table_size(e.L));
   if (over || params) b += sizeof(double) * 3;
@@ -290,6 +316,7 @@ void ensure_cap(const Engine &e, int n, bool over = false, bool params = false) 
   if (n > g.cap) {
     g.rec.reserve((size_t)n, e.L, e.M, e.C);
     g.d_part.reserve((size_t)n * g.nent * e.L);
+    g.d_sums.reserve((size_t)n * g.nf * e.L);
     if (e.solution == 1) {
       g.d_rtop.reserve((size_t)n * e.L);
       g.d_ds.reserve((size_t)n * chord_table_size(e.L));
@@ -319,11 +346,12 @@ void allow_lds(K kernel, size_t bytes) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
 }
 
-// one chunk: m walkers whose flags go to okp.  d_over (optional): the walkers' overrides in prep_profiles' units,
-// their radii checked on the device if check_radius (the host-buffer call has checked them already);
-// d_status (optional): the converter's verdicts -- a rejected sample's flag is cleared
-void run_chunk(Engine &e, const double *d_prof, int m, int kind, double *d_band, double *d_full, unsigned char *okp,
-               hipStream_t st, const double *d_over = nullptr, const int *d_status = nullptr, bool check_radius = false) {
+// one chunk up to this engine's band sums d_sums [m][nf][L] (cf_block_sums): m walkers whose flags go to okp.
+// d_over (optional): the walkers' overrides in prep_profiles' units, their radii checked on the device if
+// check_radius (the host-buffer call has checked them already); d_status (optional): the converter's verdicts -- a
+// rejected sample's flag is cleared
+void run_sums(Engine &e, const double *d_prof, int m, int kind, double *d_sums, double *d_full, unsigned char *okp,
+              hipStream_t st, const double *d_over = nullptr, const int *d_status = nullptr, bool check_radius = false) {
   const CfState &g = *e.cf;
   // the layer records under the engine's settings, as run_transit_batch builds them, into this module's buffers
   // (no radii output, only the caller's own per-walker overrides: the engine's own state is left as it was)
@@ -380,24 +408,59 @@ void run_chunk(Engine &e, const double *d_prof, int m, int kind, double *d_band,
   }
   HIPCHK(hipGetLastError());
   const size_t nout = (size_t)m * g.nf * e.L;
-  hipLaunchKernelGGL(cf_finish, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, g.d_part, m, g.nf, g.nent,
-                     e.L, g.d_f_ptr, g.d_f_ent, g.d_trapz, okp, d_band);
+  hipLaunchKernelGGL(cf_block_sums, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, g.d_part, m, g.nf, g.nent,
+                     e.L, g.d_f_ptr, g.d_f_ent, d_sums);
   HIPCHK(hipGetLastError());
 }
+
+void combine(const Engine &e, const double *d_slots, int nranks, size_t slot, int m, const unsigned char *okp,
+             double *d_band, hipStream_t st) {
+  const CfState &g = *e.cf;
+  const size_t nout = (size_t)m * g.nf * e.L;
+  hipLaunchKernelGGL(cf_combine, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, d_slots, nranks, slot, m, g.nf,
+                     e.L, g.d_trapz, okp, d_band);
+  HIPCHK(hipGetLastError());
+}
+
+// one chunk, band rows out.  With a communicator: the sums go into this rank's slot of its receive buffer, one
+// in-place all-gather on st (every rank makes the same call: m is the same everywhere), the slots combined in rank
+// order.  Without one the engine holds the whole grid and its sums are the only slot.
+void run_chunk(Engine &e, const double *d_prof, int m, int kind, double *d_band, double *d_full, unsigned char *okp,
+               hipStream_t st, const double *d_over = nullptr, const int *d_status = nullptr, bool check_radius = false) {
+  const CfState &g = *e.cf;
+  const size_t count = (size_t)m * g.nf * e.L;
+  if (Comm *c = e.comm) {
+    double *recv = comm_recv(*c, count * c->nranks);
+    run_sums(e, d_prof, m, kind, recv + (size_t)c->rank * count, d_full, okp, st, d_over, d_status, check_radius);
+    comm_allgather_inplace(*c, recv, count, st);
+    e.ncollectives++;
+    combine(e, recv, c->nranks, count, m, okp, d_band, st);
+    return;
+  }
+  if (e.lo != 0 || e.hi != e.Wfull) throw std::invalid_argument("cf: a sharded engine needs a communicator (bartrt_comm_init)");
+  run_sums(e, d_prof, m, kind, g.d_sums, d_full, okp, st, d_over, d_status, check_radius);
+  combine(e, g.d_sums, 1, count, m, okp, d_band, st);
+}
+
+// samples per row of `full` as the chunk size counts them: the largest block under a communicator (the same on
+// every rank), else this engine's own
+size_t full_rows(const Engine &e) { return e.comm ? step_block_max(e.Wfull, e.comm->nranks) : (size_t)e.W(); }
 
 }  // namespace
 
 void cf_setup(Engine &e, int nf, const int *idx0, const int *npts, const double *resp) {
   if (nf < 1 || !idx0 || !npts || !resp) throw std::invalid_argument("cf_setup: no filters");
-  const int W = e.W(), L = e.L;
+  // the engine's block [lo, hi) of the grid (the whole grid on an unsharded engine): tiles count from lo
+  const int Wfull = e.Wfull, lo = e.lo, hi = e.hi, L = e.L;
   std::vector<double> trapz(nf);
   std::vector<size_t> off(nf + 1, 0);
   for (int f = 0; f < nf; f++) {
-    if (npts[f] < 2 || idx0[f] < 0 || (long)idx0[f] + npts[f] > W)
+    if (npts[f] < 2 || idx0[f] < 0 || (long)idx0[f] + npts[f] > Wfull)
       throw std::invalid_argument("cf_setup: filter " + std::to_string(f) + " needs a window of at least two samples inside the grid");
     off[f + 1] = off[f] + npts[f];
   }
-  // trapz(resp) with unit spacing (np.trapz without x): half weights at the window's ends
+  // trapz(resp) with unit spacing (np.trapz without x): half weights at the window's ends -- its true ends on the
+  // full grid; where the block cuts a window the cut sample keeps weight 1 -- and the whole window's sum on every rank
   auto weight = [&](int f, int s) { return (s == 0 || s == npts[f] - 1 ? 0.5 : 1.0) * resp[off[f] + s]; };
   for (int f = 0; f < nf; f++) {
     double t = 0.0;
@@ -406,21 +469,25 @@ void cf_setup(Engine &e, int nf, const int *idx0, const int *npts, const double 
       throw std::invalid_argument("cf_setup: filter " + std::to_string(f) + " has no response inside the grid");
     trapz[f] = t;
   }
-  const int ntiles = (W + 63) / 64;
+  const int ntiles = (hi - lo + 63) / 64;
   std::vector<int> tile_ptr(ntiles + 1, 0), ent_f;
   std::vector<double> wt;
   for (int t = 0; t < ntiles; t++) {
+    const int t0 = lo + 64 * t, t1 = std::min(t0 + 64, hi);   // the tile's samples on the full grid
     for (int f = 0; f < nf; f++) {
-      const int a = std::max(idx0[f], 64 * t), b = std::min(idx0[f] + npts[f], 64 * t + 64);
+      const int a = std::max(idx0[f], t0), b = std::min(idx0[f] + npts[f], t1);
       if (a >= b) continue;
       ent_f.push_back(f);
       const size_t at = wt.size();
       wt.resize(at + 64, 0.0);
-      for (int i = a; i < b; i++) wt[at + (i - 64 * t)] = weight(f, i - idx0[f]);
+      for (int i = a; i < b; i++) wt[at + (i - t0)] = weight(f, i - idx0[f]);
     }
     tile_ptr[t + 1] = (int)ent_f.size();
   }
   const int nent = (int)ent_f.size();
+  // a window of n samples meets at most n / 64 + 2 tiles, wherever the tiles start
+  long bound = 0;
+  for (int f = 0; f < nf; f++) bound += npts[f] / 64 + 2;
   std::vector<int> f_ptr(nf + 1, 0), f_ent;
   for (int f = 0; f < nf; f++) {
     for (int j = 0; j < nent; j++)
@@ -439,9 +506,10 @@ void cf_setup(Engine &e, int nf, const int *idx0, const int *npts, const double 
   g->d_wt.upload(wt);
   g->d_trapz.upload(trapz);
   g->d_rdlp.upload(rdlp);
-  g->nf = nf; g->nent = nent; g->ntiles = ntiles;
-  // an earlier setup's workspaces stay unless the entry count changes (it sizes the partials); its tables go with `old`
-  if (old && old->nent == nent) static_cast<CfWork &>(*g) = std::move(*old);
+  g->nf = nf; g->nent = nent; g->ntiles = ntiles; g->nent_bound = (int)std::min<long>(bound, INT_MAX);
+  // an earlier setup's workspaces stay unless the entry or filter count changes (they size the partials and the
+  // sums); its tables go with `old`
+  if (old && old->nent == nent && old->nf == nf) static_cast<CfWork &>(*g) = std::move(*old);
   e.cf = g.release();
 }
 
@@ -476,6 +544,32 @@ void cf_run_dev(Engine &e, const double *d_prof, int n, int kind, double *d_band
               d_full ? d_full + (size_t)off * e.W() * e.L : nullptr, d_ok ? d_ok + off : g.rec.ok.get(), st, ov, nullptr,
               true);
   }
+}
+
+void cf_partials_dev(Engine &e, const double *d_prof, int n, int kind, const double *d_over, double *d_part,
+                     double *d_full, unsigned char *d_ok, hipStream_t st) {
+  check_ready(e, kind);
+  if (n <= 0) return;
+  CfState &g = *e.cf;
+  const int nprof = (e.S + 1) * e.L;
+  const int chunk = chunk_of((size_t)n, per_walker_bytes(e, d_over != nullptr));
+  ensure_cap(e, chunk, d_over != nullptr);
+  claim(g, st);
+  for (int off = 0; off < n; off += chunk) {
+    const int m = std::min(chunk, n - off);
+    const double *ov = d_over ? convert_over(g, d_over + (size_t)3 * off, m, st) : nullptr;
+    run_sums(e, d_prof + (size_t)off * nprof, m, kind, d_part + (size_t)off * g.nf * e.L,
+             d_full ? d_full + (size_t)off * e.W() * e.L : nullptr, d_ok ? d_ok + off : g.rec.ok.get(), st, ov, nullptr,
+             true);
+  }
+}
+
+void cf_combine_dev(Engine &e, const double *d_slots, int nranks, int n, const unsigned char *d_ok, double *d_band,
+                    hipStream_t st) {
+  if (!e.cf) throw std::invalid_argument("cf: call bartrt_cf_setup first");
+  if (nranks < 1 || nranks > e.Wfull) throw std::invalid_argument("cf_combine: nranks must lie in [1, the grid's sample count]");
+  if (n <= 0) return;
+  combine(e, d_slots, nranks, (size_t)n * e.cf->nf * e.L, n, d_ok, d_band, st);
 }
 
 void cf_params_dev(Engine &e, const double *d_params, int n, int npars, int kind, double *d_band, double *d_full,
@@ -550,9 +644,10 @@ void cf_run_host(Engine &e, const double *prof, int n, int kind, double *band, d
   CfState &g = *e.cf;
   const size_t nprof = (size_t)(e.S + 1) * e.L;
   const size_t bprof = sizeof(double) * nprof, bband = sizeof(double) * (size_t)g.nf * e.L,
-               bfull = full ? sizeof(double) * (size_t)e.W() * e.L : 0;
-  Staging s = stage_for(e, n, bprof + bband + bfull + 1, over != nullptr, false);
-  double *dp = s.take<double>(bprof), *db = s.take<double>(bband), *df = full ? s.take<double>(bfull) : nullptr;
+               bfull = full ? sizeof(double) * (size_t)e.W() * e.L : 0,
+               bfull_max = full ? sizeof(double) * full_rows(e) * e.L : 0;
+  Staging s = stage_for(e, n, bprof + bband + bfull_max + 1, over != nullptr, false);
+  double *dp = s.take<double>(bprof), *db = s.take<double>(bband), *df = full ? s.take<double>(bfull_max) : nullptr;
   unsigned char *dok = s.take<unsigned char>(1);
   hipStream_t st = e.stream;
   std::vector<unsigned char> hok(s.chunk);
@@ -584,9 +679,10 @@ void cf_params_host(Engine &e, const double *params, int n, int npars, int kind,
   if (n <= 0) return;
   CfState &g = *e.cf;
   const size_t bpar = sizeof(double) * (size_t)npars, bband = sizeof(double) * (size_t)g.nf * e.L,
-               bfull = full ? sizeof(double) * (size_t)e.W() * e.L : 0;
-  Staging s = stage_for(e, n, bpar + bband + bfull + sizeof(int), true, true);
-  double *dp = s.take<double>(bpar), *db = s.take<double>(bband), *df = full ? s.take<double>(bfull) : nullptr;
+               bfull = full ? sizeof(double) * (size_t)e.W() * e.L : 0,
+               bfull_max = full ? sizeof(double) * full_rows(e) * e.L : 0;
+  Staging s = stage_for(e, n, bpar + bband + bfull_max + sizeof(int), true, true);
+  double *dp = s.take<double>(bpar), *db = s.take<double>(bband), *df = full ? s.take<double>(bfull_max) : nullptr;
   int *dst = s.take<int>(sizeof(int));
   hipStream_t st = e.stream;
   for (int off = 0; off < n; off += s.chunk) {

@@ -9,11 +9,25 @@ namespace bartrt {
 
 enum { kCfContrib = 0, kCfTransmit = 1 };
 
-// Filter windows on the FULL grid (the engine must not be sharded): filter f covers samples
-// idx0[f] .. idx0[f] + npts[f] - 1 with the response resp[f] already interpolated onto them
-// (concatenated).  Replaces an earlier setup.  Throws on bad windows.
+// Filter windows on the FULL grid: filter f covers samples idx0[f] .. idx0[f] + npts[f] - 1 with the response resp[f]
+// already interpolated onto them (concatenated).  The tables are built for the engine's block [lo, hi): each window
+// clipped to it, the half weights at the window's true ends only, trapz(resp) of the whole window; a filter without
+// a sample in the block has no entries.  Replaces an earlier setup.  Throws on bad windows.
 void cf_setup(Engine &e, int nfilters, const int *idx0, const int *npts, const double *resp);
 int cf_nfilters(const Engine &e);
+// The two halves of a call, for a caller that runs its own collective (and for one GPU standing in for any rank
+// count).  cf_partials_dev: this engine's band sums d_part [n][nfilters][L] -- layers from the top, entries added in
+// tile order, not divided -- with d_full [n][W][L] of its own block, d_ok and d_over as cf_run_dev.  cf_combine_dev:
+// d_slots = nranks slots of n * nfilters * L doubles, added in rank order, divided by trapz(resp), atm layer order
+// into d_band [n][nfilters][L]; NaN rows where d_ok (optional) is 0.  No atomics: the bits depend on nranks only.
+void cf_partials_dev(Engine &e, const double *d_prof, int n, int kind, const double *d_over, double *d_part,
+                     double *d_full, unsigned char *d_ok, hipStream_t st);
+void cf_combine_dev(Engine &e, const double *d_slots, int nranks, int n, const unsigned char *d_ok, double *d_band,
+                    hipStream_t st);
+// The calls below combine the ranks' sums themselves: an unsharded engine's only slot is a workspace; an engine with
+// a communicator (sharded or not) writes its slot of the receive buffer, issues ONE in-place all-gather per chunk
+// and combines the slots -- every rank makes the same call and gets the same rows; d_full is the block's own
+// [n][W][L].  A sharded engine without a communicator: std::invalid_argument.
 // d_prof [n][nprof] -> d_band [n][nfilters][L] (atm layer order); d_full [n][W][L] (atm layer order)
 // or null; d_ok [n] or null (flags in the module's own workspace).  Asynchronous on st.
 // d_over [n][3] or null: each walker's own reference radius (km), log10 cloud-top pressure (bar) and Rayleigh value --

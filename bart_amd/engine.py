@@ -441,7 +441,8 @@ def comm_init(group=None) -> None:
     """Attaches the library's communicator over the ranks of a torch process group (gloo or nccl): rank 0 makes the
     id, one broadcast over the group hands its 128 bytes to the others, every rank attaches.  The group's ranks must be
     the engine's --shard ranks.  Afterwards step_batch / step_batch_dev / sampler.run_native run on the sharded engine
-    with one collective per step, inside the library."""
+    with one collective per step, inside the library, and so do cf_setup, contribution* and transmittance* (one
+    collective per chunk of walkers)."""
     import torch
     import torch.distributed as dist
     rank, world = dist.get_rank(group), dist.get_world_size(group)
@@ -512,10 +513,18 @@ CF_CONTRIB, CF_TRANSMIT = 0, 1
 _cf_nfilters = 0     # filters of the latest cf_setup (the band tensors' middle axis)
 
 
-def cf_setup(filters) -> int:
+def _cf_wlocal() -> int:
+    """Rows of a walker's ``full`` output: the engine's own samples (the whole grid unless sharded)."""
+    lo, hi = local_range()
+    return hi - lo
+
+
+def cf_setup(filters, block=False) -> int:
     """The filter windows of the batched contribution-function calls: a list of filter files (read and
-    windowed on the engine's grid by bart_amd.cf.filter_windows) or the (idx0, npts, resp, trapz) that
-    function returns.  Kept by the engine until the next cf_setup / init / free_memory.  -> nfilters."""
+    windowed on the engine's FULL grid by bart_amd.cf.filter_windows) or the (idx0, npts, resp, trapz) that
+    function returns.  Kept by the engine until the next cf_setup / init / free_memory.  -> nfilters.
+    A sharded engine takes it after comm_init (every rank the same windows); ``block`` (cf_setup_block): the same
+    tables for the engine's block without a communicator, for cf_partials_dev / cf_combine_dev."""
     if isinstance(filters, tuple) and len(filters) == 4 and not isinstance(filters[0], (str, bytes, os.PathLike)):
         idx0, npts, resp, _ = filters
     else:
@@ -525,9 +534,53 @@ def cf_setup(filters) -> int:
     resp = np.ascontiguousarray(resp, np.double)
     assert idx0.size == npts.size and resp.size == int(npts.sum())
     global _cf_nfilters
-    _check(trm.lib().bartrt_cf_setup(idx0.size, _ptr(idx0), _ptr(npts), _ptr(resp)))
+    setup = trm.lib().bartrt_cf_setup_block if block else trm.lib().bartrt_cf_setup
+    _check(setup(idx0.size, _ptr(idx0), _ptr(npts), _ptr(resp)))
     _cf_nfilters = int(idx0.size)
     return _cf_nfilters
+
+
+def cf_setup_block(filters) -> int:
+    """cf_setup on any engine, sharded or not, with no communicator (include/bartrt.h, bartrt_cf_setup_block): the
+    windows, stated on the full grid, are clipped to the engine's block.  For cf_partials_dev / cf_combine_dev."""
+    return cf_setup(filters, block=True)
+
+
+def cf_partials_dev(d_prof, kind, full=False, d_ok=None, stream=None, over=None):
+    """This engine's part of the band sums (bartrt_cf_partials_dev) for the filters of the latest cf_setup /
+    cf_setup_block: d_prof a float64 CUDA tensor [nwalkers, (S+1)*L], kind CF_CONTRIB / CF_TRANSMIT -> part
+    [nwalkers, nfilters, L] (layers from the top, not divided: one slot of cf_combine_dev), and with ``full`` the
+    block's own per-wavenumber values [nwalkers, W_local, L] (atm layer order).  d_ok, over as contribution_dev."""
+    import torch
+    assert d_prof.is_cuda and d_prof.dtype == torch.float64 and d_prof.is_contiguous()
+    n = d_prof.shape[0]
+    part, fout = _cf_dev_outputs(n, full, d_prof.device)
+    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    if d_ok is not None:
+        assert d_ok.is_cuda and d_ok.dtype == torch.uint8 and d_ok.numel() >= n
+    if over is not None:
+        assert over.is_cuda and over.dtype == torch.float64 and over.is_contiguous() and tuple(over.shape) == (n, 3)
+    _check(trm.lib().bartrt_cf_partials_dev(vp(d_prof), n, int(kind), vp(over), vp(part), vp(fout), vp(d_ok),
+                                            _stream_ptr(stream)))
+    return (part, fout) if full else part
+
+
+def cf_combine_dev(d_slots, nranks, d_ok=None, stream=None):
+    """The ranks' parts where an all-gather leaves them -> band rows (bartrt_cf_combine_dev): d_slots a float64 CUDA
+    tensor of nranks slots [nwalkers, nfilters, L] (slot r = rank r's cf_partials_dev), added in rank order, divided by
+    trapz(resp), atm layer order -> [nwalkers, nfilters, L]; NaN rows where d_ok (uint8 [nwalkers]) is 0."""
+    import torch
+    assert d_slots.is_cuda and d_slots.dtype == torch.float64 and d_slots.is_contiguous()
+    per = _cf_nfilters * nlayers()
+    assert _cf_nfilters and nranks >= 1 and d_slots.numel() % (nranks * per) == 0
+    n = d_slots.numel() // (nranks * per)
+    if d_ok is not None:
+        assert d_ok.is_cuda and d_ok.dtype == torch.uint8 and d_ok.numel() >= n
+    band = torch.empty((n, _cf_nfilters, nlayers()), dtype=torch.float64, device=d_slots.device)
+    _check(trm.lib().bartrt_cf_combine_dev(
+        C.c_void_p(d_slots.data_ptr()), int(nranks), n, C.c_void_p(d_ok.data_ptr()) if d_ok is not None else None,
+        C.c_void_p(band.data_ptr()), _stream_ptr(stream)))
+    return band
 
 
 def _cf_over(over, n):
@@ -542,7 +595,7 @@ def _cf_over(over, n):
 def _cf_batch(profiles, filters, kind, full, want_ok, over=None):
     prof = np.ascontiguousarray(profiles, np.double).reshape(-1, nprof())
     nf = cf_setup(filters)
-    n, L, W = prof.shape[0], nlayers(), trm.get_no_samples()
+    n, L, W = prof.shape[0], nlayers(), _cf_wlocal()
     band = np.zeros((n, nf, L))
     fout = np.zeros((n, W, L)) if full else None
     ok = np.zeros(n, np.uint8)
@@ -562,7 +615,9 @@ def contribution(profiles, filters, normalize=True, full=False, want_ok=False, o
     then (full) the per-wavenumber values [nwalkers, W, L], then (want_ok) the walkers' flags -- without
     want_ok a non-finite profile raises; with it, that walker's rows are NaN.  A single array is returned
     bare, several as a tuple.  ``over`` [nwalkers, 3]: every walker's own reference radius (km), log10 cloud-top
-    pressure (bar) and Rayleigh value, NaN = the engine-wide setting (bartrt_cf_batch_over)."""
+    pressure (bar) and Rayleigh value, NaN = the engine-wide setting (bartrt_cf_batch_over).
+    On a sharded engine after comm_init every rank makes the same call and gets the same band rows; ``filters`` are
+    windows on the full grid and the per-wavenumber values are the rank's own block [nwalkers, W_local, L]."""
     from .cf import normalize as _norm
     band, fout, ok = _cf_batch(profiles, filters, CF_CONTRIB, full, want_ok, over)
     out = [band] + ([_norm(band)] if normalize else []) + ([fout] if full else []) + ([ok] if want_ok else [])
@@ -583,7 +638,7 @@ def _cf_dev_outputs(n, full, device):
     if not _cf_nfilters:
         raise trm.TransitError("the device forms of the contribution-function calls: call engine.cf_setup(filters) first")
     band = torch.empty((n, _cf_nfilters, nlayers()), dtype=torch.float64, device=device)
-    fout = torch.empty((n, trm.get_no_samples(), nlayers()), dtype=torch.float64, device=device) if full else None
+    fout = torch.empty((n, _cf_wlocal(), nlayers()), dtype=torch.float64, device=device) if full else None
     return band, fout
 
 
@@ -623,7 +678,7 @@ def _cf_params(params, filters, kind, full):
     p = np.ascontiguousarray(params, np.double)
     p = p.reshape(-1, p.shape[-1])
     nf = cf_setup(filters)
-    n, L, W = p.shape[0], nlayers(), trm.get_no_samples()
+    n, L, W = p.shape[0], nlayers(), _cf_wlocal()
     band = np.zeros((n, nf, L))
     fout = np.zeros((n, W, L)) if full else None
     status = np.zeros(n, np.int32)

@@ -119,6 +119,9 @@ def lib():
         L.bartrt_cf_batch_over_dev.argtypes = [p, i, p, i, p, p, p, p]
         L.bartrt_cf_params.argtypes = [p, i, i, i, p, p, p]
         L.bartrt_cf_params_dev.argtypes = [p, i, i, i, p, p, p, p]
+        L.bartrt_cf_setup_block.argtypes = [i, p, p, p]
+        L.bartrt_cf_partials_dev.argtypes = [p, i, i, p, p, p, p, p]
+        L.bartrt_cf_combine_dev.argtypes = [p, i, i, p, p, p]
         L.bartrt_algorithmic_bytes.argtypes = [i]
         L.bartrt_algorithmic_bytes.restype = d
         _lib = L

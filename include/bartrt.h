@@ -308,8 +308,11 @@ int bartrt_step_bandflux_blocks_dev(const double *d_blocks, int nranks, int nwal
  * LOCKSTEP: bartrt_mcmc_run is host code around that step -- every rank runs the same seeded loop on band fluxes that
  * are the same bits on every rank, so the ranks draw the same proposals, issue the same collectives and write
  * identical chains; give every rank the same arguments.
- * Line-by-line engines: the step with a communicator returns BARTRT_ENOTSUP.  Contribution functions stay
- * unsupported on sharded engines.  Without a communicator a sharded engine's step fails as before. */
+ * The contribution-function calls (bartrt_cf_setup, _batch, _batch_over, _params and their _dev forms, below) follow
+ * the same rule: with a communicator they run on sharded engines, one in-place ncclAllGather per chunk of walkers in
+ * the same receive buffer, and every rank gets the same band rows bit for bit.
+ * Line-by-line engines: the step with a communicator returns BARTRT_ENOTSUP, and so do the contribution-function
+ * calls.  Without a communicator a sharded engine's step and its bartrt_cf_setup fail as before. */
 #define BARTRT_COMM_ID_BYTES 128          /* = NCCL_UNIQUE_ID_BYTES */
 int bartrt_comm_get_unique_id(void *id);  /* rank 0 calls it; the launcher broadcasts the bytes */
 int bartrt_comm_init(const void *id, int rank, int nranks);
@@ -378,7 +381,7 @@ int bartrt_get_intensity_of(int walker, double *intens, int nangles, int nwave);
  * filter's window (filter_cf: np.trapz without x, half weights at the window's two ends).
  * Normalisation (filt_cf_norm) is left to the caller (bart_amd.engine.contribution).
  *
- * bartrt_cf_setup: the filter windows on the FULL grid: filter f covers samples idx0[f] ..
+ * bartrt_cf_setup: the filter windows on the FULL grid (on a sharded engine too): filter f covers samples idx0[f] ..
  * idx0[f] + npts[f] - 1 (at least two, inside the grid) with the filter's response already
  * interpolated onto them, resp = the nfilters windows concatenated (bart_amd.cf.filter_windows
  * builds them as filter_cf does: the samples strictly inside the filter's wavenumber range).
@@ -398,7 +401,36 @@ int bartrt_get_intensity_of(int walker, double *intens, int nangles, int nwave);
  * walked-layer records, bartrt_get_radius.  Results are bit-identical from run to run and
  * do not depend on which other walkers share the call.  Internally the walkers go in chunks
  * whose workspace stays under BARTRT_CF_WORKSPACE_BYTES (default 256 MiB).
- * BARTRT_ENOTSUP: line-by-line engines, sharded engines (--shard), chain-service clients.
+ * BARTRT_ENOTSUP: line-by-line engines, sharded engines (--shard) WITHOUT a communicator, chain-service clients.
+ *
+ * Sharded engines (--shard r n) with a communicator attached (bartrt_comm_init): every call of this block is
+ * accepted, bartrt_cf_setup included, and bartrt_comm_free brings BARTRT_ENOTSUP back.  The windows are still
+ * stated on the FULL grid.  Each rank works on its own block [lo, hi): the windows clipped to it (the half weights of
+ * the unit-spacing trapezoid stay at a window's true first and last sample, whichever rank holds them; a sample where
+ * the block cuts a window has weight 1; a filter without a sample on a rank contributes 0 there), its sums
+ * part[walker][filter][layer] -- layers from the top, added in tile order, not yet divided -- written straight into
+ * this rank's slot of the communicator's receive buffer.  Per chunk of walkers ONE in-place ncclAllGather on the
+ * call's stream fills the other slots, and one kernel adds the slots in rank order (no atomics), divides by the
+ * whole window's trapz(resp) and writes atm layer order.  Every rank makes the same calls with the same arguments
+ * and the same BARTRT_CF_WORKSPACE_BYTES (the chunk size follows from the windows and the largest block, never from
+ * the rank's own block) and gets the same band rows bit for bit; they agree with the unsharded engine's to the
+ * rounding of a differently associated sum.  `full` is the rank's own [nwalkers][hi - lo][nlayers].  The ok flags and
+ * the per-walker settings do not depend on wavenumber: every rank flags the same walkers.  An unsharded engine with
+ * a communicator of one rank takes the same code and returns the bits it returns without one.  The sharded form has
+ * run on one GPU only (ranks one after the other, two processes on one device, RCCL worlds of one): no time is
+ * stated for it because none has been measured, and no machine with more than one GPU has run it.
+ *
+ * For callers that run their own collective, and for one GPU standing in for any rank count (the counterpart of
+ * bartrt_step_bandflux_blocks_dev); no communicator needed, any table engine, sharded or not:
+ *   bartrt_cf_setup_block    bartrt_cf_setup's arguments and tables for the engine's block, accepted on a sharded
+ *                            engine without a communicator (where bartrt_cf_setup keeps refusing).
+ *   bartrt_cf_partials_dev   d_prof[nwalkers][nprof] -> this engine's d_part[nwalkers][nfilters][nlayers] as above;
+ *                            d_over[nwalkers][3] as bartrt_cf_batch_over_dev or NULL; d_full (the block's own
+ *                            [nwalkers][hi - lo][nlayers]) and d_ok may be NULL.  Asynchronous on `stream`.
+ *   bartrt_cf_combine_dev    d_slots = nranks slots of nwalkers * nfilters * nlayers doubles, slot r = rank r's
+ *                            d_part -> d_band[nwalkers][nfilters][nlayers]; NaN rows where d_ok[w] == 0 (NULL: no
+ *                            walker is flagged).  1 <= nranks <= the grid's sample count.  On one slot: the bits
+ *                            of bartrt_cf_batch_dev.
  *
  * bartrt_cf_batch_over / _over_dev: the same with every walker under its OWN settings -- a
  * posterior's samples, whose radius, cloud top and scattering are fitted parameters
@@ -450,6 +482,11 @@ int bartrt_cf_params(const double *params, int nwalkers, int npars, int kind,
                      double *band, double *full, int *status);
 int bartrt_cf_params_dev(const double *d_params, int nwalkers, int npars, int kind,
                          double *d_band, double *d_full, int *d_status, void *stream);
+int bartrt_cf_setup_block(int nfilters, const int *idx0, const int *npts, const double *resp);
+int bartrt_cf_partials_dev(const double *d_prof, int nwalkers, int kind, const double *d_over,
+                           double *d_part, double *d_full, unsigned char *d_ok, void *stream);
+int bartrt_cf_combine_dev(const double *d_slots, int nranks, int nwalkers, const unsigned char *d_ok,
+                          double *d_band, void *stream);
 
 /* Line-by-line engines only (cfg has `linedb`, no `opacityfile`): the Voigt
  * extinction of one profile, ext[nlayers][nwave_local] in cm-1, atm layer order. */
