@@ -35,31 +35,46 @@ static int fail(int code, const std::string &m) {
   return code;
 }
 
+// the one ladder from the exception in flight to the code and text the C ABI reports
+struct Failure {
+  int code;
+  std::string msg;
+};
+static Failure what_failed() {
+  try {
+    throw;
+  } catch (const IoError &e) { return {BARTRT_EIO, e.msg};
+  } catch (const HipError &e) { return {BARTRT_ENODEV, std::string(e.what) + ": " + hipGetErrorString(e.e)};
+  } catch (const svc::Error &e) { return {e.code, e.msg};
+  } catch (const CommError &e) { return {e.code, e.msg};
+  } catch (const std::exception &e) { return {BARTRT_EINVAL, e.what()};
+  } catch (...) { return {BARTRT_EINVAL, "unknown error"}; }
+}
+
 template <class F>
 static int guarded(F &&f) {
   try {
     return f();
-  } catch (const IoError &e) {
-    return fail(BARTRT_EIO, e.msg);
-  } catch (const HipError &e) {
-    return fail(BARTRT_ENODEV, std::string(e.what) + ": " + hipGetErrorString(e.e));
-  } catch (const svc::Error &e) {
-    return fail(e.code, e.msg);
-  } catch (const CommError &e) {
-    return fail(e.code, e.msg);
-  } catch (const std::exception &e) {
-    return fail(BARTRT_EINVAL, e.what());
+  } catch (...) {
+    const Failure w = what_failed();
+    return fail(w.code, w.msg);
   }
 }
 
-#define NEED_ENGINE()                                                                                              \
-  if (!g_eng)                                                                                                      \
-  return g_cli ? fail(BARTRT_ENOTSUP, std::string(__func__) +                                                      \
-                                          ": this process is a client of the shareOpacity chain service (the engine lives in " \
-                                          "process " + std::to_string(g_cli->seg.hdr()->owner_pid.load()) +         \
-                                          "); the reference module's eight calls and the plain getters are served -- " \
-                                          "BARTRT_SHARE_MODE=ipc (or off) gives every process its own engine")      \
-               : fail(BARTRT_EINVAL, "engine not initialised: call bartrt_init first")
+// func: the entry point's own name, as the refusal to a service client states it
+static int need_engine(const char *func) {
+  if (g_eng) return BARTRT_OK;
+  return g_cli ? fail(BARTRT_ENOTSUP, std::string(func) +
+                                          ": this process is a client of the shareOpacity chain service (the engine lives in "
+                                          "process " + std::to_string(g_cli->seg.hdr()->owner_pid.load()) +
+                                          "); the reference module's eight calls and the plain getters are served -- "
+                                          "BARTRT_SHARE_MODE=ipc (or off) gives every process its own engine")
+               : fail(BARTRT_EINVAL, "engine not initialised: call bartrt_init first");
+}
+#define NEED_ENGINE() \
+  if (int rc_ = need_engine(__func__)) return rc_
+// the stream a device-buffer call runs on: the caller's, or (null) the engine's own
+static hipStream_t stream_of(void *stream) { return stream ? (hipStream_t)stream : g_eng->stream; }
 // the calls a service client answers itself
 #define CLIENT_OR_ENGINE() \
   if (!g_eng && !g_cli) return fail(BARTRT_EINVAL, "engine not initialised: call bartrt_init first")
@@ -132,17 +147,6 @@ std::string service_key(const InitArgs &a) {
          "|shard " + std::to_string(a.shard_rank) + "/" + std::to_string(a.shard_n) + "|svc v3|" + bartrt_build_id();
 }
 
-std::string what_failed() {
-  try {
-    throw;
-  } catch (const IoError &e) { return e.msg;
-  } catch (const HipError &e) { return std::string(e.what) + ": " + hipGetErrorString(e.e);
-  } catch (const svc::Error &e) { return e.msg;
-  } catch (const CommError &e) { return e.msg;
-  } catch (const std::exception &e) { return e.what();
-  } catch (...) { return "unknown error"; }
-}
-
 void teardown(double wait_s) {
   if (g_cli) {
     g_cli->detach();
@@ -183,7 +187,7 @@ void start_service(int argc, const char **argv, const InitArgs &ia) {
         e->init(argc, argv);
         g_svc = ChainService::start(std::move(seg), e);
       } catch (...) {
-        const std::string why = what_failed();
+        const std::string why = what_failed().msg;
         svc::retire(seg, why.c_str());
         seg.unmap();
         delete e;
@@ -467,7 +471,7 @@ int bartrt_run_transit_batch_dev(const double *d_prof, int nwalkers, double *d_s
   NEED_ENGINE();
   if (!d_prof || !d_spec || nwalkers < 0) return fail(BARTRT_EINVAL, "run_transit_batch_dev: null buffer");
   return guarded([&] {
-    hipStream_t st = stream ? (hipStream_t)stream : g_eng->stream;
+    hipStream_t st = stream_of(stream);
     // device-buffer calls keep no profile: the optical-depth / intensity getters must not fall
     // back on an older host-buffer call's
     g_eng->forget_profiles();
@@ -713,7 +717,7 @@ double bartrt_algorithmic_bytes(int nwalkers) {
 // what the batched post-processing does not serve: line-by-line engines, and -- the calls that combine the ranks'
 // sums themselves (blocks false) -- sharded engines without a communicator, the rule the step follows (a service
 // client never gets here: NEED_ENGINE answers it with BARTRT_ENOTSUP)
-static int cf_unsupported(const Engine *e, const char *who, bool blocks = false) {
+static int cf_unsupported(const Engine *e, const char *who, bool blocks) {
   if (e->lbl) return fail(BARTRT_ENOTSUP, std::string(who) + ": line-by-line engines are not supported");
   if (!blocks && !e->comm && (e->lo != 0 || e->hi != e->Wfull))
     return fail(BARTRT_ENOTSUP, std::string(who) + ": sharded engines are not supported without a communicator "
@@ -740,77 +744,77 @@ int bartrt_cf_setup_block(int nfilters, const int *idx0, const int *npts, const 
   return cf_setup_any(nfilters, idx0, npts, resp, "cf_setup_block", true);
 }
 
-static int cf_check_kind(const Engine *e, int kind, const char *who, bool blocks = false) {
-  if (int rc = cf_unsupported(e, who, blocks)) return rc;
-  if (kind != BARTRT_CF_CONTRIB && kind != BARTRT_CF_TRANSMIT)
-    return fail(BARTRT_EINVAL, std::string(who) + ": kind must be BARTRT_CF_CONTRIB or BARTRT_CF_TRANSMIT");
-  if (kind == BARTRT_CF_CONTRIB && e->solution != 0)
-    return fail(BARTRT_ENOTSUP, std::string(who) + ": contribution functions need the eclipse geometry (transmittance serves transit)");
-  if (cf_nfilters(*e) == 0) return fail(BARTRT_EINVAL, std::string(who) + ": call bartrt_cf_setup first");
-  return BARTRT_OK;
+// The one gate of the batch calls: a request (contrib.hpp) is checked here, once, and cf_run trusts it.  In order: the
+// engine, its limits, the step's setup (parameter calls), kind and geometry, the CF setup, the parameter count, the
+// buffers, the stated profile length (nprof; -1 where the ABI takes none).  rq.stream arrives as the caller's handle.
+static int cf_call(const char *who, CfRequest rq, int nprof = -1) {
+  if (int rc = need_engine(("bartrt_" + std::string(who)).c_str())) return rc;
+  Engine *e = g_eng;
+  const std::string pre = std::string(who) + ": ";
+  if (int rc = cf_unsupported(e, who, rq.partials)) return rc;
+  if (rq.from_params && !e->step) return fail(BARTRT_EINVAL, pre + "call bartrt_step_setup first");
+  if (rq.kind != BARTRT_CF_CONTRIB && rq.kind != BARTRT_CF_TRANSMIT)
+    return fail(BARTRT_EINVAL, pre + "kind must be BARTRT_CF_CONTRIB or BARTRT_CF_TRANSMIT");
+  if (rq.kind == BARTRT_CF_CONTRIB && e->solution != 0)
+    return fail(BARTRT_ENOTSUP, pre + "contribution functions need the eclipse geometry (transmittance serves transit)");
+  if (cf_nfilters(*e) == 0) return fail(BARTRT_EINVAL, pre + "call bartrt_cf_setup first");
+  if (rq.from_params && rq.npars != step_npars(*e))
+    return fail(BARTRT_EINVAL, pre + "npars must be nPT + (radius, cloud top, scattering parameters "
+                                     "declared with step_set_extras) + nmolfit");
+  if (!rq.in || !rq.out || rq.n < 0) return fail(BARTRT_EINVAL, pre + "null buffer");
+  if (nprof >= 0 && nprof != (e->S + 1) * e->L) return fail(BARTRT_EINVAL, pre + "profile length must be (nspecies+1)*nlayers");
+  rq.stream = stream_of(rq.stream);
+  return guarded([&] {
+    cf_run(*e, rq);
+    return BARTRT_OK;
+  });
+}
+
+// the entry points' arguments as requests: profiles (with overrides or null) and parameter rows; stream null with
+// `host`, which runs on the engine's own
+static CfRequest cf_profiles(const double *prof, int n, const double *over, int kind, double *out, double *full,
+                             unsigned char *ok, bool host, void *stream) {
+  CfRequest rq;
+  rq.n = n; rq.kind = kind; rq.in = prof; rq.over = over; rq.out = out; rq.full = full; rq.ok = ok;
+  rq.host = host; rq.stream = (hipStream_t)stream;
+  return rq;
+}
+
+static CfRequest cf_params(const double *params, int n, int npars, int kind, double *band, double *full, int *status,
+                           bool host, void *stream) {
+  CfRequest rq;
+  rq.n = n; rq.kind = kind; rq.in = params; rq.from_params = true; rq.npars = npars; rq.out = band; rq.full = full;
+  rq.status = status; rq.host = host; rq.stream = (hipStream_t)stream;
+  return rq;
 }
 
 int bartrt_cf_batch(const double *prof, int nwalkers, int nprof, int kind, double *band, double *full, unsigned char *ok) {
-  NEED_ENGINE();
-  Engine *e = g_eng;
-  if (int rc = cf_check_kind(e, kind, "cf_batch")) return rc;
-  if (!prof || !band || nwalkers < 0) return fail(BARTRT_EINVAL, "cf_batch: null buffer");
-  if (nprof != (e->S + 1) * e->L) return fail(BARTRT_EINVAL, "cf_batch: profile length must be (nspecies+1)*nlayers");
-  return guarded([&] {
-    cf_run_host(*e, prof, nwalkers, kind, band, full, ok);
-    return BARTRT_OK;
-  });
+  return cf_call("cf_batch", cf_profiles(prof, nwalkers, nullptr, kind, band, full, ok, true, nullptr), nprof);
 }
 
 int bartrt_cf_batch_dev(const double *d_prof, int nwalkers, int kind, double *d_band, double *d_full,
                         unsigned char *d_ok, void *stream) {
-  NEED_ENGINE();
-  Engine *e = g_eng;
-  if (int rc = cf_check_kind(e, kind, "cf_batch_dev")) return rc;
-  if (!d_prof || !d_band || nwalkers < 0) return fail(BARTRT_EINVAL, "cf_batch_dev: null buffer");
-  return guarded([&] {
-    cf_run_dev(*e, d_prof, nwalkers, kind, d_band, d_full, d_ok, stream ? (hipStream_t)stream : e->stream);
-    return BARTRT_OK;
-  });
+  return cf_call("cf_batch_dev", cf_profiles(d_prof, nwalkers, nullptr, kind, d_band, d_full, d_ok, false, stream));
 }
 
 int bartrt_cf_batch_over(const double *prof, int nwalkers, int nprof, const double *over, int kind, double *band,
                          double *full, unsigned char *ok) {
-  NEED_ENGINE();
-  Engine *e = g_eng;
-  if (int rc = cf_check_kind(e, kind, "cf_batch_over")) return rc;
-  if (!prof || !band || nwalkers < 0) return fail(BARTRT_EINVAL, "cf_batch_over: null buffer");
-  if (nprof != (e->S + 1) * e->L) return fail(BARTRT_EINVAL, "cf_batch_over: profile length must be (nspecies+1)*nlayers");
-  return guarded([&] {
-    cf_run_host(*e, prof, nwalkers, kind, band, full, ok, over);
-    return BARTRT_OK;
-  });
+  return cf_call("cf_batch_over", cf_profiles(prof, nwalkers, over, kind, band, full, ok, true, nullptr), nprof);
 }
 
 int bartrt_cf_batch_over_dev(const double *d_prof, int nwalkers, const double *d_over, int kind, double *d_band,
                              double *d_full, unsigned char *d_ok, void *stream) {
-  NEED_ENGINE();
-  Engine *e = g_eng;
-  if (int rc = cf_check_kind(e, kind, "cf_batch_over_dev")) return rc;
-  if (!d_prof || !d_band || nwalkers < 0) return fail(BARTRT_EINVAL, "cf_batch_over_dev: null buffer");
-  return guarded([&] {
-    cf_run_dev(*e, d_prof, nwalkers, kind, d_band, d_full, d_ok, stream ? (hipStream_t)stream : e->stream, d_over);
-    return BARTRT_OK;
-  });
+  return cf_call("cf_batch_over_dev", cf_profiles(d_prof, nwalkers, d_over, kind, d_band, d_full, d_ok, false, stream));
 }
 
 int bartrt_cf_partials_dev(const double *d_prof, int nwalkers, int kind, const double *d_over, double *d_part,
                            double *d_full, unsigned char *d_ok, void *stream) {
-  NEED_ENGINE();
-  Engine *e = g_eng;
-  if (int rc = cf_check_kind(e, kind, "cf_partials_dev", true)) return rc;
-  if (!d_prof || !d_part || nwalkers < 0) return fail(BARTRT_EINVAL, "cf_partials_dev: null buffer");
-  return guarded([&] {
-    cf_partials_dev(*e, d_prof, nwalkers, kind, d_over, d_part, d_full, d_ok, stream ? (hipStream_t)stream : e->stream);
-    return BARTRT_OK;
-  });
+  CfRequest rq = cf_profiles(d_prof, nwalkers, d_over, kind, d_part, d_full, d_ok, false, stream);
+  rq.partials = true;   // (this block's sums, no collective: served on a sharded engine without a communicator too)
+  return cf_call("cf_partials_dev", rq);
 }
 
+// (not a request: the ranks' slots in, no walker runs; the engine limits and the setup as above)
 int bartrt_cf_combine_dev(const double *d_slots, int nranks, int nwalkers, const unsigned char *d_ok, double *d_band,
                           void *stream) {
   NEED_ENGINE();
@@ -819,43 +823,18 @@ int bartrt_cf_combine_dev(const double *d_slots, int nranks, int nwalkers, const
   if (cf_nfilters(*e) == 0) return fail(BARTRT_EINVAL, "cf_combine_dev: call bartrt_cf_setup first");
   if (!d_slots || !d_band || nwalkers < 0) return fail(BARTRT_EINVAL, "cf_combine_dev: null buffer");
   return guarded([&] {
-    cf_combine_dev(*e, d_slots, nranks, nwalkers, d_ok, d_band, stream ? (hipStream_t)stream : e->stream);
+    cf_combine_dev(*e, d_slots, nranks, nwalkers, d_ok, d_band, stream_of(stream));
     return BARTRT_OK;
   });
-}
-
-// the parameter front end: the engine limits of cf_batch, then the step's setup and parameter count
-static int cf_check_params(const Engine *e, int kind, int npars, const char *who) {
-  if (int rc = cf_unsupported(e, who)) return rc;
-  if (!e->step) return fail(BARTRT_EINVAL, std::string(who) + ": call bartrt_step_setup first");
-  if (int rc = cf_check_kind(e, kind, who)) return rc;
-  if (npars != step_npars(*e))
-    return fail(BARTRT_EINVAL, std::string(who) + ": npars must be nPT + (radius, cloud top, scattering parameters "
-                                                  "declared with step_set_extras) + nmolfit");
-  return BARTRT_OK;
 }
 
 int bartrt_cf_params(const double *params, int nwalkers, int npars, int kind, double *band, double *full, int *status) {
-  NEED_ENGINE();
-  Engine *e = g_eng;
-  if (int rc = cf_check_params(e, kind, npars, "cf_params")) return rc;
-  if (!params || !band || nwalkers < 0) return fail(BARTRT_EINVAL, "cf_params: null buffer");
-  return guarded([&] {
-    cf_params_host(*e, params, nwalkers, npars, kind, band, full, status);
-    return BARTRT_OK;
-  });
+  return cf_call("cf_params", cf_params(params, nwalkers, npars, kind, band, full, status, true, nullptr));
 }
 
 int bartrt_cf_params_dev(const double *d_params, int nwalkers, int npars, int kind, double *d_band, double *d_full,
                          int *d_status, void *stream) {
-  NEED_ENGINE();
-  Engine *e = g_eng;
-  if (int rc = cf_check_params(e, kind, npars, "cf_params_dev")) return rc;
-  if (!d_params || !d_band || nwalkers < 0) return fail(BARTRT_EINVAL, "cf_params_dev: null buffer");
-  return guarded([&] {
-    cf_params_dev(*e, d_params, nwalkers, npars, kind, d_band, d_full, d_status, stream ? (hipStream_t)stream : e->stream);
-    return BARTRT_OK;
-  });
+  return cf_call("cf_params_dev", cf_params(d_params, nwalkers, npars, kind, d_band, d_full, d_status, false, stream));
 }
 
 // ---- per-step converters (step.hip) ------------------------------------
@@ -887,7 +866,7 @@ int bartrt_step_profiles_dev(const double *d_params, int nwalkers, int npars,
   if (!g_eng->step) return fail(BARTRT_EINVAL, "step_profiles: call bartrt_step_setup first");
   if (!d_params || !d_prof || !d_status) return fail(BARTRT_EINVAL, "step_profiles: null buffer");
   return guarded([&] {
-    hipStream_t st = stream ? (hipStream_t)stream : g_eng->stream;
+    hipStream_t st = stream_of(stream);
     step_profiles_dev(*g_eng, d_params, nwalkers, npars, d_prof, d_status, st);
     return BARTRT_OK;
   });
@@ -899,7 +878,7 @@ int bartrt_step_bandflux_dev(const double *d_spec_full, int nwalkers, int *d_sta
   if (!g_eng->step) return fail(BARTRT_EINVAL, "step_bandflux: call bartrt_step_setup first");
   if (!d_spec_full || !d_bandflux || !d_status) return fail(BARTRT_EINVAL, "step_bandflux: null buffer");
   return guarded([&] {
-    hipStream_t st = stream ? (hipStream_t)stream : g_eng->stream;
+    hipStream_t st = stream_of(stream);
     step_bandflux_dev(*g_eng, d_spec_full, nwalkers, d_status, d_bandflux, st);
     return BARTRT_OK;
   });
@@ -911,7 +890,7 @@ int bartrt_step_batch_dev(const double *d_params, int nwalkers, int npars,
   NEED_ENGINE();
   if (!g_eng->step) return fail(BARTRT_EINVAL, "step_batch: call bartrt_step_setup first");
   return guarded([&] {
-    hipStream_t st = stream ? (hipStream_t)stream : g_eng->stream;
+    hipStream_t st = stream_of(stream);
     step_run_dev(*g_eng, d_params, nwalkers, npars, d_bandflux, d_status, d_spec, st);
     return BARTRT_OK;
   });
@@ -1015,7 +994,7 @@ int bartrt_step_bandflux_blocks_dev(const double *d_blocks, int nranks, int nwal
   if (!d_blocks || !d_bandflux || !d_status || nwalkers < 0)
     return fail(BARTRT_EINVAL, "step_bandflux_blocks: null buffer");
   return guarded([&] {
-    hipStream_t st = stream ? (hipStream_t)stream : g_eng->stream;
+    hipStream_t st = stream_of(stream);
     step_bandflux_blocks_dev(*g_eng, d_blocks, nranks, nwalkers, d_status, d_bandflux, st);
     return BARTRT_OK;
   });

@@ -28,6 +28,10 @@
 // reference radius, cloud top and Rayleigh value (PrepArgs::over, the per-step path's mechanism); from parameter
 // vectors the step's converter (step_convert_dev) writes profiles, statuses and those overrides into this module's
 // workspaces first.  The CF kernels themselves do not know: they read records, chord tables and deck layers.
+// Host half: every batch call of the C ABI is one CfRequest (contrib.hpp) -- profiles or parameter rows in, overrides,
+// band rows or this block's sums out, host or device buffers -- and cf_run holds the module's one chunk loop: stage in,
+// convert, run_sums / run_chunk on the chunk's view of the request (CfChunk), stage out.  capi.hip validates a request
+// (kind, setup, step setup) before it gets here; nothing below repeats that.
 // Every sum has a fixed order and no atomics: the bits do not depend on the batch a walker is in.  Not part of the
 // per-step hot path: no kernel table, no run-time instantiation; molecule and CIA counts are run-time parameters.
 #include "comm.hpp"
@@ -291,7 +295,8 @@ size_t workspace_cap() {
   return c && *c ? std::max<size_t>(1, std::strtoull(c, nullptr, 10)) : (size_t)256 << 20;
 }
 
-size_t per_walker_bytes(const Engine &e, bool over = false, bool params = false) {
+// (over: the chunk holds per-walker overrides; params: and the converter's profiles and statuses)
+size_t per_walker_bytes(const Engine &e, bool over, bool params) {
   const CfState &g = *e.cf;
   // (nothing here depends on the engine's block: ranks that make the same call cut it into the same chunks)
   size_t b = sizeof(double) * ((size_t)g.nent_bound + g.nf) * e.L + sizeof(double) * (size_t)e.L * coef_stride(e.M, e.C) +
@@ -308,7 +313,7 @@ void claim(CfState &g, hipStream_t st) {
   g.last_stream = st;
 }
 
-void ensure_cap(const Engine &e, int n, bool over = false, bool params = false) {
+void ensure_cap(const Engine &e, int n, bool over, bool params) {
   CfState &g = *e.cf;
   over = over || params;
   if (n <= g.cap && (!over || n <= g.cap_over) && (!params || n <= g.cap_par)) return;
@@ -334,76 +339,71 @@ void ensure_cap(const Engine &e, int n, bool over = false, bool params = false) 
   }
 }
 
-void check_ready(const Engine &e, int kind) {
-  if (kind != kCfContrib && kind != kCfTransmit) throw std::invalid_argument("cf: kind must be BARTRT_CF_CONTRIB or BARTRT_CF_TRANSMIT");
-  if (!e.cf) throw std::invalid_argument("cf: call bartrt_cf_setup first");
-}
+// One chunk of a request as the kernels see it: m walkers, every pointer the device's and already at the chunk.
+struct CfChunk {
+  int m, kind;
+  const double *prof;     // [m][(S+1) L]
+  const double *over;     // [m][3] in prep_profiles' units (cm, barye, Rayleigh value; NaN: the engine's), or null
+  bool check_radius;      // the radii in `over` are checked on the device (cf_mask); false: the host has refused bad ones
+  const int *status;      // [m] the converter's verdicts, or null: a rejected sample's flag is cleared
+  double *out;            // [m][nf][L] band rows (run_chunk)
+  double *full;           // [m][W][L] or null
+  unsigned char *ok;      // [m] flags, never null
+  hipStream_t st;
+};
 
+// the CF kernel of this engine's geometry and rule, with the dynamic LDS it needs (above 64 kB: asked for first)
 template <class K>
-void allow_lds(K kernel, size_t bytes) {
-  if (bytes > 160 * 1024) throw std::invalid_argument("cf: the column's layer records and sums do not fit in LDS (160 kB)");
-  if (bytes > 64 * 1024)
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+void launch_cf(K kernel, size_t lds, int nblocks, hipStream_t st, const CfArgs &a) {
+  if (lds > 160 * 1024) throw std::invalid_argument("cf: the column's layer records and sums do not fit in LDS (160 kB)");
+  if (lds > 64 * 1024)
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(64), lds, st, a);
 }
 
-// one chunk up to this engine's band sums d_sums [m][nf][L] (cf_block_sums): m walkers whose flags go to okp.
-// d_over (optional): the walkers' overrides in prep_profiles' units, their radii checked on the device if
-// check_radius (the host-buffer call has checked them already); d_status (optional): the converter's verdicts -- a
-// rejected sample's flag is cleared
-void run_sums(Engine &e, const double *d_prof, int m, int kind, double *d_sums, double *d_full, unsigned char *okp,
-              hipStream_t st, const double *d_over = nullptr, const int *d_status = nullptr, bool check_radius = false) {
+// one chunk up to this engine's band sums d_sums [m][nf][L] (cf_block_sums, not divided)
+void run_sums(Engine &e, const CfChunk &c, double *d_sums) {
   const CfState &g = *e.cf;
+  const int m = c.m;
+  hipStream_t st = c.st;
   // the layer records under the engine's settings, as run_transit_batch builds them, into this module's buffers
   // (no radii output, only the caller's own per-walker overrides: the engine's own state is left as it was)
-  PrepArgs pa = e.prep_args(RunRequest(d_prof, m, nullptr, okp, st), g.rec);
+  PrepArgs pa = e.prep_args(RunRequest(c.prof, m, nullptr, c.ok, st), g.rec);
   pa.rad_out = nullptr;
-  pa.over = d_over;
+  pa.over = c.over;
   pa.rtop = e.solution == 1 ? g.d_rtop.get() : nullptr;
   pa.ds = e.solution == 1 ? g.d_ds.get() : nullptr;
   HIPCHK(launch_prep(pa, st));
   // (transit: the radii the preparation wrote are the walker's own -- hydrostatic from ITS reference radius -- and so
   // is the chord table filled from them)
   if (e.solution == 1) HIPCHK(launch_chord_table(pa, st));
-  if (d_status || (d_over && check_radius)) {
-    hipLaunchKernelGGL(cf_mask, dim3((m + 255) / 256), dim3(256), 0, st, d_status, check_radius ? d_over : nullptr, okp, m);
+  const double *radii = c.check_radius ? c.over : nullptr;
+  if (c.status || radii) {
+    hipLaunchKernelGGL(cf_mask, dim3((m + 255) / 256), dim3(256), 0, st, c.status, radii, c.ok, m);
     HIPCHK(hipGetLastError());
   }
 
   CfArgs a{};
-  a.L = e.L; a.M = e.M; a.C = e.C; a.W = e.W(); a.nwalkers = m; a.ntiles = g.ntiles; a.kind = kind; a.nent = g.nent;
+  a.L = e.L; a.M = e.M; a.C = e.C; a.W = e.W(); a.nwalkers = m; a.ntiles = g.ntiles; a.kind = c.kind; a.nent = g.nent;
   a.kappa = e.rt.kappa; a.cia = e.rt.cia; a.wn = e.rt.wn;
   a.coef = g.rec.coef; a.idx = g.rec.idx; a.kstop = g.rec.kstop;
   a.rdlp = g.d_rdlp;
   a.rtop = g.d_rtop; a.ds = g.d_ds;
   a.tile_ptr = g.d_tile_ptr; a.wt = g.d_wt;
-  a.part = g.d_part; a.full = d_full;
+  a.part = g.d_part; a.full = c.full;
   const int nblocks = (g.ntiles + 7) / 8 * 8 * m;
   const size_t L = e.L, NC = coef_stride(e.M, e.C), NI = idx_stride(e.C), blk = (size_t)kCfRows * kCfPitch;
   if (e.solution == 1) {
     const size_t with = sizeof(double) * (L * NC + L * NI + L * 64 + blk), without = sizeof(double) * (L * 64 + blk);
-    if (with <= 160 * 1024) {
-      allow_lds(cf_transit<true>, with);
-      hipLaunchKernelGGL(cf_transit<true>, dim3(nblocks), dim3(64), with, st, a);
-    } else {
-      allow_lds(cf_transit<false>, without);
-      hipLaunchKernelGGL(cf_transit<false>, dim3(nblocks), dim3(64), without, st, a);
-    }
+    if (with <= 160 * 1024) launch_cf(cf_transit<true>, with, nblocks, st, a);
+    else launch_cf(cf_transit<false>, without, nblocks, st, a);
   } else {
     const size_t base = sizeof(double) * (L * NC + L * NI + blk);
     const size_t simp = base + sizeof(double) * simpson_lds_doubles(e.L);
     switch (e.integ) {
-      case kIntegTransmittance:
-        allow_lds(cf_eclipse<kIntegTransmittance>, base);
-        hipLaunchKernelGGL(cf_eclipse<kIntegTransmittance>, dim3(nblocks), dim3(64), base, st, a);
-        break;
-      case kIntegSimpson:
-        allow_lds(cf_eclipse<kIntegSimpson>, simp);
-        hipLaunchKernelGGL(cf_eclipse<kIntegSimpson>, dim3(nblocks), dim3(64), simp, st, a);
-        break;
-      default:
-        allow_lds(cf_eclipse<kIntegTrapzTau>, base);
-        hipLaunchKernelGGL(cf_eclipse<kIntegTrapzTau>, dim3(nblocks), dim3(64), base, st, a);
-        break;
+      case kIntegTransmittance: launch_cf(cf_eclipse<kIntegTransmittance>, base, nblocks, st, a); break;
+      case kIntegSimpson: launch_cf(cf_eclipse<kIntegSimpson>, simp, nblocks, st, a); break;
+      default: launch_cf(cf_eclipse<kIntegTrapzTau>, base, nblocks, st, a); break;
     }
   }
   HIPCHK(hipGetLastError());
@@ -423,23 +423,24 @@ void combine(const Engine &e, const double *d_slots, int nranks, size_t slot, in
 }
 
 // one chunk, band rows out.  With a communicator: the sums go into this rank's slot of its receive buffer, one
-// in-place all-gather on st (every rank makes the same call: m is the same everywhere), the slots combined in rank
+// in-place all-gather on c.st (every rank makes the same call: m is the same everywhere), the slots combined in rank
 // order.  Without one the engine holds the whole grid and its sums are the only slot.
-void run_chunk(Engine &e, const double *d_prof, int m, int kind, double *d_band, double *d_full, unsigned char *okp,
-               hipStream_t st, const double *d_over = nullptr, const int *d_status = nullptr, bool check_radius = false) {
+void run_chunk(Engine &e, const CfChunk &c) {
   const CfState &g = *e.cf;
-  const size_t count = (size_t)m * g.nf * e.L;
-  if (Comm *c = e.comm) {
-    double *recv = comm_recv(*c, count * c->nranks);
-    run_sums(e, d_prof, m, kind, recv + (size_t)c->rank * count, d_full, okp, st, d_over, d_status, check_radius);
-    comm_allgather_inplace(*c, recv, count, st);
-    e.ncollectives++;
-    combine(e, recv, c->nranks, count, m, okp, d_band, st);
+  const size_t count = (size_t)c.m * g.nf * e.L;
+  if (Comm *cm = e.comm) {
+    double *recv = comm_recv(*cm, count * cm->nranks);
+    run_sums(e, c, recv + (size_t)cm->rank * count);
+    comm_allgather_inplace(*cm, recv, count, c.st);
+    e.ncollectives++;   // (one per chunk: bartrt_get_comm reports it)
+    combine(e, recv, cm->nranks, count, c.m, c.ok, c.out, c.st);
     return;
   }
+  // The backstop: capi.hip answers the combining calls on a sharded engine without a communicator with BARTRT_ENOTSUP
+  // before they get here; rq.partials (run_sums alone) is served on such an engine.
   if (e.lo != 0 || e.hi != e.Wfull) throw std::invalid_argument("cf: a sharded engine needs a communicator (bartrt_comm_init)");
-  run_sums(e, d_prof, m, kind, g.d_sums, d_full, okp, st, d_over, d_status, check_radius);
-  combine(e, g.d_sums, 1, count, m, okp, d_band, st);
+  run_sums(e, c, g.d_sums);
+  combine(e, g.d_sums, 1, count, c.m, c.ok, c.out, c.st);
 }
 
 // samples per row of `full` as the chunk size counts them: the largest block under a communicator (the same on
@@ -515,85 +516,16 @@ void cf_setup(Engine &e, int nf, const int *idx0, const int *npts, const double 
 
 int cf_nfilters(const Engine &e) { return e.cf ? e.cf->nf : 0; }
 
-namespace {
-
-// the caller's overrides of walkers [0, m) (device, public units) -> g.d_over
-const double *convert_over(CfState &g, const double *d_over, int m, hipStream_t st) {
-  hipLaunchKernelGGL(cf_over_units, dim3((3 * m + 255) / 256), dim3(256), 0, st, d_over, g.d_over.get(), 3 * m);
-  HIPCHK(hipGetLastError());
-  return g.d_over;
-}
-
-int chunk_of(size_t n, size_t per) { return (int)std::max<size_t>(1, std::min<size_t>(n, workspace_cap() / per)); }
-
-}  // namespace
-
-void cf_run_dev(Engine &e, const double *d_prof, int n, int kind, double *d_band, double *d_full, unsigned char *d_ok,
-                hipStream_t st, const double *d_over) {
-  check_ready(e, kind);
-  if (n <= 0) return;
-  CfState &g = *e.cf;
-  const int nprof = (e.S + 1) * e.L;
-  const int chunk = chunk_of((size_t)n, per_walker_bytes(e, d_over != nullptr));
-  ensure_cap(e, chunk, d_over != nullptr);
-  claim(g, st);
-  for (int off = 0; off < n; off += chunk) {
-    const int m = std::min(chunk, n - off);
-    const double *ov = d_over ? convert_over(g, d_over + (size_t)3 * off, m, st) : nullptr;
-    run_chunk(e, d_prof + (size_t)off * nprof, m, kind, d_band + (size_t)off * g.nf * e.L,
-              d_full ? d_full + (size_t)off * e.W() * e.L : nullptr, d_ok ? d_ok + off : g.rec.ok.get(), st, ov, nullptr,
-              true);
-  }
-}
-
-void cf_partials_dev(Engine &e, const double *d_prof, int n, int kind, const double *d_over, double *d_part,
-                     double *d_full, unsigned char *d_ok, hipStream_t st) {
-  check_ready(e, kind);
-  if (n <= 0) return;
-  CfState &g = *e.cf;
-  const int nprof = (e.S + 1) * e.L;
-  const int chunk = chunk_of((size_t)n, per_walker_bytes(e, d_over != nullptr));
-  ensure_cap(e, chunk, d_over != nullptr);
-  claim(g, st);
-  for (int off = 0; off < n; off += chunk) {
-    const int m = std::min(chunk, n - off);
-    const double *ov = d_over ? convert_over(g, d_over + (size_t)3 * off, m, st) : nullptr;
-    run_sums(e, d_prof + (size_t)off * nprof, m, kind, d_part + (size_t)off * g.nf * e.L,
-             d_full ? d_full + (size_t)off * e.W() * e.L : nullptr, d_ok ? d_ok + off : g.rec.ok.get(), st, ov, nullptr,
-             true);
-  }
-}
-
 void cf_combine_dev(Engine &e, const double *d_slots, int nranks, int n, const unsigned char *d_ok, double *d_band,
                     hipStream_t st) {
-  if (!e.cf) throw std::invalid_argument("cf: call bartrt_cf_setup first");
   if (nranks < 1 || nranks > e.Wfull) throw std::invalid_argument("cf_combine: nranks must lie in [1, the grid's sample count]");
   if (n <= 0) return;
   combine(e, d_slots, nranks, (size_t)n * e.cf->nf * e.L, n, d_ok, d_band, st);
 }
 
-void cf_params_dev(Engine &e, const double *d_params, int n, int npars, int kind, double *d_band, double *d_full,
-                   int *d_status, hipStream_t st) {
-  check_ready(e, kind);
-  if (!e.step) throw std::invalid_argument("cf: call bartrt_step_setup first");
-  if (n <= 0) return;
-  CfState &g = *e.cf;
-  const int chunk = chunk_of((size_t)n, per_walker_bytes(e, true, true));
-  ensure_cap(e, chunk, true, true);
-  claim(g, st);
-  for (int off = 0; off < n; off += chunk) {
-    const int m = std::min(chunk, n - off);
-    int *status = d_status ? d_status + off : g.d_status.get();
-    step_convert_dev(e, d_params + (size_t)off * npars, m, npars, g.d_prof, status, g.d_over, st);
-    run_chunk(e, g.d_prof, m, kind, d_band + (size_t)off * g.nf * e.L,
-              d_full ? d_full + (size_t)off * e.W() * e.L : nullptr, g.rec.ok, st, g.d_over, status, true);
-  }
-}
-
 namespace {
 
-// The host-buffer calls stage their rows chunk by chunk in one allocation: consecutive arrays of `chunk` rows each.
-// The staging buffers and the workspaces of a chunk share the cap.
+// Host buffers are staged chunk by chunk in one allocation: consecutive arrays of `chunk` rows each.
 struct Staging {
   char *base = nullptr;
   size_t at = 0;
@@ -605,95 +537,113 @@ struct Staging {
   }
 };
 
-Staging stage_for(Engine &e, int n, size_t row_bytes, bool over, bool params) {
-  CfState &g = *e.cf;
-  Staging s;
-  s.chunk = chunk_of((size_t)n, per_walker_bytes(e, over, params) + row_bytes);
-  ensure_cap(e, s.chunk, over, params);
-  const size_t need = (size_t)s.chunk * row_bytes;
-  if (need > g.d_stage.count()) {
-    HIPCHK(hipDeviceSynchronize());
-    g.d_stage.reserve(need);
-  }
-  claim(g, e.stream);
-  s.base = g.d_stage;
-  return s;
-}
-
-// the setters' own conversions (capi.hip), on the host: km -> cm, log10 bar -> barye; NaN stays NaN
-void over_units(const double *in, double *out, size_t n) {
-  for (size_t w = 0; w < n; w++) {
-    out[3 * w] = in[3 * w] * 1e5;
-    out[3 * w + 1] = std::pow(10.0, in[3 * w + 1]) * 1e6;
-    out[3 * w + 2] = in[3 * w + 2];
-  }
-}
-
 }  // namespace
 
-void cf_run_host(Engine &e, const double *prof, int n, int kind, double *band, double *full, unsigned char *ok,
-                 const double *over) {
-  check_ready(e, kind);
+void cf_run(Engine &e, const CfRequest &rq) {
+  const int n = rq.n;
   if (n <= 0) return;
-  if (over)
-    for (int w = 0; w < n; w++) {   // (as bartrt_set_radius)
-      const double r = over[3 * (size_t)w];
+  const bool host = rq.host, params = rq.from_params, over = rq.over && !params;
+  // Host-buffer profile calls refuse a bad radius as bartrt_set_radius does, naming the walker, before any launch;
+  // device buffers cannot be read here: cf_mask flags such a walker instead.
+  if (host && over)
+    for (int w = 0; w < n; w++) {
+      const double r = rq.over[3 * (size_t)w];
       if (r == r && !(r > 0 && r < 1e295))
         throw std::invalid_argument("cf: walker " + std::to_string(w) + "'s radius must be positive");
     }
   CfState &g = *e.cf;
-  const size_t nprof = (size_t)(e.S + 1) * e.L;
-  const size_t bprof = sizeof(double) * nprof, bband = sizeof(double) * (size_t)g.nf * e.L,
-               bfull = full ? sizeof(double) * (size_t)e.W() * e.L : 0,
-               bfull_max = full ? sizeof(double) * full_rows(e) * e.L : 0;
-  Staging s = stage_for(e, n, bprof + bband + bfull_max + 1, over != nullptr, false);
-  double *dp = s.take<double>(bprof), *db = s.take<double>(bband), *df = full ? s.take<double>(bfull_max) : nullptr;
-  unsigned char *dok = s.take<unsigned char>(1);
-  hipStream_t st = e.stream;
-  std::vector<unsigned char> hok(s.chunk);
-  std::vector<double> hov(over ? (size_t)3 * s.chunk : 0);
-  for (int off = 0; off < n; off += s.chunk) {
-    const int m = std::min(s.chunk, n - off);
-    HIPCHK(hipMemcpyAsync(dp, prof + (size_t)off * nprof, bprof * m, hipMemcpyHostToDevice, st));
-    if (over) {
-      // converted here with the setters' arithmetic, so a walker's deck is the layer the setter would give it
-      over_units(over + (size_t)3 * off, hov.data(), (size_t)m);
-      HIPCHK(hipMemcpyAsync(g.d_over, hov.data(), sizeof(double) * 3 * m, hipMemcpyHostToDevice, st));
+  hipStream_t st = host ? e.stream : rq.stream;
+  const size_t nin = params ? (size_t)rq.npars : (size_t)(e.S + 1) * e.L, nband = (size_t)g.nf * e.L,
+               nfull = (size_t)e.W() * e.L;
+  // Chunk size: what the cap leaves for a walker's workspaces plus, for host buffers, its staged rows -- input, band
+  // row, `full` counted at the LARGEST block's samples under a communicator (full_rows), the flag or status.  Nothing
+  // in it depends on this engine's block, so ranks that make the same call cut it identically and issue the same
+  // number of collectives (one per chunk).
+  const size_t bin = sizeof(double) * nin, bband = sizeof(double) * nband,
+               bfull_max = rq.full ? sizeof(double) * full_rows(e) * e.L : 0, bflag = params ? sizeof(int) : 1,
+               brow = host ? bin + bband + bfull_max + bflag : 0;
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>(n, workspace_cap() / (per_walker_bytes(e, over, params) + brow)));
+  // Order kept: the workspaces grow (a device-wide synchronize if they do: an earlier launch on any stream may still
+  // use the old ones), then the staging buffer likewise, then the stream claims them.  Workspaces that fit stay, also
+  // across a cf_setup with equal entry and filter counts.
+  ensure_cap(e, chunk, over, params);
+  Staging s;
+  s.chunk = chunk;
+  if (host && (size_t)chunk * brow > g.d_stage.count()) {
+    HIPCHK(hipDeviceSynchronize());
+    g.d_stage.reserve((size_t)chunk * brow);
+  }
+  claim(g, st);
+  s.base = g.d_stage;
+  double *din = nullptr, *dband = nullptr, *dfull = nullptr;
+  unsigned char *dok = nullptr;
+  int *dstatus = nullptr;
+  std::vector<unsigned char> hok;
+  std::vector<double> hov;
+  if (host) {
+    din = s.take<double>(bin);
+    dband = s.take<double>(bband);
+    if (rq.full) dfull = s.take<double>(bfull_max);
+    if (params) dstatus = s.take<int>(sizeof(int));
+    else dok = s.take<unsigned char>(1);
+    hok.resize(params ? 0 : chunk);
+    hov.resize(over ? (size_t)3 * chunk : 0);
+  }
+  // the module's one chunk loop
+  for (int off = 0; off < n; off += chunk) {
+    const int m = std::min(chunk, n - off);
+    const double *in = rq.in + (size_t)off * nin;
+    if (host) {
+      HIPCHK(hipMemcpyAsync(din, in, bin * m, hipMemcpyHostToDevice, st));
+      in = din;
     }
-    run_chunk(e, dp, m, kind, db, df, dok, st, over ? g.d_over.get() : nullptr);
-    HIPCHK(hipMemcpyAsync(band + (size_t)off * g.nf * e.L, db, bband * m, hipMemcpyDeviceToHost, st));
-    if (full) HIPCHK(hipMemcpyAsync(full + (size_t)off * e.W() * e.L, df, bfull * m, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(hok.data(), dok, (size_t)m, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));   // (hov and hok are free again)
-    if (ok) std::copy(hok.begin(), hok.begin() + m, ok + off);
+    CfChunk c{};
+    c.m = m; c.kind = rq.kind; c.st = st;
+    c.out = host ? dband : rq.out + (size_t)off * nband;
+    c.full = !rq.full ? nullptr : host ? dfull : rq.full + (size_t)off * nfull;
+    if (params) {
+      // the converter's overrides are in the preparation's units as written; cf_mask clears a rejected sample's flag
+      // (and checks the radius): the sample is reported through status, never an error
+      int *status = host ? dstatus : rq.status ? rq.status + off : g.d_status.get();
+      step_convert_dev(e, in, m, rq.npars, g.d_prof, status, g.d_over, st);
+      c.prof = g.d_prof; c.over = g.d_over; c.status = status; c.ok = g.rec.ok; c.check_radius = true;
+    } else {
+      c.prof = in;
+      c.ok = host ? dok : rq.ok ? rq.ok + off : g.rec.ok.get();
+      c.check_radius = !host;
+      if (over && host) {
+        // converted here with the setters' own arithmetic (capi.hip: km -> cm, log10 bar -> barye; NaN stays NaN),
+        // so a walker's deck is the layer the setter would give it
+        for (int w = 0; w < m; w++) {
+          const double *o = rq.over + 3 * (size_t)(off + w);
+          hov[3 * w] = o[0] * 1e5;
+          hov[3 * w + 1] = std::pow(10.0, o[1]) * 1e6;
+          hov[3 * w + 2] = o[2];
+        }
+        HIPCHK(hipMemcpyAsync(g.d_over, hov.data(), sizeof(double) * 3 * m, hipMemcpyHostToDevice, st));
+        c.over = g.d_over;
+      } else if (over) {
+        // converted on the device (cf_over_units: the device's pow); cf_mask flags a bad radius
+        hipLaunchKernelGGL(cf_over_units, dim3((3 * m + 255) / 256), dim3(256), 0, st, rq.over + (size_t)3 * off,
+                           g.d_over.get(), 3 * m);
+        HIPCHK(hipGetLastError());
+        c.over = g.d_over;
+      }
+    }
+    if (rq.partials) run_sums(e, c, c.out);
+    else run_chunk(e, c);
+    if (!host) continue;
+    HIPCHK(hipMemcpyAsync(rq.out + (size_t)off * nband, dband, bband * m, hipMemcpyDeviceToHost, st));
+    if (rq.full) HIPCHK(hipMemcpyAsync(rq.full + (size_t)off * nfull, dfull, sizeof(double) * nfull * m, hipMemcpyDeviceToHost, st));
+    if (params && rq.status) HIPCHK(hipMemcpyAsync(rq.status + off, dstatus, sizeof(int) * m, hipMemcpyDeviceToHost, st));
+    if (!params) HIPCHK(hipMemcpyAsync(hok.data(), dok, (size_t)m, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));   // (the one wait per chunk: the staging rows, hov and hok are free again)
+    if (params) continue;
+    // a profile call without `ok` fails on a flagged profile
+    if (rq.ok) std::copy(hok.begin(), hok.begin() + m, rq.ok + off);
     else
       for (int w = 0; w < m; w++)
         if (!hok[w]) throw std::invalid_argument("cf: profile " + std::to_string(off + w) + " holds a non-finite or non-positive temperature");
-  }
-}
-
-void cf_params_host(Engine &e, const double *params, int n, int npars, int kind, double *band, double *full,
-                    int *status) {
-  check_ready(e, kind);
-  if (!e.step) throw std::invalid_argument("cf: call bartrt_step_setup first");
-  if (n <= 0) return;
-  CfState &g = *e.cf;
-  const size_t bpar = sizeof(double) * (size_t)npars, bband = sizeof(double) * (size_t)g.nf * e.L,
-               bfull = full ? sizeof(double) * (size_t)e.W() * e.L : 0,
-               bfull_max = full ? sizeof(double) * full_rows(e) * e.L : 0;
-  Staging s = stage_for(e, n, bpar + bband + bfull_max + sizeof(int), true, true);
-  double *dp = s.take<double>(bpar), *db = s.take<double>(bband), *df = full ? s.take<double>(bfull_max) : nullptr;
-  int *dst = s.take<int>(sizeof(int));
-  hipStream_t st = e.stream;
-  for (int off = 0; off < n; off += s.chunk) {
-    const int m = std::min(s.chunk, n - off);
-    HIPCHK(hipMemcpyAsync(dp, params + (size_t)off * npars, bpar * m, hipMemcpyHostToDevice, st));
-    step_convert_dev(e, dp, m, npars, g.d_prof, dst, g.d_over, st);
-    run_chunk(e, g.d_prof, m, kind, db, df, g.rec.ok, st, g.d_over, dst, true);
-    HIPCHK(hipMemcpyAsync(band + (size_t)off * g.nf * e.L, db, bband * m, hipMemcpyDeviceToHost, st));
-    if (full) HIPCHK(hipMemcpyAsync(full + (size_t)off * e.W() * e.L, df, bfull * m, hipMemcpyDeviceToHost, st));
-    if (status) HIPCHK(hipMemcpyAsync(status + off, dst, sizeof(int) * m, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));   // (a rejected sample is reported, not an error)
   }
 }
 

@@ -15,40 +15,43 @@ enum { kCfContrib = 0, kCfTransmit = 1 };
 // a sample in the block has no entries.  Replaces an earlier setup.  Throws on bad windows.
 void cf_setup(Engine &e, int nfilters, const int *idx0, const int *npts, const double *resp);
 int cf_nfilters(const Engine &e);
-// The two halves of a call, for a caller that runs its own collective (and for one GPU standing in for any rank
-// count).  cf_partials_dev: this engine's band sums d_part [n][nfilters][L] -- layers from the top, entries added in
-// tile order, not divided -- with d_full [n][W][L] of its own block, d_ok and d_over as cf_run_dev.  cf_combine_dev:
-// d_slots = nranks slots of n * nfilters * L doubles, added in rank order, divided by trapz(resp), atm layer order
-// into d_band [n][nfilters][L]; NaN rows where d_ok (optional) is 0.  No atomics: the bits depend on nranks only.
-void cf_partials_dev(Engine &e, const double *d_prof, int n, int kind, const double *d_over, double *d_part,
-                     double *d_full, unsigned char *d_ok, hipStream_t st);
+// Everything ONE contribution-function call is asked to do (cf_run), as RunRequest is for Engine::run: it travels by
+// const reference from the entry point (capi.hip, which has validated it) into the one chunk loop; the engine keeps
+// nothing of it.  Four choices -- input, overrides, destination, buffers -- and the plain outputs.
+struct CfRequest {
+  int n = 0;                     // walkers: profiles, or parameter rows
+  int kind = kCfContrib;         // kCfContrib (eclipse geometry) or kCfTransmit
+  const double *in = nullptr;    // [n][(S+1) L] profiles, or (from_params) [n][npars] rows as step_run_dev takes them
+  bool from_params = false;      // `in` goes through the step's converter (step_convert_dev; after step_setup) first:
+  int npars = 0;                 //   T(p), abundances, the declared radius / cloud-top / Rayleigh slots as overrides
+  const double *over = nullptr;  // [n][3] or null, profile calls: each walker's radius (km), log10 cloud top (bar), Rayleigh
+                                 //   value as the setters take them; NaN in a slot = the engine-wide setting
+  double *out = nullptr;         // [n][nfilters][L]: band rows, atm layer order, divided by trapz(resp); or (partials)
+  bool partials = false;         //   this engine's own sums, layers from the top, tile order, not divided, no collective
+  double *full = nullptr;        // [n][W][L] or null: the block's own per-wavenumber values, atm layer order
+  unsigned char *ok = nullptr;   // [n] or null, profile calls: 0 for a walker the preparation (or its radius) flags
+  int *status = nullptr;         // [n] or null, parameter calls: 0, 1 (temperature), 2 (abundance) as the step reports
+  hipStream_t stream = nullptr;  // device buffers: asynchronous on it; host buffers run on the engine's own stream
+  bool host = false;             // the buffers are the host's: staged chunk by chunk, back when the call returns
+};
+// The one driver of bartrt_cf_batch / _over / _params, their _dev forms and bartrt_cf_partials_dev.  The walkers go
+// through the per-walker workspaces in chunks that stay under BARTRT_CF_WORKSPACE_BYTES; per chunk: the input (host
+// buffers: staged in; parameters: converted), the overrides, the preparation, the CF kernel, this engine's band sums,
+// and -- unless rq.partials -- the ranks' sums combined: an unsharded engine's only slot is a workspace; an engine with
+// a communicator (sharded or not) writes its slot of the receive buffer, issues ONE in-place all-gather per chunk and
+// combines the slots -- every rank makes the same call and gets the same rows.  A sharded engine without a
+// communicator serves rq.partials only (else std::invalid_argument).
+// Overrides: device buffers are converted on the device and a radius that is not positive and finite flags the walker
+// (ok = 0, NaN rows); host buffers are converted with the setters' own arithmetic and such a radius throws before any
+// launch.  Null: exactly the launches of the call without overrides.
+// Flags: the band rows of a flagged walker or a rejected sample are NaN, its rows of `full` undefined.  A host-buffer
+// profile call without `ok` throws on a flagged profile; a parameter call never fails on a rejected sample.
+void cf_run(Engine &e, const CfRequest &rq);
+// The other half of rq.partials, for a caller that runs its own collective (and for one GPU standing in for any rank
+// count): d_slots = nranks slots of n * nfilters * L doubles, added in rank order, divided by trapz(resp), atm layer
+// order into d_band [n][nfilters][L]; NaN rows where d_ok (optional) is 0.  No atomics: the bits depend on nranks only.
 void cf_combine_dev(Engine &e, const double *d_slots, int nranks, int n, const unsigned char *d_ok, double *d_band,
                     hipStream_t st);
-// The calls below combine the ranks' sums themselves: an unsharded engine's only slot is a workspace; an engine with
-// a communicator (sharded or not) writes its slot of the receive buffer, issues ONE in-place all-gather per chunk
-// and combines the slots -- every rank makes the same call and gets the same rows; d_full is the block's own
-// [n][W][L].  A sharded engine without a communicator: std::invalid_argument.
-// d_prof [n][nprof] -> d_band [n][nfilters][L] (atm layer order); d_full [n][W][L] (atm layer order)
-// or null; d_ok [n] or null (flags in the module's own workspace).  Asynchronous on st.
-// d_over [n][3] or null: each walker's own reference radius (km), log10 cloud-top pressure (bar) and Rayleigh value --
-// what bartrt_set_radius / _set_cloudtop / _set_scattering take -- NaN in a slot = the engine-wide setting
-// (prep_profiles' own sentinel, prep.hpp).  Null: exactly the launches of the call without overrides.  A radius that
-// is not positive and finite: the walker is flagged (device form) / the call throws (host form).
-void cf_run_dev(Engine &e, const double *d_prof, int n, int kind, double *d_band, double *d_full,
-                unsigned char *d_ok, hipStream_t st, const double *d_over = nullptr);
-// the same from / to host buffers (returns when the results are there); ok null: a non-finite
-// profile fails the call
-void cf_run_host(Engine &e, const double *prof, int n, int kind, double *band, double *full, unsigned char *ok,
-                 const double *over = nullptr);
-// Parameters in (after step_setup): params [n][npars] as step_run_dev takes them go through the step's converter
-// (step_convert_dev: T(p), abundances, the declared radius / cloud-top / Rayleigh slots as per-walker overrides) into
-// this module's workspaces, then through the records and kernels above.  status [n] or null: 0, 1 (temperature),
-// 2 (abundance) as the step reports them; the band rows of a rejected sample (and of a profile the preparation
-// flags) are NaN, its rows of `full` undefined.  A rejected sample does not fail the call.
-void cf_params_dev(Engine &e, const double *d_params, int n, int npars, int kind, double *d_band, double *d_full,
-                   int *d_status, hipStream_t st);
-void cf_params_host(Engine &e, const double *params, int n, int npars, int kind, double *band, double *full,
-                    int *status);
 // frees the engine's filter tables and workspaces (~Engine, an earlier setup's)
 void cf_release(Engine &e);
 

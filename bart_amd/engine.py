@@ -599,12 +599,9 @@ def _cf_batch(profiles, filters, kind, full, want_ok, over=None):
     band = np.zeros((n, nf, L))
     fout = np.zeros((n, W, L)) if full else None
     ok = np.zeros(n, np.uint8)
-    if over is None:
-        _check(trm.lib().bartrt_cf_batch(_ptr(prof), n, prof.shape[1], kind, _ptr(band),
-                                         _ptr(fout) if full else None, _ptr(ok) if want_ok else None))
-    else:
-        _check(trm.lib().bartrt_cf_batch_over(_ptr(prof), n, prof.shape[1], _ptr(_cf_over(over, n)), kind, _ptr(band),
-                                              _ptr(fout) if full else None, _ptr(ok) if want_ok else None))
+    pover = None if over is None else _ptr(_cf_over(over, n))    # (null: the plain call)
+    _check(trm.lib().bartrt_cf_batch_over(_ptr(prof), n, prof.shape[1], pover, kind, _ptr(band),
+                                          _ptr(fout) if full else None, _ptr(ok) if want_ok else None))
     return band, fout, ok
 
 
@@ -650,12 +647,10 @@ def _cf_batch_dev(d_prof, kind, full, d_ok, stream, d_over=None):
     if d_ok is not None:
         assert d_ok.is_cuda and d_ok.dtype == torch.uint8 and d_ok.numel() >= n
     vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    if d_over is None:
-        _check(trm.lib().bartrt_cf_batch_dev(vp(d_prof), n, kind, vp(band), vp(fout), vp(d_ok), _stream_ptr(stream)))
-    else:
+    if d_over is not None:
         assert d_over.is_cuda and d_over.dtype == torch.float64 and d_over.is_contiguous() and tuple(d_over.shape) == (n, 3)
-        _check(trm.lib().bartrt_cf_batch_over_dev(vp(d_prof), n, vp(d_over), kind, vp(band), vp(fout), vp(d_ok),
-                                                  _stream_ptr(stream)))
+    _check(trm.lib().bartrt_cf_batch_over_dev(vp(d_prof), n, vp(d_over), kind, vp(band), vp(fout), vp(d_ok),
+                                              _stream_ptr(stream)))
     return (band, fout) if full else band
 
 

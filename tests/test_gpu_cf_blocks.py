@@ -207,3 +207,43 @@ def test_three_blocks_against_the_oracle(cases):
             err = _rel(band[w], ref)
             print("cf blocks n=3 %s walker %d: against the oracle %.3e" % (kind, w, err))
             assert err < TOL
+
+
+def test_partials_cut_into_chunks_are_the_one_chunk_bits(cases, monkeypatch):
+    """cf_partials_dev is the one call shape no other test cuts into chunks: three walkers (walker 1 under its own
+    cloud top, the others' override rows NaN) with `full` and d_ok, once under the default workspace cap (one chunk)
+    and once under BARTRT_CF_WORKSPACE_BYTES=1 (one walker per chunk).  The sums, the per-wavenumber values and the
+    flags are the same bytes, and cf_combine_dev over that one slot is contribution_dev on the same inputs."""
+    import torch
+    from bart_amd import engine, transit_module as trm
+    case = cases(None)
+    profs = batch(case)[1][:3]
+    over = np.full((3, 3), np.nan)
+    over[1, 1] = -1.5
+    engine.init(case.tcfg)
+    try:
+        engine.cf_setup(windows(1))
+        d, dov = torch.from_numpy(profs).cuda(), torch.from_numpy(over).cuda()
+
+        def partials():
+            ok = torch.zeros(3, dtype=torch.uint8, device="cuda")
+            part, full = engine.cf_partials_dev(d, engine.CF_CONTRIB, full=True, d_ok=ok, over=dov)
+            torch.cuda.synchronize()
+            return [t.cpu().numpy() for t in (part, full, ok)], part
+
+        monkeypatch.delenv("BARTRT_CF_WORKSPACE_BYTES", raising=False)
+        one, _ = partials()
+        monkeypatch.setenv("BARTRT_CF_WORKSPACE_BYTES", "1")
+        cut, d_part = partials()
+        monkeypatch.delenv("BARTRT_CF_WORKSPACE_BYTES")
+        assert one[2].tolist() == [1, 1, 1] and np.isfinite(one[0]).all()
+        for a, b in zip(one, cut):
+            assert np.array_equal(a, b)
+        ok = torch.zeros(3, dtype=torch.uint8, device="cuda")
+        band = engine.cf_combine_dev(d_part, 1, d_ok=torch.from_numpy(cut[2]).cuda())
+        rband, rfull = engine.contribution_dev(d, full=True, d_ok=ok, over=dov)
+        torch.cuda.synchronize()
+        assert np.array_equal(band.cpu().numpy(), rband.cpu().numpy())
+        assert np.array_equal(cut[1], rfull.cpu().numpy()) and ok.cpu().numpy().tolist() == [1, 1, 1]
+    finally:
+        trm.free_memory()
