@@ -226,6 +226,7 @@ int bartrt_init(int argc, const char **argv) {
   if (argc < 1 || !argv) return fail(BARTRT_EINVAL, "bartrt_init: empty argv");
   return guarded([&] {
     teardown(svc::env_num("BARTRT_SHARE_WAIT_S", 60.0));
+    (void)slant_opt_guard();   // (a BARTRT_SLANT_OPT that is no guard is refused here, not at the first launch)
     const InitArgs ia = parse_init_args(argc, argv);
     if (ia.cfile.empty()) throw IoError{"transit_init: no '-c <configuration file>' in argv"};
     const int mode = resolve_share_mode(read_tcfg(ia.cfile), ia.no_service);
@@ -304,6 +305,23 @@ int bartrt_set_cut(int slant) {
   NEED_ENGINE();
   if (slant != 0 && slant != 1) return fail(BARTRT_EINVAL, "set_cut: 0 (vertical) or 1 (slant)");
   g_eng->cut_slant = slant != 0;
+  return BARTRT_OK;
+}
+
+int bartrt_set_slant_opt(double guard) {
+  if (!set_slant_opt_guard(guard)) return fail(BARTRT_EINVAL, "set_slant_opt: 0 (off) or a power of two 2^-10 .. 1");
+  return BARTRT_OK;
+}
+
+int bartrt_get_slant_opt(double *guard) {
+  if (!guard) return fail(BARTRT_EINVAL, "get_slant_opt: null output pointer");
+  return guarded([&] { *guard = slant_opt_guard(); return BARTRT_OK; });
+}
+
+int bartrt_parse_slant_opt(const char *text, double *guard) {
+  double g = 0.0;
+  if (!parse_slant_opt(text, &g)) return fail(BARTRT_EINVAL, "BARTRT_SLANT_OPT: an integer 0 .. 10 (0: off, n: guard 2^-n)");
+  if (guard) *guard = g;
   return BARTRT_OK;
 }
 
@@ -670,6 +688,21 @@ int bartrt_walked_end(int *walked, int cap, int *nwalkers, int *ncolumns, int *w
     if (walked && n > 0) {
       if ((size_t)cap < (size_t)n * nc) throw std::invalid_argument("walked_end: buffer too small");
       HIPCHK(hipMemcpy(walked, e->d_walked, sizeof(int) * (size_t)n * nc, hipMemcpyDeviceToHost));
+    }
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_walked_restarts(int *restarts, int cap, int *nwalkers) {
+  NEED_ENGINE();
+  return guarded([&] {
+    Engine *e = g_eng;
+    HIPCHK(hipDeviceSynchronize());
+    const int n = e->walked_nwalkers;
+    if (nwalkers) *nwalkers = n;
+    if (restarts && n > 0) {
+      if (cap < n) throw std::invalid_argument("walked_restarts: buffer too small");
+      HIPCHK(hipMemcpy(restarts, e->d_walked.get() + e->walked_restart_off, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
     }
     return BARTRT_OK;
   });

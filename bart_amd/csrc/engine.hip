@@ -857,6 +857,7 @@ RtArgs Engine::rt_args(const RunRequest &rq, const PrepArgs &pa, const Prefetch 
   r.integ = integ;
   r.cut_slant = cut_slant ? 1 : 0;
   r.toomuch = toomuch;
+  r.opt_guard = slant_opt_guard();
   if (cut_slant) slant_thresholds(r);
   r.spec = rq.spec;
   r.tau_out = (rq.want_tau && n == 1) ? d_tau.get() : nullptr;
@@ -894,14 +895,17 @@ RtArgs Engine::rt_args(const RunRequest &rq, const PrepArgs &pa, const Prefetch 
     if (rq.lbl_fused) HIPCHK(hipEventRecord(ev[ev_used], rq.stream));
     else { r.ev_start = ev[ev_used]; r.ev_stop = ev[ev_used + 1]; }
   }
-  r.walked_out = nullptr;
+  r.walked_out = r.restart_out = nullptr;
   if (want_walked && eclipse_rt) {
-    // the finest column any eclipse kernel records is ONE wavenumber wide (rt_eclipse_quad with one ray per lane, R = 8)
+    // the finest column any eclipse kernel records is ONE wavenumber wide (rt_eclipse_quad with one ray per lane, R = 8);
+    // behind the layers walked, per walker: the waves that walked their column twice (RtArgs::restart_out)
     const size_t need = (size_t)n * ((size_t)r.W + 64);
-    d_walked.reserve(need);
-    HIPCHK(hipMemsetAsync(d_walked, 0, need * sizeof(int), rq.stream));
+    d_walked.reserve(need + (size_t)n);
+    HIPCHK(hipMemsetAsync(d_walked, 0, (need + (size_t)n) * sizeof(int), rq.stream));
     r.walked_out = d_walked;
+    r.restart_out = d_walked.get() + need;
     walked_nwalkers = n;
+    walked_restart_off = need;
   }
   return r;
 }

@@ -154,6 +154,7 @@ struct Engine : EngineStream {
   bool want_walked = false;
   DevBuf<int> d_walked;
   int walked_nwalkers = 0;
+  size_t walked_restart_off = 0;   // the restarted-wave counts of the last record: d_walked + this, [walked_nwalkers]
   RtLaunchInfo walked_info{};
   // timing of RT launches
   bool timing = false;

@@ -26,6 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <stdexcept>
 #include <utility>
 
 namespace bartrt {
@@ -252,6 +253,39 @@ KernelMode rt_kernel_mode() {
     return KernelMode::kDefault;
   }();
   return mode;
+}
+bool parse_slant_opt(const char *text, double *guard) {
+  if (!text || !*text) return false;
+  char *end = nullptr;
+  const long n = std::strtol(text, &end, 10);
+  if (*end != '\0' || n < 0 || n > 10) return false;
+  if (guard) *guard = n == 0 ? 0.0 : std::ldexp(1.0, -(int)n);
+  return true;
+}
+// (< 0: the environment's value was refused and no setter call has replaced it)
+static double &slant_opt_state() {
+  static double g = [] {
+    const char *e = std::getenv("BARTRT_SLANT_OPT");
+    double v = 0.0625;   // 2^-4
+    if (e && !parse_slant_opt(e, &v)) {
+      std::fprintf(stderr, "libbartrt: BARTRT_SLANT_OPT=%s is not an integer 0 .. 10 (0: off, n: guard 2^-n); refused\n", e);
+      v = -1.0;
+    }
+    return v;
+  }();
+  return g;
+}
+double slant_opt_guard() {
+  const double g = slant_opt_state();
+  if (g < 0.0) throw std::invalid_argument("BARTRT_SLANT_OPT must be an integer 0 .. 10 (0: off, n: guard 2^-n)");
+  return g;
+}
+bool set_slant_opt_guard(double guard) {
+  int ex = 0;
+  const bool pow2 = guard > 0.0 && std::frexp(guard, &ex) == 0.5 && ex >= -9 && ex <= 1;   // 2^(ex - 1)
+  if (!(guard == 0.0 || pow2)) return false;
+  slant_opt_state() = guard;
+  return true;
 }
 static bool rt_force_window() {
   static const bool v = std::getenv("BARTRT_WINDOW") != nullptr;  // windowed addressing on any grid (tests)

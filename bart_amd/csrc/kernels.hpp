@@ -218,6 +218,9 @@ struct RtArgs {
   int integ;               // integration rule of the eclipse geometry (integ.hpp: 0 / 1 / 2)
   int cut_slant;           // `toomuch` acts on each ray's slant depth tau / mu (cfg `cut slant`): generic kernel
   double toomuch;
+  double opt_guard;        // rt_eclipse_simpson_slant's optimistic loop (rt_eclipse_s1s.hpp): whole blocks run without ray
+                           // flags while tau <= opt_guard * min(thr).  0: off; else a power of two, 2^-10 .. 1
+                           // (slant_opt_guard(): BARTRT_SLANT_OPT, bartrt_set_slant_opt).  The other kernels ignore it
   double invmu[kMaxAngles];
   double wgt[kMaxAngles];  // pi (sin^2 hi - sin^2 lo)
   double wq[kMaxAngles];   // wgt[a] * invmu[a]: the angle quadrature of rules 1 / 2 taken before the layer sum
@@ -233,6 +236,8 @@ struct RtArgs {
   int *last_out;           // optional [W]
   double *intens_out;      // optional [A][W] intensities per ray angle (single walker)
   int *walked_out;         // optional diagnostics: layers walked per (walker, column of the launched kernel)
+  int *restart_out;        // optional, with walked_out: [nw] waves of the walker that walked their column a second time
+                           // (rt_eclipse_simpson_slant; cleared by the host)
   // transit geometry
   const double *rtop, *ds;
   double inv_starrad2;
@@ -296,6 +301,13 @@ struct RtLaunchInfo {
 enum class KernelMode { kDefault, kGeneric, kMono, kMonoOcc, kMonoIlp, kSplit, kQuad, kOcto, kHexa, kR32, kAdj8, kAdj16 };
 // parsed once per process (kernels.hip); an unknown value is reported on stderr and the default choice applies
 KernelMode rt_kernel_mode();
+// RtArgs::opt_guard of the launches to come.  BARTRT_SLANT_OPT, read once per process: 0 = off, n = 1 .. 10: the guard
+// 2^-n; unset: 2^-4.  parse_slant_opt: that reading (false: not an integer 0 .. 10).  A value the environment holds
+// and parse_slant_opt refuses makes slant_opt_guard() throw std::invalid_argument until set_slant_opt_guard() names
+// a valid one: 0 or a power of two 2^-10 .. 2^0 (false: refused, nothing changes).
+bool parse_slant_opt(const char *text, double *guard);
+double slant_opt_guard();
+bool set_slant_opt_guard(double guard);
 #endif
 
 // ---------------------------------------------------------------------------

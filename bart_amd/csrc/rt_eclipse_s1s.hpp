@@ -35,6 +35,18 @@
 //  * zero-width tau panels (two adjacent layers of exactly zero extinction) make a reciprocal
 //    infinite and the lane's sums non-finite, which is sticky; a wave that ends with a non-finite
 //    flux recomputes its columns ray by ray with SlantRay (integ.hpp), case analysis and all.
+//  * flags and log exist to freeze the sums of rays that have died and to record where; on a layer where every ray
+//    of every lane is alive they compute nothing (the flags are 1.0, fma(c, 1.0, P) is c + P to the bit, no event is
+//    logged).  So the walk has TWO loops over whole blocks.  The OPTIMISTIC loop runs first, on blocks without flags
+//    and log (FLAGS = false: P += c), while the wave's largest tm stands at or below the guard g = min_a thr_a *
+//    RtArgs::opt_guard at a block's start.  After each such block the wave checks tm <= min_a thr_a on all lanes:
+//    tm is monotone, so the value at the block's end bounds every value inside it, every flag the flagged walk
+//    would have formed there was 1, and the block's state is the flagged walk's bit for bit.  When the guard fails
+//    (it stays failed) the flagged loop takes over at that block.  When the END-of-block check fails -- a ray died
+//    inside an optimistic block: tau rose by more than 1 / opt_guard within six layers -- the wave drops the column
+//    and walks it again from layer 0 with the flagged loop alone (a second copy of that code behind a forward
+//    branch at the block boundary): no saved state -- there are no registers for a snapshot -- and one partial walk
+//    lost by that wave.  opt_guard = 0: flagged loop only.
 #pragma once
 #include "integ.hpp"
 #include "kernels.hpp"
@@ -128,21 +140,35 @@ void rt_eclipse_simpson_slant(RtArgs p) {
   const double tcap = tau_cap(p, A);
   // `toomuch` ends a ray only where a deeper layer exists (nothing follows the bottom layer)
   const int kcut = kend < L - 2 ? kend : L - 2;
-  double thr_max = p.thr[0];
+  double thr_max = p.thr[0], thr_min = p.thr[0];
 #pragma unroll
-  for (int a = 1; a < A; a++) thr_max = p.thr[a] > thr_max ? p.thr[a] : thr_max;
+  for (int a = 1; a < A; a++) {
+    thr_max = p.thr[a] > thr_max ? p.thr[a] : thr_max;
+    thr_min = p.thr[a] < thr_min ? p.thr[a] : thr_min;
+  }
+  // the optimistic loop's guard (negative thresholds: negative, never met; opt_guard is 0 or a power of two <= 1)
+  const double thr_opt = thr_min * p.opt_guard;
 
   // optical depth: tau of the last even layer, the last two extinctions
-  double s_even = 0.0, eprev = 0.0, e2 = 0.0;
+  double s_even, eprev, e2;
   // the tau grid of the intensity integrals: abscissa of the previous point, the previous
   // interval and its reciprocal; tm = the largest tau so far (layers <= kcut)
-  double x1 = 0.0, h0 = 0.0, r0 = 1.0, tm = 0.0;
+  double x1, h0, r0, tm;
   [[maybe_unused]] int out_last = 0;          // OUT: the deepest layer with a living ray, its optical depth
   [[maybe_unused]] double out_tau = 0.0;
   // per ray angle: the last two integrands, the sums of the panels that end on even / odd points
   double y1[A], y2[A], P0[A], P1[A];
+  double nprev;          // rays alive when the previous layer began (a sum of the 0 / 1 flags)
+  auto init_walk = [&]() {
+    s_even = eprev = e2 = 0.0;
+    x1 = h0 = tm = 0.0;
+    r0 = 1.0;
+    out_last = 0;
+    out_tau = 0.0;
+    nprev = (double)A;
 #pragma unroll
-  for (int a = 0; a < A; a++) { y1[a] = y2[a] = P0[a] = P1[a] = 0.0; }
+    for (int a = 0; a < A; a++) { y1[a] = y2[a] = P0[a] = P1[a] = 0.0; }
+  };
   // the wave's event log: [slot 0 .. A-1][lane] (tau, interval) pairs, then [slot][lane] layer indices
   // (-1: no event in that slot), addressed through a descriptor of exactly its size
   const unsigned nth = blockDim.x;                      // 64, 128 or 256
@@ -153,7 +179,6 @@ void rt_eclipse_simpson_slant(RtArgs p) {
   const unsigned log_k0 = nth * (unsigned)A * 16u + threadIdx.x * 4u;   // this lane's index of slot 0
 #pragma unroll
   for (int sl = 0; sl < A; sl++) __builtin_amdgcn_raw_buffer_store_b32(-1, rs_log, (int)(log_k0 + sl * nth * 4u), 0, 0);
-  double nprev = (double)A;  // rays alive when the previous layer began (a sum of the 0 / 1 flags)
   const unsigned tid16 = threadIdx.x * 16u;
   // logs the event "the rays alive dropped from nprev to nnow on layer kev" (tau and interval of that layer
   // are x1 and h0 by now); lanes without one store out of range, which the hardware drops
@@ -174,10 +199,13 @@ void rt_eclipse_simpson_slant(RtArgs p) {
   // k0 = 0, MASKED = the column's last block: layers past kend are walked with clamped inputs
   // and masked; the blocks above it lie inside the column (k0 + 5 <= kcut) and carry no range
   // logic at all.
-  auto layer = [&](auto Jc, auto Fc, auto Mc, int k0, const double (&r)[NR], const double (&cf)[NC],
-                   double (&cfn)[NC]) {
+  // FLAGS = false: a layer of the optimistic loop -- every ray of every lane is taken to be alive: no flags, no
+  // event, the panels are added as they are (the caller checks tm at the block's end)
+  auto layer = [&](auto Jc, auto Fc, auto Mc, auto Gc, int k0, const double (&r)[NR], const double (&cf)[NC],
+                   double (&cfn)[NC]) __attribute__((always_inline)) {
     constexpr int J = decltype(Jc)::value;
-    constexpr bool FIRST = decltype(Fc)::value, MASKED = decltype(Mc)::value;
+    constexpr bool FIRST = decltype(Fc)::value, MASKED = decltype(Mc)::value, FLAGS = decltype(Gc)::value;
+    static_assert(FLAGS || !(FIRST || MASKED), "the optimistic form is for whole blocks inside the column");
     const int k = k0 + J;
     auto read_rec = [&](int kk, double (&c_)[NC]) {
       const double *c = sC + ((MASKED || J == kBlk - 1) ? (kk < kend ? kk : kend) : kk) * NC;
@@ -206,8 +234,9 @@ void rt_eclipse_simpson_slant(RtArgs p) {
     bool inr = true;                      // wave-uniform: the layer lies inside the column
     if constexpr (MASKED) inr = k <= kend;
     // (one multiplication and, per ray, one clamped addition: alive_flags)
-    double m[A];
-    const double nnow = alive_flags<A>(p, tm, m);
+    [[maybe_unused]] double m[A];
+    [[maybe_unused]] double nnow = 0.0;
+    if constexpr (FLAGS) nnow = alive_flags<A>(p, tm, m);
     if constexpr (OUT) {
       if (p.tau_out && valid && inr && tm <= thr_max) {   // some ray of the sample is alive on this layer
         p.tau_out[(size_t)i * L + k] = tau;
@@ -219,7 +248,7 @@ void rt_eclipse_simpson_slant(RtArgs p) {
 #pragma unroll
       for (int a = 0; a < A; a++) m[a] = inr ? m[a] : 0.0;
     }
-    if constexpr (!(FIRST && J == 0)) log_event(nnow, k - 1);
+    if constexpr (FLAGS && !(FIRST && J == 0)) log_event(nnow, k - 1);
     // Planck exponent and the slant-path exponents in one interleaved batch
     const double tcl = fmin(tau, tcap);
     double xs[AE + 1], ex[AE + 1], y[A];
@@ -251,7 +280,10 @@ void rt_eclipse_simpson_slant(RtArgs p) {
 #pragma unroll
       for (int a = 0; a < A; a++) {
         const double c = fma(w0, y2[a], fma(w1, y1[a], w2 * y[a]));
-        if constexpr ((J & 1) != 0) P1[a] = fma(c, m[a], P1[a]);
+        if constexpr (!FLAGS) {      // fma(c, 1.0, P) to the bit: one addition of the finished panel
+          if constexpr ((J & 1) != 0) P1[a] = c + P1[a];
+          else P0[a] = c + P0[a];
+        } else if constexpr ((J & 1) != 0) P1[a] = fma(c, m[a], P1[a]);
         else P0[a] = fma(c, m[a], P0[a]);
         y2[a] = y1[a];
         y1[a] = y[a];
@@ -275,55 +307,86 @@ void rt_eclipse_simpson_slant(RtArgs p) {
   // table loads in flight: 119 against 88 us per ten-walker launch)
   double s0[NR], s1[NR], s2[NR];
   double cfE[NC], cfO[NC];
-  auto block6 = [&](auto Fc, auto Mc, int k0) {
+  auto block6 = [&](auto Fc, auto Mc, auto Gc, int k0) __attribute__((always_inline)) {
     constexpr bool MASKED = decltype(Mc)::value;
     auto inblk = [&](int k) { return MASKED ? clampk(k) : k; };
-    layer(integral_constant<int, 0>{}, Fc, Mc, k0, s0, cfE, cfO);
+    layer(integral_constant<int, 0>{}, Fc, Mc, Gc, k0, s0, cfE, cfO);
     load_layer(inblk(k0 + 3), s0);
-    layer(integral_constant<int, 1>{}, Fc, Mc, k0, s1, cfO, cfE);
+    layer(integral_constant<int, 1>{}, Fc, Mc, Gc, k0, s1, cfO, cfE);
     load_layer(inblk(k0 + 4), s1);
-    layer(integral_constant<int, 2>{}, Fc, Mc, k0, s2, cfE, cfO);
+    layer(integral_constant<int, 2>{}, Fc, Mc, Gc, k0, s2, cfE, cfO);
     load_layer(inblk(k0 + 5), s2);
-    layer(integral_constant<int, 3>{}, Fc, Mc, k0, s0, cfO, cfE);
+    layer(integral_constant<int, 3>{}, Fc, Mc, Gc, k0, s0, cfO, cfE);
     load_layer(clampk(k0 + 6), s0);
-    layer(integral_constant<int, 4>{}, Fc, Mc, k0, s1, cfE, cfO);
+    layer(integral_constant<int, 4>{}, Fc, Mc, Gc, k0, s1, cfE, cfO);
     load_layer(clampk(k0 + 7), s1);
-    layer(integral_constant<int, 5>{}, Fc, Mc, k0, s2, cfO, cfE);
+    layer(integral_constant<int, 5>{}, Fc, Mc, Gc, k0, s2, cfO, cfE);
     load_layer(clampk(k0 + 8), s2);
   };
-  load_layer(clampk(0), s0);
-  load_layer(clampk(1), s1);
-  load_layer(clampk(2), s2);
-  if constexpr (SCHED != 0) {
-#pragma unroll
-    for (int j = 0; j < NC; j++) cfE[j] = sC[j];
-  }
   // some ray of this lane is still alive (the one with the largest threshold goes last)
   auto any_active = [&]() {
     unsigned long long mk = __ballot(tm <= thr_max);
     asm volatile("" : "+s"(mk));
     return mk != 0ull;
   };
-  int kw = kBlk;   // layers walked (whole blocks)
-  if (kcut >= kBlk - 1) {
-    block6(true_type{}, false_type{}, 0);
-    int k0 = kBlk;
-    bool alive = any_active();
-    if (alive & (k0 + kBlk - 1 <= kcut)) {
-      do {
-        block6(false_type{}, false_type{}, k0);
-        k0 += kBlk;
-        alive = any_active();
-      } while (alive & (k0 + kBlk - 1 <= kcut));
+  // no lane's tm has passed lim (a NaN limit counts as passed)
+  auto none_above = [&](double lim) {
+    unsigned long long mk = __ballot(!(tm <= lim));
+    asm volatile("" : "+s"(mk));
+    return mk == 0ull;
+  };
+  int kw;                            // layers walked (whole blocks)
+  // the walk.  OPT: with the optimistic loop in front (returns true: a ray died inside one of its blocks -- the
+  // column is to be walked again); without it: the flagged loop alone
+  auto walk = [&](auto Oc) __attribute__((always_inline)) {
+    constexpr bool OPT = decltype(Oc)::value;
+    init_walk();
+    load_layer(clampk(0), s0);
+    load_layer(clampk(1), s1);
+    load_layer(clampk(2), s2);
+    if constexpr (SCHED != 0) {
+#pragma unroll
+      for (int j = 0; j < NC; j++) cfE[j] = sC[j];
     }
-    kw = k0;
-    if (alive & (k0 <= kend)) {   // the column's last, partial block (at most kBlk layers are left: kend <= kcut + 1)
-      block6(false_type{}, true_type{}, k0);
-      kw = k0 + kBlk;
+    kw = kBlk;
+    if (!OPT || kcut >= kBlk - 1) {   // (a second walk follows an optimistic block: the column has whole blocks)
+      block6(true_type{}, false_type{}, true_type{}, 0);
+      int k0 = kBlk;
+      if constexpr (OPT) {
+        bool died = false;
+        bool go = (p.opt_guard > 0.0) & (k0 + kBlk - 1 <= kcut) & none_above(thr_opt);
+        if (go) {
+          do {
+            block6(false_type{}, false_type{}, false_type{}, k0);
+            k0 += kBlk;
+            died = !none_above(thr_min);
+            go = !died & (k0 + kBlk - 1 <= kcut) & none_above(thr_opt);
+          } while (go);
+        }
+        if (died) return true;   // (nothing was logged: the guard held, so no ray had died before that block either)
+      }
+      bool alive = any_active();
+      if (alive & (k0 + kBlk - 1 <= kcut)) {
+        do {
+          block6(false_type{}, false_type{}, true_type{}, k0);
+          k0 += kBlk;
+          alive = any_active();
+        } while (alive & (k0 + kBlk - 1 <= kcut));
+      }
+      kw = k0;
+      if (alive & (k0 <= kend)) {   // the column's last, partial block (at most kBlk layers are left: kend <= kcut + 1)
+        block6(false_type{}, true_type{}, true_type{}, k0);
+        kw = k0 + kBlk;
+      }
+    } else {
+      block6(true_type{}, true_type{}, true_type{}, 0);
     }
-  } else {
-    block6(true_type{}, true_type{}, 0);
-  }
+    return false;
+  };
+  // (the second walk is a second copy of the flagged code, reached by a forward branch: with a branch BACK to the one
+  // copy the register allocator spilled 163 registers of <5, 4, 2> instead of 21, some of them inside the loops)
+  const bool restarted = walk(true_type{});
+  if (restarted) walk(false_type{});
 
   // ---- after the walk: per ray angle the sum of its parity, its padded panel, the deck's surface term
   double F = 0.0;
@@ -459,6 +522,8 @@ void rt_eclipse_simpson_slant(RtArgs p) {
   if (valid) p.spec[(size_t)w * W + i] = F;
   if (p.walked_out && threadIdx.x == 0)  // diagnostics: layers this wave walked (bench.py's byte model)
     p.walked_out[(size_t)w * p.ntiles + tile] = (kw < kend + 1 ? kw : kend + 1);
+  if (p.restart_out && restarted && (threadIdx.x & 63) == 0)   // diagnostics: waves of this walker that walked twice
+    atomicAdd(p.restart_out + w, 1);
 }
 
 // (built in rt_eclipse_slant_ilp.hip: five angles, the line-by-line hand-off, the tau / intensity outputs; other ray-grid

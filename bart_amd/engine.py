@@ -496,6 +496,17 @@ def walked_end():
     return out, wpc.value, name.value.decode()
 
 
+def walked_restarts():
+    """-> restarts[nwalkers] of the record walked_end() returned: the waves of each walker that walked their column
+    a second time (the optimistic loop of the single-wave `cut slant` kernel, trm.set_slant_opt)."""
+    n = C.c_int()
+    _check(trm.lib().bartrt_walked_restarts(None, 0, C.byref(n)))
+    out = np.zeros(n.value, np.int32)
+    if out.size:
+        _check(trm.lib().bartrt_walked_restarts(_ptr(out), out.size, C.byref(n)))
+    return out
+
+
 def kernel_inventory() -> list[tuple[str, bool, str]]:
     """The eclipse kernels the library holds ahead of time: (template-id, max-ILP run-time build, object) each.  No GPU,
     no engine."""

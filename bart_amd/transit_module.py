@@ -100,6 +100,10 @@ def lib():
         L.bartrt_set_integ.argtypes = [i]
         L.bartrt_set_cut.argtypes = [i]
         L.bartrt_get_cut.argtypes = [C.POINTER(i)]
+        L.bartrt_set_slant_opt.argtypes = [d]
+        L.bartrt_get_slant_opt.argtypes = [C.POINTER(d)]
+        L.bartrt_parse_slant_opt.argtypes = [C.c_char_p, C.POINTER(d)]
+        L.bartrt_walked_restarts.argtypes = [p, i, C.POINTER(i)]
         L.bartrt_set_kernel_by.argtypes = [i]
         L.bartrt_get_kernel_by.argtypes = [C.POINTER(i)]
         L.bartrt_get_cia_interp.argtypes = [C.POINTER(i)]
@@ -208,6 +212,25 @@ def set_cut(cut):
     """'slant' (default) or 'vertical': which optical depth `toomuch` is compared with
     (include/bartrt.h, bartrt_set_cut)."""
     check(lib().bartrt_set_cut({"vertical": 0, "slant": 1, 0: 0, 1: 1}[cut]))
+
+
+def set_slant_opt(guard):
+    """Guard of the single-wave `cut slant` kernel's optimistic loop: 0 (off) or a power of two 2^-10 .. 1
+    (include/bartrt.h, bartrt_set_slant_opt).  Needs no engine; the spectra do not depend on it."""
+    check(lib().bartrt_set_slant_opt(float(guard)))
+
+
+def get_slant_opt() -> float:
+    v = C.c_double(-1.0)
+    check(lib().bartrt_get_slant_opt(C.byref(v)))
+    return v.value
+
+
+def parse_slant_opt(text: str) -> float:
+    """The guard a BARTRT_SLANT_OPT of this text names (refused: the library's error)."""
+    v = C.c_double(-1.0)
+    check(lib().bartrt_parse_slant_opt(text.encode(), C.byref(v)))
+    return v.value
 
 
 def set_kernel_by(which):

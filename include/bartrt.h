@@ -104,6 +104,16 @@ int bartrt_get_integ(int *rule);
  * the cfg key `cut vertical|slant` and BARTRT_CUT. */
 int bartrt_set_cut(int slant);
 int bartrt_get_cut(int *slant);
+/* The optimistic loop of rule 1's single-wave `cut slant` kernel (csrc/rt_eclipse_s1s.hpp): whole six-layer blocks
+ * are walked without ray flags and event log while every lane's optical depth stands at or below guard * (the
+ * smallest ray threshold) at the block's start; a wave that finds a ray dead at such a block's end walks its column
+ * again with the flags.  Spectra are the same bits for every guard.  guard: 0 = off, or a power of two 2^-10 .. 1
+ * (default 2^-4); anything else is refused.  Process-wide, applies to the launches that follow; needs no engine.
+ * BARTRT_SLANT_OPT=n sets it at start-up: 0 = off, n = 1 .. 10 = 2^-n (bartrt_parse_slant_opt is that reading); any
+ * other text is refused: bartrt_init and bartrt_get_slant_opt fail with BARTRT_EINVAL until the setter is called. */
+int bartrt_set_slant_opt(double guard);
+int bartrt_get_slant_opt(double *guard);
+int bartrt_parse_slant_opt(const char *text, double *guard);
 
 /* Sharded engines ("--shard r n"): which column count picks the kernel variant.  1 (DEFAULT) = this
  * block's own: a block of a few hundred samples takes the layer-parallel kernels instead of the
@@ -519,6 +529,9 @@ int bartrt_timing_end(double *kernel_ms, int *nlaunch);
 int bartrt_walked_begin(void);
 int bartrt_walked_end(int *walked, int cap, int *nwalkers, int *ncolumns, int *wn_per_column,
                       char *kernel, int kernel_len);
+/* With the same record (after bartrt_walked_end): restarts[nwalkers], per walker of the last launch the waves that
+ * walked their column a second time (bartrt_set_slant_opt; 0 for every other kernel). */
+int bartrt_walked_restarts(int *restarts, int cap, int *nwalkers);
 /* Shapes outside the ahead-of-time set (seven and more table molecules with two cross-section files under the default
  * spline, nine and more molecules, ten and more ray angles) are instantiated from the same kernel templates when they
  * are first launched (hiprtc; cached under BARTRT_RTC_CACHE, default ~/.cache/bartrt; BARTRT_RTC=0 or a machine without
