@@ -522,7 +522,9 @@ void rt_eclipse_simpson_slant(RtArgs p) {
   if (valid) p.spec[(size_t)w * W + i] = F;
   if (p.walked_out && threadIdx.x == 0)  // diagnostics: layers this wave walked (bench.py's byte model)
     p.walked_out[(size_t)w * p.ntiles + tile] = (kw < kend + 1 ? kw : kend + 1);
-  if (p.restart_out && restarted && (threadIdx.x & 63) == 0)   // diagnostics: waves of this walker that walked twice
+  // diagnostics: waves of this walker that walked twice.  Only waves that hold a wavenumber count (`valid` on a wave's
+  // first lane): in a workgroup of 128 or 256 lanes the waves past the last wavenumber walk copies of its column
+  if (p.restart_out && restarted && valid && (threadIdx.x & 63) == 0)
     atomicAdd(p.restart_out + w, 1);
 }
 
