@@ -971,6 +971,43 @@ int bartrt_mcmc_run(int nchains, int npars, long nsteps, const double *params, c
   });
 }
 
+int bartrt_mcmc_run_resident(int nchains, int npars, long nsteps, const double *params, const double *pmin,
+                             const double *pmax, const double *stepsize, int ndata, const double *data,
+                             const double *uncert, const bartrt_mcmc_opts *opts, double *chain, double *chisq,
+                             double *models, long *naccept, long *nbad) {
+  NEED_ENGINE();
+  if (!g_eng->step) return fail(BARTRT_EINVAL, "mcmc_run_resident: call bartrt_step_setup first");
+  if (!params || !pmin || !pmax || !stepsize || !data || !uncert || !chain || !chisq)
+    return fail(BARTRT_EINVAL, "mcmc_run_resident: null buffer");
+  // the caller's struct may be an older, shorter one: fields past its size read as zero
+  bartrt_mcmc_opts o;
+  std::memset(&o, 0, sizeof o);
+  if (opts) {
+    if (opts->size < sizeof(opts->size)) return fail(BARTRT_EINVAL, "mcmc_run_resident: set opts->size");
+    std::memcpy(&o, opts, opts->size < sizeof o ? opts->size : sizeof o);
+  }
+  McmcOpts m;
+  m.snooker = o.snooker;
+  m.seed = o.seed;
+  m.thin = o.thin ? o.thin : 1;
+  m.block = o.block ? o.block : 256;
+  m.prior = o.prior; m.priorlow = o.priorlow; m.priorup = o.priorup;
+  m.progress = o.progress; m.progress_user = o.progress_user;
+  return guarded([&] {
+    mcmc_run_resident(*g_eng, nchains, npars, nsteps, params, pmin, pmax, stepsize, ndata, data, uncert, m, chain,
+                      chisq, models, naccept, nbad);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_mcmc_draws(unsigned long long seed, unsigned long long t, int nchains, int npars, double *out) {
+  if (!out) return fail(BARTRT_EINVAL, "bartrt_mcmc_draws: null buffer");
+  return guarded([&] {
+    mcmc_draws_probe(seed, t, nchains, npars, out);
+    return BARTRT_OK;
+  });
+}
+
 // ---- the ranks' communicator (comm.hip) -----------------------------------
 int bartrt_comm_get_unique_id(void *id) {
   // (needs no engine: rank 0 may ask before its bartrt_init; a chain-service client gets what every non-reference

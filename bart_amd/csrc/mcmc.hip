@@ -11,9 +11,14 @@
 #include <cmath>
 #include <limits>
 #include <random>
+#include <stdexcept>
+#include <string>
 #include <vector>
 
+#include "../../include/bartrt.h"
+#include "comm.hpp"
 #include "engine.hpp"
+#include "mcmc_core.hpp"
 #include "step.hpp"
 
 namespace bartrt {
@@ -159,6 +164,187 @@ void mcmc_run(Engine &e, int nch, int npars, long nsteps, const double *params, 
     }
   }
   if (naccept_out) *naccept_out = naccept;
+}
+
+// ---- the resident loop ---------------------------------------------------------------------------------------------
+// The same sampler with the population in HBM and no host wait inside an iteration.  Its arithmetic and its random
+// draws are mcmc_core.hpp's: a counter-based generator, so a chain can be restated draw for draw anywhere (the
+// streams of mcmc_run above and of bart_amd/sampler.py remain their own).  Shared parameters (stepsize < 0),
+// Gaussian priors, thinning and the per-sample band fluxes are served here and only here.
+namespace {
+
+// One workgroup, chain i on lane i.  Launch t finishes iteration t - 1 on the band fluxes and statuses the step left
+// (decision, new state, output rows, per-lane counters), then -- every chain's new point in place -- proposes
+// iteration t into the rows the next step reads.  snap (host-mapped, optional): the lanes' accept counts so far.
+__global__ __launch_bounds__(mcmc::kMaxChains) void mcmc_advance(mcmc::State s, long t, int finish_prev,
+                                                                 int propose_next, long *snap) {
+  const int i = threadIdx.x;
+  if (finish_prev && i < s.nch) {
+    mcmc::finish(s, t - 1, i);
+    if (snap) snap[i] = s.counts[(size_t)i * 4];
+  }
+  __syncthreads();
+  if (propose_next && i < s.nch) mcmc::propose(s, t, i);
+}
+
+__global__ void mcmc_draws_kernel(unsigned long long seed, unsigned long long t, int nch, int npars, double *out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nch) mcmc::draws_row(seed, t, nch, i, npars, out + (size_t)i * (mcmc::kDrawsHead + npars));
+}
+
+struct Events {
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  Events() {
+    for (hipEvent_t &e : ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+  ~Events() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+}  // namespace
+
+void mcmc_draws_probe(unsigned long long seed, unsigned long long t, int nchains, int npars, double *out) {
+  if (nchains < 1 || nchains > (1 << 20) || npars < 1 || npars > mcmc::kMaxPars)
+    throw std::invalid_argument("mcmc_draws: 1 <= nchains <= 2^20 and 1 <= npars <= 64");
+  const size_t n = (size_t)nchains * (mcmc::kDrawsHead + npars);
+  DevBuf<double> d;
+  d.reserve(n);
+  mcmc_draws_kernel<<<dim3((unsigned)((nchains + 255) / 256)), dim3(256)>>>(seed, t, nchains, npars, d);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(out, d, sizeof(double) * n, hipMemcpyDeviceToHost));
+}
+
+void mcmc_run_resident(Engine &e, int nch, int npars, long nsteps, const double *params, const double *pmin,
+                       const double *pmax, const double *stepsize, int ndata, const double *data,
+                       const double *uncert, const McmcOpts &opts, double *chain, double *chisq, double *models,
+                       long *naccept_out, long *nbad) {
+  if (!e.step) throw IoError{"mcmc_run_resident: call step_setup first"};
+  if (nch < 1 || npars < 1 || nsteps < 1) throw std::invalid_argument("mcmc_run_resident: bad sizes");
+  if (nch > mcmc::kMaxChains)
+    throw std::invalid_argument("mcmc_run_resident: at most 1024 chains (one workgroup); more stay with mcmc_run");
+  if (npars > mcmc::kMaxPars) throw std::invalid_argument("mcmc_run_resident: too many parameters (at most 64)");
+  if (opts.thin < 1 || opts.block < 1) throw std::invalid_argument("mcmc_run_resident: thin and block must be >= 1");
+  if (ndata < 1 || ndata != e.step->nfilters)
+    throw std::invalid_argument("mcmc_run_resident: data length must equal the number of filters");
+  const bool priors = opts.prior || opts.priorlow || opts.priorup;
+  if (priors && !(opts.prior && opts.priorlow && opts.priorup))
+    throw std::invalid_argument("mcmc_run_resident: prior, priorlow and priorup come together");
+  int nfree = 0;
+  if (const int bad = mcmc::check_stepsize(npars, stepsize, &nfree))
+    throw std::invalid_argument("mcmc_run_resident: stepsize[" + std::to_string(bad - 1) + "] = " +
+                                std::to_string(stepsize[bad - 1]) + " shares parameter " +
+                                std::to_string(bad - 1) + " with a parameter that is out of range or itself shared");
+  if (e.lbl && e.comm)
+    throw CommError{BARTRT_ENOTSUP, "mcmc_run_resident: line-by-line engines do not take the communicator's path"};
+
+  const long nkept = mcmc::kept_rows(nsteps, opts.thin);
+  const size_t np = npars, nd = ndata, n = nch;
+  // the start, on the host through step_run_host as mcmc_run makes it, then uploaded once
+  std::vector<double> x(n * np), c(n), cur(n * nd);
+  std::vector<int> status(n);
+  long nbad_start[4] = {0, 0, 0, 0};
+  mcmc::State h{};
+  h.nch = nch; h.npars = npars; h.ndata = ndata; h.nfree = nfree; h.snooker = opts.snooker; h.seed = opts.seed;
+  h.nsteps = nsteps; h.thin = opts.thin;
+  h.pmin = pmin; h.pmax = pmax; h.stepsize = stepsize; h.data = data; h.uncert = uncert;
+  h.prior = opts.prior; h.priorlow = opts.priorlow; h.priorup = opts.priorup;
+  h.x = x.data(); h.c = c.data(); h.cur = cur.data();
+  auto model = [&](const double *rows, int m, double *band, int *st) { step_run_host(e, rows, m, npars, band, st); };
+  if (!mcmc::start_population(h, params, model, status.data(), nbad_start))
+    throw IoError{"mcmc_run_resident: no chain starts on a physical model: check params/pmin/pmax"};
+
+  // constants: pmin pmax stepsize [prior priorlow priorup] data uncert
+  std::vector<double> consts;
+  auto put = [&](const double *v, size_t m) { consts.insert(consts.end(), v, v + m); };
+  put(pmin, np); put(pmax, np); put(stepsize, np);
+  if (priors) { put(opts.prior, np); put(opts.priorlow, np); put(opts.priorup, np); }
+  put(data, nd); put(uncert, nd);
+  DevBuf<double> d_consts, d_pop, d_out;
+  DevBuf<int> d_int;
+  DevBuf<long> d_counts;
+  d_consts.upload(consts);
+  // population: x c cur logjac prop band
+  d_pop.reserve(n * np + n + n * nd + n + n * np + n * nd);
+  d_int.reserve(2 * n);
+  d_counts.reserve(4 * n);
+  d_out.reserve((size_t)nch * nkept * (np + 1 + (models ? nd : 0)));
+  HIPCHK(hipMemset(d_pop, 0, sizeof(double) * d_pop.count()));
+  HIPCHK(hipMemset(d_int, 0, sizeof(int) * 2 * n));
+  HIPCHK(hipMemset(d_counts, 0, sizeof(long) * 4 * n));
+  mcmc::State d = h;
+  const double *k = d_consts;
+  d.pmin = k; d.pmax = k + np; d.stepsize = k + 2 * np;
+  k += 3 * np;
+  if (priors) { d.prior = k; d.priorlow = k + np; d.priorup = k + 2 * np; k += 3 * np; }
+  d.data = k; d.uncert = k + nd;
+  double *q = d_pop;
+  d.x = q; q += n * np;
+  d.c = q; q += n;
+  d.cur = q; q += n * nd;
+  d.logjac = q; q += n;
+  d.prop = q; q += n * np;
+  double *d_band = q;
+  d.band = d_band;
+  d.inside = d_int;
+  int *d_status = d_int + n;
+  d.status = d_status;
+  d.counts = d_counts;
+  d.chain = d_out;
+  d.chisq = d.chain + (size_t)nch * nkept * np;
+  d.models = models ? d.chisq + (size_t)nch * nkept : nullptr;
+  HIPCHK(hipMemcpy(d.x, x.data(), sizeof(double) * n * np, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d.c, c.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d.cur, cur.data(), sizeof(double) * n * nd, hipMemcpyHostToDevice));
+
+  // accept counts at the end of a block, one slot per block in flight
+  PinBuf<long> snap;
+  snap.reserve(2 * n);
+  void *snap_dev = nullptr;
+  HIPCHK(hipHostGetDevicePointer(&snap_dev, snap.get(), 0));
+  Events events;
+  const long B = opts.block, nblocks = (nsteps + B - 1) / B;
+  const unsigned threads = (unsigned)((nch + 63) / 64 * 64);
+  auto launch = [&](long t, long *snap_slot) {
+    hipLaunchKernelGGL(mcmc_advance, dim3(1), dim3(threads), 0, e.stream, d, t, (int)(t > 0), (int)(t < nsteps),
+                       snap_slot);
+    HIPCHK(hipGetLastError());
+    if (t < nsteps) step_run_dev(e, d.prop, nch, npars, d_band, d_status, nullptr, e.stream, nullptr);
+  };
+  auto finished = [&](long b) {   // block b is done: wait for it and report
+    HIPCHK(hipEventSynchronize(events.ev[b % 2]));
+    if (!opts.progress) return;
+    long acc = 0;
+    for (size_t i = 0; i < n; i++) acc += snap.get()[(size_t)(b % 2) * n + i];
+    opts.progress(std::min((b + 1) * B, nsteps), acc, opts.progress_user);
+  };
+  launch(0, nullptr);
+  for (long b = 0; b < nblocks; b++) {
+    if (b >= 2) finished(b - 2);   // at most two blocks in flight
+    const long last = std::min((b + 1) * B, nsteps);
+    for (long t = b * B + 1; t <= last; t++)
+      launch(t, t == last ? static_cast<long *>(snap_dev) + (size_t)(b % 2) * n : nullptr);
+    HIPCHK(hipEventRecord(events.ev[b % 2], e.stream));
+  }
+  for (long b = std::max(0L, nblocks - 2); b < nblocks; b++) finished(b);
+  HIPCHK(hipStreamSynchronize(e.stream));
+
+  const size_t rows = (size_t)nch * nkept;
+  HIPCHK(hipMemcpy(chain, d.chain, sizeof(double) * rows * np, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(chisq, d.chisq, sizeof(double) * rows, hipMemcpyDeviceToHost));
+  if (models) HIPCHK(hipMemcpy(models, d.models, sizeof(double) * rows * nd, hipMemcpyDeviceToHost));
+  std::vector<long> counts(4 * n);
+  HIPCHK(hipMemcpy(counts.data(), d_counts, sizeof(long) * 4 * n, hipMemcpyDeviceToHost));
+  long total[4] = {0, nbad_start[1], nbad_start[2], nbad_start[3]};
+  for (size_t i = 0; i < n; i++)
+    for (int s = 0; s < 4; s++) total[s] += counts[4 * i + s];
+  if (naccept_out) *naccept_out = total[0];
+  if (nbad) {
+    nbad[0] = 0;
+    for (int s = 1; s < 4; s++) nbad[s] = total[s];
+  }
 }
 
 }  // namespace bartrt

@@ -1,0 +1,349 @@
+// The sampler's arithmetic, stated once for host and device: the counter-based random draws, the DEMC and snooker
+// moves, shared parameters, Gaussian priors and the acceptance rule of the resident loop (mcmc.hip: mcmc_advance,
+// mcmc_run_resident).  Plain inline functions on plain pointers, no HIP call: the kernel runs them one chain per
+// lane, the host runs them for the start of a run, and a host compiler alone builds them for the CPU tests
+// (tests/mcmc_core_host.cpp).
+//
+// GENERATOR.  Philox4x32-10 (Salmon et al. 2011).  key = (seed low word, seed high word); counter = (t low word,
+// t high word, chain, slot).  t is the iteration, 0 <= t < 2^63; the start of a run draws at t = kStartT + round
+// (round 0: the jittered start, rounds 1..20: the re-draws of chains that start on a rejected model).  No draw
+// depends on how many other draws were made, and the generator has no state anywhere.
+//
+// Each block of four words gives two uniforms, u0 from words (0, 1) and u1 from words (2, 3): the top 53 bits h of
+// the 64-bit number (word 0 high), u = (h + 0.5) 2^-53 in double arithmetic, and 1 - 2^-53 where that sum rounds to 1
+// (h + 0.5 is not a double above 2^52), so 0 < u < 1 always.  A pair of normals comes from Box-Muller on (u0, u1):
+// n0 = r cos(2 pi u1), n1 = r sin(2 pi u1), r = sqrt(-2 log u0).
+//
+//   slot        u0 / n0                          u1 / n1
+//   0           partner r1                       partner r2
+//   1           snooker's third chain z          snooker's gamma = 1.2 + u1
+//   2           acceptance uniform               (unused)
+//   3 + j / 2   jitter normal of parameter j     jitter normal of parameter j + 1       (j even; DEMC moves and the
+//                                                                                        start, free parameters only)
+//
+// PARAMETERS.  stepsize[j] > 0: free.  stepsize[j] == 0: fixed at its configured value.  stepsize[j] = -k (MC3's
+// convention, k counted from 1): shared, a copy of parameter k - 1 in every proposal and start point; the target must
+// be in range and not itself shared.  nfree counts the free ones; the box [pmin, pmax] applies to them alone.
+//
+// CHI-SQUARE.  The data term is summed over the filters in index order.  With prior arrays and priorlow[j] != 0,
+// parameter j adds ((p_j - prior_j) / sigma)^2, sigma = priorlow[j] below prior_j and priorup[j] above.  The chisq the
+// loop keeps and writes out is the data term PLUS the prior terms.
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#ifndef __HIPCC__
+#define __host__
+#define __device__
+#endif
+#define MCMC_HD __host__ __device__ inline
+// the same roundings on the host and on the device: no multiply-add contraction in these functions
+#if defined(__clang__)
+#define MCMC_EXACT _Pragma("clang fp contract(off)")
+#else
+#define MCMC_EXACT
+#endif
+
+namespace bartrt {
+namespace mcmc {
+
+constexpr int kMaxPars = 64, kMaxChains = 1024;
+constexpr unsigned kSlotPartners = 0, kSlotSnooker = 1, kSlotAccept = 2, kSlotJitter = 3;
+constexpr unsigned long long kStartT = 0xFFFFFFFFFFFFFF00ull;
+constexpr int kStartRounds = 20;
+
+struct Words {
+  uint32_t w[4];
+};
+
+MCMC_HD Words philox4x32_10(Words c, uint32_t k0, uint32_t k1) {
+  for (int r = 0; r < 10; r++) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c.w[0], p1 = (uint64_t)0xCD9E8D57u * c.w[2];
+    const Words n = {{(uint32_t)(p1 >> 32) ^ c.w[1] ^ k0, (uint32_t)p1, (uint32_t)(p0 >> 32) ^ c.w[3] ^ k1,
+                      (uint32_t)p0}};
+    c = n;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return c;
+}
+
+MCMC_HD Words block(unsigned long long seed, unsigned long long t, int chain, unsigned slot) {
+  const Words c = {{(uint32_t)t, (uint32_t)(t >> 32), (uint32_t)chain, slot}};
+  return philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+
+MCMC_HD double uniform53(uint32_t hi, uint32_t lo) {
+  MCMC_EXACT
+  const uint64_t h = (((uint64_t)hi << 32) | lo) >> 11;
+  const double u = ((double)h + 0.5) * 0x1p-53;
+  return u < 1.0 ? u : 1.0 - 0x1p-53;
+}
+
+MCMC_HD void uniforms(unsigned long long seed, unsigned long long t, int chain, unsigned slot, double &u0,
+                      double &u1) {
+  const Words b = block(seed, t, chain, slot);
+  u0 = uniform53(b.w[0], b.w[1]);
+  u1 = uniform53(b.w[2], b.w[3]);
+}
+
+MCMC_HD void normals(unsigned long long seed, unsigned long long t, int chain, unsigned slot, double &n0,
+                     double &n1) {
+  MCMC_EXACT
+  double u0, u1;
+  uniforms(seed, t, chain, slot, u0, u1);
+  const double r = sqrt(-2.0 * log(u0)), a = 6.283185307179586 * u1;
+  n0 = r * cos(a);
+  n1 = r * sin(a);
+}
+
+// uniform over the chains other than i, a, b (a, b < 0: unused), from the uniform u
+MCMC_HD int other(double u, int nch, int i, int a, int b) {
+  MCMC_EXACT
+  int ex[3] = {i, a, b};
+  const int k = 1 + (a >= 0) + (b >= 0);
+  // ascending; unused entries (-1) come first
+  if (ex[0] > ex[1]) { const int s = ex[0]; ex[0] = ex[1]; ex[1] = s; }
+  if (ex[1] > ex[2]) { const int s = ex[1]; ex[1] = ex[2]; ex[2] = s; }
+  if (ex[0] > ex[1]) { const int s = ex[0]; ex[0] = ex[1]; ex[1] = s; }
+  int draw = (int)(u * (nch - k));
+  if (draw >= nch - k) draw = nch - k - 1;
+  for (int q = 3 - k; q < 3; q++) draw += draw >= ex[q];
+  return draw;
+}
+
+// The run as the two halves of an iteration see it.  Every pointer is memory of the side that calls (device memory
+// in the kernel, host memory in host code).
+struct State {
+  // the problem
+  int nch, npars, ndata, nfree;
+  int snooker;                               // the walk asked for; it applies with more than three chains
+  unsigned long long seed;
+  long nsteps, thin;                         // rows t = thin - 1, 2 thin - 1, ... and the last iteration are written
+  const double *pmin, *pmax, *stepsize;      // [npars]
+  const double *data, *uncert;               // [ndata]
+  const double *prior, *priorlow, *priorup;  // [npars], or all null: uniform priors
+  // the population, kept between the halves
+  double *x;        // [nch][npars] current points
+  double *c;        // [nch] their chisq (data + prior terms; inf: not on a physical model)
+  double *cur;      // [nch][ndata] their band fluxes
+  double *logjac;   // [nch] of the pending proposal
+  int *inside;      // [nch] the pending proposal lies in the box (else the model was given the current point)
+  long *counts;     // [nch][4] accepted proposals, models rejected with status 1, 2, 3
+  // the exchange with the model
+  double *prop;         // [nch][npars] rows the model is evaluated on
+  const double *band;   // [nch][ndata] its band fluxes
+  const int *status;    // [nch] its statuses
+  // results
+  double *chain, *chisq;  // [nch][nkept][npars], [nch][nkept]
+  double *models;         // [nch][nkept][ndata] band fluxes of the chains' current states, or null
+};
+
+MCMC_HD long kept_rows(long nsteps, long thin) { return (nsteps + thin - 1) / thin; }
+
+// 0, or 1 + the index of the first parameter whose shared target is out of range or itself shared; *nfree counted
+MCMC_HD int check_stepsize(int npars, const double *stepsize, int *nfree) {
+  int n = 0;
+  for (int j = 0; j < npars; j++) {
+    const double s = stepsize[j];
+    if (s > 0) n++;
+    if (s < 0) {
+      const double k = -s;
+      if (!(k >= 1.0 && k <= (double)npars) || k != (double)(int)k || stepsize[(int)k - 1] < 0) return j + 1;
+    }
+  }
+  if (nfree) *nfree = n;
+  return 0;
+}
+
+MCMC_HD void copy_shared(int npars, const double *stepsize, double *p) {
+  for (int j = 0; j < npars; j++)
+    if (stepsize[j] < 0) p[j] = p[(int)(-stepsize[j]) - 1];
+}
+
+MCMC_HD double prior_term(const State &s, const double *p) {
+  MCMC_EXACT
+  double c = 0.0;
+  if (!s.prior || !s.priorlow || !s.priorup) return c;
+  for (int j = 0; j < s.npars; j++) {
+    if (s.priorlow[j] == 0.0) continue;
+    const double d = p[j] - s.prior[j];
+    const double r = d / (d < 0.0 ? s.priorlow[j] : s.priorup[j]);
+    c += r * r;
+  }
+  return c;
+}
+
+// chisq of a model row at the point p: data term in filter order, then the prior terms
+MCMC_HD double chisq_of(const State &s, const double *band, const double *p) {
+  MCMC_EXACT
+  double c = 0.0;
+  for (int f = 0; f < s.ndata; f++) {
+    const double r = (band[f] - s.data[f]) / s.uncert[f];
+    c += r * r;
+  }
+  return c + prior_term(s, p);
+}
+
+MCMC_HD bool accepts(double u, double cp, double c, double logjac) {
+  MCMC_EXACT
+  return std::isfinite(cp) && log(u) < -0.5 * (cp - c) + logjac;
+}
+
+// Start point of chain i: round 0 is the configured point, jittered by the stepsizes for every chain but the first;
+// a later round re-draws it a tenth as wide.  Free parameters are clipped to the box; shared ones follow.
+MCMC_HD void start_point(const State &s, int round, int i, const double *params, double *xi) {
+  MCMC_EXACT
+  const double width = round == 0 ? (i > 0 ? 1.0 : 0.0) : 0.1;
+  for (int j = 0; j < s.npars; j += 2) {
+    const bool f0 = s.stepsize[j] > 0, f1 = j + 1 < s.npars && s.stepsize[j + 1] > 0;
+    double n0 = 0.0, n1 = 0.0;
+    if ((f0 || f1) && width != 0.0) normals(s.seed, kStartT + (unsigned)round, i, kSlotJitter + j / 2, n0, n1);
+    xi[j] = params[j] + (f0 ? width * s.stepsize[j] * n0 : 0.0);
+    if (f0) xi[j] = fmin(fmax(xi[j], s.pmin[j]), s.pmax[j]);
+    if (j + 1 < s.npars) {
+      xi[j + 1] = params[j + 1] + (f1 ? width * s.stepsize[j + 1] * n1 : 0.0);
+      if (f1) xi[j + 1] = fmin(fmax(xi[j + 1], s.pmin[j + 1]), s.pmax[j + 1]);
+    }
+  }
+  copy_shared(s.npars, s.stepsize, xi);
+}
+
+// First half of iteration t for chain i: the proposal from the population x into row i of prop.  A proposal outside
+// the box is not sent to the model: the row gets the chain's current point and inside[i] = 0.
+MCMC_HD void propose(const State &s, long t, int i) {
+  MCMC_EXACT
+  const int nch = s.nch, np = s.npars;
+  const double *xi = s.x + (size_t)i * np;
+  double *pi = s.prop + (size_t)i * np;
+  for (int j = 0; j < np; j++) pi[j] = xi[j];
+  double u0, u1;
+  uniforms(s.seed, (unsigned long long)t, i, kSlotPartners, u0, u1);
+  const int r1 = nch > 1 ? other(u0, nch, i, -1, -1) : i;
+  const int r2 = nch > 2 ? other(u1, nch, i, r1, -1) : r1;
+  const double *x1 = s.x + (size_t)r1 * np, *x2 = s.x + (size_t)r2 * np;
+  double logjac = 0.0;
+  if (s.snooker && nch > 3 && t % 10 != 0) {
+    // snooker update: move along the line through a third chain
+    uniforms(s.seed, (unsigned long long)t, i, kSlotSnooker, u0, u1);
+    const double *xz = s.x + (size_t)other(u0, nch, i, r1, r2) * np;
+    double nd = 0.0, proj = 0.0;
+    for (int j = 0; j < np; j++)
+      if (s.stepsize[j] > 0) nd += (xi[j] - xz[j]) * (xi[j] - xz[j]);
+    nd = sqrt(nd);
+    if (nd == 0.0) nd = 1.0;
+    for (int j = 0; j < np; j++)
+      if (s.stepsize[j] > 0) proj += (x1[j] - x2[j]) * (xi[j] - xz[j]) / nd;
+    const double g = 1.2 + u1;
+    double ndn = 0.0;
+    for (int j = 0; j < np; j++)
+      if (s.stepsize[j] > 0) {
+        pi[j] = xi[j] + g * proj * (xi[j] - xz[j]) / nd;
+        ndn += (pi[j] - xz[j]) * (pi[j] - xz[j]);
+      }
+    logjac = (s.nfree - 1) * (log(fmax(sqrt(ndn), 1e-300)) - log(nd));
+  } else {
+    const double gam = t % 10 == 0 ? 1.0 : 2.38 / sqrt(2.0 * (s.nfree > 1 ? s.nfree : 1));
+    for (int j = 0; j < np; j += 2) {
+      const bool f0 = s.stepsize[j] > 0, f1 = j + 1 < np && s.stepsize[j + 1] > 0;
+      if (!f0 && !f1) continue;
+      double n0, n1;
+      normals(s.seed, (unsigned long long)t, i, kSlotJitter + j / 2, n0, n1);
+      if (f0) pi[j] = xi[j] + gam * (x1[j] - x2[j]) + 1e-3 * s.stepsize[j] * n0;
+      if (f1) pi[j + 1] = xi[j + 1] + gam * (x1[j + 1] - x2[j + 1]) + 1e-3 * s.stepsize[j + 1] * n1;
+    }
+  }
+  int in = 1;
+  for (int j = 0; j < np; j++)
+    if (s.stepsize[j] > 0) in = in && pi[j] >= s.pmin[j] && pi[j] <= s.pmax[j];
+  if (in) copy_shared(np, s.stepsize, pi);
+  else
+    for (int j = 0; j < np; j++) pi[j] = xi[j];
+  s.inside[i] = in;
+  s.logjac[i] = logjac;
+}
+
+// Second half of iteration t for chain i, once the model has run on prop: chisq, the decision, the chain's new
+// state, its counters and (on a kept iteration) its output rows.  A proposal that fell outside the box is refused
+// and its model row (the current point's) is not counted as a rejected model.
+MCMC_HD void finish(const State &s, long t, int i) {
+  const int np = s.npars, nd = s.ndata;
+  double *xi = s.x + (size_t)i * np, *ci = s.cur + (size_t)i * nd;
+  const double *pi = s.prop + (size_t)i * np, *bi = s.band + (size_t)i * nd;
+  double cp = INFINITY;
+  if (s.inside[i]) {
+    const int st = s.status[i];
+    if (st >= 1 && st <= 3) s.counts[(size_t)i * 4 + st]++;
+    if (st == 0) cp = chisq_of(s, bi, pi);
+  }
+  double u, unused;
+  uniforms(s.seed, (unsigned long long)t, i, kSlotAccept, u, unused);
+  if (accepts(u, cp, s.c[i], s.logjac[i])) {
+    for (int j = 0; j < np; j++) xi[j] = pi[j];
+    for (int f = 0; f < nd; f++) ci[f] = bi[f];
+    s.c[i] = cp;
+    s.counts[(size_t)i * 4]++;
+  }
+  if ((t + 1) % s.thin != 0 && t != s.nsteps - 1) return;
+  const size_t row = (size_t)i * kept_rows(s.nsteps, s.thin) + (size_t)(t / s.thin);
+  for (int j = 0; j < np; j++) s.chain[row * np + j] = xi[j];
+  s.chisq[row] = s.c[i];
+  if (s.models)
+    for (int f = 0; f < nd; f++) s.models[row * nd + f] = ci[f];
+}
+
+// Host code.  The start of a run: the configured point jittered by the stepsizes, chains that start on a rejected
+// model re-drawn up to kStartRounds times, every round one model call on all chains.  model(rows [n][npars], n,
+// band [n][ndata], status [n]) is the batched model; status [nch] is scratch.  Fills x, c and cur; counts the
+// rejected models in nbad[1..3] (null: not counted).  False: no chain starts on a physical model.
+template <class Model>
+inline bool start_population(const State &s, const double *params, Model &&model, int *status, long *nbad) {
+  auto evaluate = [&] {
+    model(s.x, s.nch, s.cur, status);
+    for (int i = 0; i < s.nch; i++) {
+      if (nbad && status[i] >= 1 && status[i] <= 3) nbad[status[i]]++;
+      s.c[i] = status[i] == 0 ? chisq_of(s, s.cur + (size_t)i * s.ndata, s.x + (size_t)i * s.npars) : INFINITY;
+    }
+  };
+  for (int i = 0; i < s.nch; i++) start_point(s, 0, i, params, s.x + (size_t)i * s.npars);
+  evaluate();
+  for (int round = 1; round <= kStartRounds; round++) {
+    bool any_bad = false;
+    for (int i = 0; i < s.nch; i++)
+      if (!std::isfinite(s.c[i])) {
+        any_bad = true;
+        start_point(s, round, i, params, s.x + (size_t)i * s.npars);
+      }
+    if (!any_bad) break;
+    evaluate();
+  }
+  for (int i = 0; i < s.nch; i++)
+    if (std::isfinite(s.c[i])) return true;
+  return false;
+}
+
+// Diagnostics (bartrt_mcmc_draws): every draw of chain i at iteration t among nch chains, as doubles:
+// out[0..4] the uniforms of r1, r2, z, gamma and acceptance, out[5] log of the acceptance uniform, out[6..8] the
+// partners r1, r2, z (z = -1 with fewer than four chains), out[9 + j] the jitter normal of parameter j.
+constexpr int kDrawsHead = 9;
+MCMC_HD void draws_row(unsigned long long seed, unsigned long long t, int nch, int i, int npars, double *out) {
+  double unused;
+  uniforms(seed, t, i, kSlotPartners, out[0], out[1]);
+  uniforms(seed, t, i, kSlotSnooker, out[2], out[3]);
+  uniforms(seed, t, i, kSlotAccept, out[4], unused);
+  out[5] = log(out[4]);
+  const int r1 = nch > 1 ? other(out[0], nch, i, -1, -1) : i;
+  const int r2 = nch > 2 ? other(out[1], nch, i, r1, -1) : r1;
+  out[6] = r1;
+  out[7] = r2;
+  out[8] = nch > 3 ? other(out[2], nch, i, r1, r2) : -1;
+  for (int j = 0; j < npars; j += 2) {
+    double n0, n1;
+    normals(seed, t, i, kSlotJitter + j / 2, n0, n1);
+    out[kDrawsHead + j] = n0;
+    if (j + 1 < npars) out[kDrawsHead + j + 1] = n1;
+  }
+}
+
+}  // namespace mcmc
+}  // namespace bartrt

@@ -86,5 +86,24 @@ void mcmc_run(Engine &e, int nchains, int npars, long nsteps, const double *para
               const double *pmax, const double *stepsize, int ndata, const double *data,
               const double *uncert, int snooker, unsigned long long seed, double *chain,
               double *chisq, long *naccept, long *nbad);
+// The same sampler resident on the GPU (mcmc.hip; arithmetic in mcmc_core.hpp): per iteration one mcmc_advance
+// launch and one step_run_dev, enqueued without a host wait, in blocks of `block` iterations, two blocks in flight.
+struct McmcOpts {
+  int snooker = 0;
+  unsigned long long seed = 0;
+  long thin = 1, block = 256;
+  const double *prior = nullptr, *priorlow = nullptr, *priorup = nullptr;   // [npars], all or none
+  void (*progress)(long iterations, long naccept, void *user) = nullptr;   // per finished block
+  void *progress_user = nullptr;
+};
+// chain[nchains][nkept][npars], chisq[nchains][nkept], models[nchains][nkept][ndata] (may be null),
+// nkept = ceil(nsteps / thin).  Bad sizes or stepsizes: std::invalid_argument
+void mcmc_run_resident(Engine &e, int nchains, int npars, long nsteps, const double *params, const double *pmin,
+                       const double *pmax, const double *stepsize, int ndata, const double *data,
+                       const double *uncert, const McmcOpts &opts, double *chain, double *chisq, double *models,
+                       long *naccept, long *nbad);
+// diagnostics (bartrt_mcmc_draws): the core's draws of chains 0 .. nchains - 1 at iteration t, evaluated on the
+// device: out[nchains][9 + npars] (mcmc_core.hpp, draws_row); needs no engine
+void mcmc_draws_probe(unsigned long long seed, unsigned long long t, int nchains, int npars, double *out);
 
 }  // namespace bartrt

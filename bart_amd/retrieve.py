@@ -12,7 +12,11 @@ the library's own communicator and runs the native loop on every rank in
 lockstep (include/bartrt.h, bartrt_comm_init).  Reads the
 reference's ``[MCMC]`` keys (examples/demo/BART_eclipse.cfg) and writes
 ``output.npy`` (posterior sample [nchains, nsteps, npars]), ``bestFit.txt`` and
-``MCMC.log`` in the output directory.
+``MCMC.log`` in the output directory.  ``--resident`` runs the sampler resident
+on the GPU (sampler.run_resident) and also honours ``prior`` / ``priorlow`` /
+``priorup``, negative (shared) stepsizes, ``thinning`` and ``savemodel`` (the band
+fluxes of every kept sample, [nchains, ndata, nkept], written under that file's
+name in the output directory).
 """
 from __future__ import annotations
 
@@ -35,6 +39,9 @@ def main(argv=None):
     ap.add_argument("--native-sharded", action="store_true",
                     help="with WORLD_SIZE > 1: attach the library's communicator and run the native loop on every "
                          "rank (one collective per step inside the library) instead of the Python loop")
+    ap.add_argument("--resident", action="store_true",
+                    help="run the sampler resident on the GPU (sampler.run_resident): reproducible draws, shared "
+                         "parameters, priors, thinning and the `savemodel` array of the configuration")
     a = ap.parse_args(argv)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -62,9 +69,14 @@ def main(argv=None):
     if native and world > 1:
         from . import engine
         engine.comm_init()
-    res = sampler.run_native(w, scfg, log=log) if native else sampler.run(w.step, scfg, log=log)
+    if a.resident and not native:
+        ap.error("--resident runs the native way: not with --python-loop, and on several ranks only with --native-sharded")
+    if a.resident:
+        res = sampler.run_resident(w, scfg, log=log)
+    else:
+        res = sampler.run_native(w, scfg, log=log) if native else sampler.run(w.step, scfg, log=log)
     dt = time.perf_counter() - t0
-    nmodel = res["chain"].shape[0] * res["chain"].shape[1]
+    nmodel = scfg.nchains * max(1, int(np.ceil(scfg.numit / scfg.nchains)))   # (a thinned chain holds fewer rows)
     log("%d models in %.2f s (%.0f models/s); acceptance %.3f; best chisq %.4f" % (
         nmodel, dt, nmodel / dt, res["accept_rate"], res["best_chisq"]))
     if res["grstat"] is not None:
@@ -77,6 +89,10 @@ def main(argv=None):
         with open(os.path.join(out, "bestFit.txt"), "w") as f:
             f.write("# best-fit parameters, chisq = %.6f\n" % res["best_chisq"])
             f.write(" ".join("%.8g" % p for p in res["bestp"]) + "\n")
+        if a.resident and native and scfg.savemodel:
+            # MC3's layout of `savemodel`: [nchains, ndata, nkept]
+            np.save(os.path.join(out, os.path.basename(scfg.savemodel)),
+                    np.ascontiguousarray(res["models"].transpose(0, 2, 1)))
         with open(os.path.join(out, "MCMC.log"), "w") as f:
             f.write("\n".join(lines) + "\n")
     w.close()

@@ -19,6 +19,7 @@ spectrum and the all-gather inside the model call reassembles them.
 from __future__ import annotations
 
 import configparser
+import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
@@ -38,6 +39,12 @@ class SamplerConfig:
     walk: str = "demc"
     grtest: bool = True
     seed: int = 0
+    # read by run_resident alone (MC3's keys of the same names; `thinning`, `savemodel`)
+    prior: np.ndarray | None = None
+    priorlow: np.ndarray | None = None
+    priorup: np.ndarray | None = None
+    thinning: int = 1
+    savemodel: str | None = None
 
     @classmethod
     def from_cfg(cls, path: str, section: str = "MCMC") -> "SamplerConfig":
@@ -51,7 +58,11 @@ class SamplerConfig:
                    nchains=int(d.get("nchains", 10)), numit=int(float(d.get("numit", 10000))),
                    burnin=int(d.get("burnin", 500)), walk=d.get("walk", "demc"),
                    grtest=d.get("grtest", "True").strip() == "True",
-                   seed=int(d.get("seed", 0)))
+                   seed=int(d.get("seed", 0)),
+                   prior=arr("prior") if "prior" in d else None,
+                   priorlow=arr("priorlow") if "priorlow" in d else None,
+                   priorup=arr("priorup") if "priorup" in d else None,
+                   thinning=int(d.get("thinning", 1)), savemodel=d.get("savemodel") or None)
 
 
 def gelman_rubin(chains: np.ndarray) -> np.ndarray:
@@ -227,3 +238,91 @@ def run_native(worker, cfg: SamplerConfig, log=None):
     gr = gelman_rubin(post[:, :, free]) if cfg.grtest and post.shape[1] > 3 and nch > 1 else None
     return {"chain": chain, "chisq": chis, "bestp": chain[ib], "best_chisq": float(chis[ib]),
             "accept_rate": nacc.value / (nsteps * nch), "grstat": gr, "free": free}
+
+
+class McmcOpts(C.Structure):
+    """``bartrt_mcmc_opts`` of include/bartrt.h."""
+    _fields_ = [("size", C.c_ulong), ("snooker", C.c_int), ("seed", C.c_ulonglong), ("thin", C.c_long),
+                ("block", C.c_long), ("prior", C.c_void_p), ("priorlow", C.c_void_p), ("priorup", C.c_void_p),
+                ("progress", C.c_void_p), ("progress_user", C.c_void_p)]
+
+
+PROGRESS = C.CFUNCTYPE(None, C.c_long, C.c_long, C.c_void_p)
+
+
+def draws(seed: int, t: int, nchains: int, npars: int) -> np.ndarray:
+    """The resident sampler's draws of every chain at iteration ``t``, evaluated on the device
+    (``bartrt_mcmc_draws``): [nchains, 9 + npars], columns as csrc/mcmc_core.hpp's ``draws_row``."""
+    from . import transit_module as trm
+    out = np.zeros((nchains, 9 + npars))
+    trm.check(trm.lib().bartrt_mcmc_draws(C.c_ulonglong(seed), C.c_ulonglong(t), nchains, npars,
+                                          out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def run_resident(worker, cfg: SamplerConfig, log=None, block: int = 256):
+    """The sampler resident on the GPU through ``bartrt_mcmc_run_resident`` (csrc/mcmc.hip, csrc/mcmc_core.hpp):
+    population, chi-squares and counters stay in device memory and an iteration is one small sampler launch plus the
+    model's launches, enqueued without a host wait, ``block`` iterations at a time.  Its draws come from a
+    counter-based generator keyed by ``cfg.seed``: a run can be restated draw for draw (tests/mcmc_restate.py); the
+    stream is not :func:`run_native`'s.  Of the three loops only this one takes shared parameters (``stepsize = -k``:
+    a copy of parameter k, counted from 1), Gaussian priors (``prior``, ``priorlow``, ``priorup``; ``chisq`` then
+    holds the data term plus the prior terms), ``thinning`` and the per-sample band fluxes of ``savemodel``.  At most
+    1024 chains and 64 parameters.  Sharded engines as :func:`run_native`: with the library's communicator every rank
+    makes this call in lockstep and gets the same chains.
+
+    Speed: SLOWER than :func:`run_native` as measured (MEASUREMENTS.md row 17; one MI355X, ten chains, snooker):
+    7 745 against 9 045 iterations/s on the headline shape, 10 948 against 15 528 on the WASP-12b shape, 11 163
+    against 14 896 on the demo shape -- the one-lane-per-chain sampler launch costs more than the host round trip it
+    removes.  Opt-in for what else it gives; :func:`run_native` stays the default.
+
+    Returns the dictionary of :func:`run_native` (``chain`` [nchains, nkept, npars], ``chisq`` [nchains, nkept],
+    nkept = ceil(nsteps / thinning)) plus ``models`` [nchains, nkept, ndata]: the band fluxes of each chain's current
+    state at the kept iterations."""
+    from . import engine, transit_module as trm
+    lo, hi = engine.local_range()
+    if hi - lo != worker.nwave and engine.comm_info()["nranks"] == 0:
+        raise ValueError("run_resident: the engine is sharded and has no communicator (engine.comm_init); use run()")
+    nch = cfg.nchains
+    nsteps = max(1, int(np.ceil(cfg.numit / nch)))
+    thin = max(1, int(cfg.thinning))
+    nkept = -(-nsteps // thin)
+    npars = len(cfg.params)
+    a = lambda v: np.ascontiguousarray(v, np.double)
+    par, pmin, pmax, step = a(cfg.params), a(cfg.pmin), a(cfg.pmax), a(cfg.stepsize)
+    data, unc = a(cfg.data), a(cfg.uncert)
+    ptr = lambda v: v.ctypes.data_as(C.c_void_p)
+    opts = McmcOpts(size=C.sizeof(McmcOpts), snooker=int(cfg.walk == "snooker"), seed=cfg.seed, thin=thin, block=block)
+    given = [v is not None for v in (cfg.prior, cfg.priorlow, cfg.priorup)]
+    if any(given):
+        if not all(given):
+            raise ValueError("run_resident: prior, priorlow and priorup come together")
+        pri = [a(v) for v in (cfg.prior, cfg.priorlow, cfg.priorup)]
+        if any(v.shape != par.shape for v in pri):
+            raise ValueError("run_resident: prior, priorlow and priorup have one value per parameter")
+        opts.prior, opts.priorlow, opts.priorup = (v.ctypes.data for v in pri)
+    if any(v.shape != par.shape for v in (pmin, pmax, step)) or unc.shape != data.shape:
+        raise ValueError("run_resident: pmin, pmax and stepsize have one value per parameter, uncert one per datum")
+    if log is not None:
+        report = PROGRESS(lambda it, acc, _: log("step %d/%d  acceptance %.2f" % (it, nsteps, acc / (it * nch))))
+        opts.progress = C.cast(report, C.c_void_p)
+    chain = np.zeros((nch, nkept, npars))
+    chis = np.zeros((nch, nkept))
+    models = np.zeros((nch, nkept, len(data)))
+    nacc = C.c_long(0)
+    nbad = (C.c_long * 4)()
+    trm.check(trm.lib().bartrt_mcmc_run_resident(
+        nch, npars, C.c_long(nsteps), ptr(par), ptr(pmin), ptr(pmax), ptr(step), len(data), ptr(data), ptr(unc),
+        C.cast(C.byref(opts), C.c_void_p), ptr(chain), ptr(chis), ptr(models),
+        C.cast(C.byref(nacc), C.c_void_p), C.cast(nbad, C.c_void_p)))
+    for k in (1, 2, 3):
+        worker.nbad[k] += int(nbad[k])
+    free = np.where(cfg.stepsize > 0)[0]
+    if log is not None:
+        log("%d iterations of %d chains; best chisq %.4f  acceptance %.2f" % (
+            nsteps, nch, float(chis.min()), nacc.value / (nsteps * nch)))
+    ib = np.unravel_index(np.argmin(chis), chis.shape)
+    post = chain[:, min(cfg.burnin // thin, nkept - 1):]
+    gr = gelman_rubin(post[:, :, free]) if cfg.grtest and post.shape[1] > 3 and nch > 1 else None
+    return {"chain": chain, "chisq": chis, "bestp": chain[ib], "best_chisq": float(chis[ib]),
+            "accept_rate": nacc.value / (nsteps * nch), "grstat": gr, "free": free, "models": models}

@@ -78,6 +78,10 @@ def lib():
         L.bartrt_step_set_extras.argtypes = [i, i, i]
         L.bartrt_step_batch.argtypes = [p, i, i, p, p]
         L.bartrt_mcmc_run.argtypes = [i, i, C.c_long, p, p, p, p, i, p, p, i, C.c_ulonglong, p, p, p, p]
+        # (an A/B library built from an earlier commit, BARTRT_LIBPATH, lacks these two: calling them then fails by name)
+        if hasattr(L, "bartrt_mcmc_run_resident"):
+            L.bartrt_mcmc_run_resident.argtypes = [i, i, C.c_long, p, p, p, p, i, p, p, p, p, p, p, p, p]
+            L.bartrt_mcmc_draws.argtypes = [C.c_ulonglong, C.c_ulonglong, i, i, p]
         L.bartrt_step_batch_dev.argtypes = [p, i, i, p, p, p, p]
         L.bartrt_step_profiles_dev.argtypes = [p, i, i, p, p, p]
         L.bartrt_step_bandflux_dev.argtypes = [p, i, p, p, p]

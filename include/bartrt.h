@@ -272,6 +272,50 @@ int bartrt_mcmc_run(int nchains, int npars, long nsteps, const double *params, c
                     const double *pmax, const double *stepsize, int ndata, const double *data,
                     const double *uncert, int snooker, unsigned long long seed, double *chain,
                     double *chisq, long *naccept, long *nbad);
+/* The same sampler RESIDENT on the GPU: population, chi-squares and counters stay in device memory, and an iteration
+ * is one small sampler launch (one workgroup, chain i on lane i) followed by the model's launches, enqueued without a
+ * host wait -- the host works `block` iterations at a time and keeps at most two blocks in flight.  Arguments as
+ * bartrt_mcmc_run, and:
+ *   - the random draws come from a counter-based generator (Philox4x32-10 keyed by `seed`, counter = iteration,
+ *     chain, slot; bart_amd/csrc/mcmc_core.hpp has the table), so a run can be restated draw for draw anywhere; its
+ *     stream is not bartrt_mcmc_run's;
+ *   - stepsize[j] = -k (MC3's convention, k counted from 1) makes parameter j a copy of parameter k - 1 in every
+ *     proposal and start point; a target out of range or itself shared is BARTRT_EINVAL;
+ *   - prior / priorlow / priorup ([npars], all three or none): where priorlow[j] != 0, chi-square gains
+ *     ((p_j - prior_j) / sigma)^2 with sigma = priorlow[j] below prior_j and priorup[j] above.  THE chisq ARRAY HOLDS
+ *     THE DATA TERM PLUS THESE TERMS;
+ *   - thin = n writes every n-th iteration: rows t = n - 1, 2n - 1, ... and the last one, nkept = ceil(nsteps / n);
+ *   - a proposal outside [pmin, pmax] is not sent to the model (the launch gets the chain's current point in its
+ *     place, so every launch has nchains rows) and is not counted in nbad;
+ *   - progress (may be NULL) is called after every finished block with the iterations done and the proposals
+ *     accepted so far.
+ * chain[nchains][nkept][npars], chisq[nchains][nkept]; models (may be NULL) [nchains][nkept][ndata]: the band fluxes
+ * of each chain's CURRENT state at the kept iterations (what MC3's `savemodel` holds).  opts may be NULL (demc, seed
+ * 0, thin 1, block 256, uniform priors); set opts->size = sizeof(bartrt_mcmc_opts) -- fields past `size` read as zero.
+ * At most 1024 chains and 64 parameters (BARTRT_EINVAL beyond; larger populations stay with bartrt_mcmc_run).
+ * Sharded engines: whatever the step serves.  LOCKSTEP as for bartrt_mcmc_run: with a communicator attached every
+ * rank makes this call with the same arguments, the step's all-gather leaves the same band-flux bits on every rank,
+ * so every rank advances the same population and writes the same chain.  Chain-service clients and line-by-line
+ * engines with a communicator: BARTRT_ENOTSUP. */
+typedef struct bartrt_mcmc_opts {
+  unsigned long size;                 /* sizeof(bartrt_mcmc_opts) of the caller */
+  int snooker;                        /* 0: demc, 1: snooker */
+  unsigned long long seed;
+  long thin;                          /* 0 reads as 1 */
+  long block;                         /* iterations per block; 0 reads as 256 */
+  const double *prior, *priorlow, *priorup;
+  void (*progress)(long iterations, long naccept, void *user);
+  void *progress_user;
+} bartrt_mcmc_opts;
+int bartrt_mcmc_run_resident(int nchains, int npars, long nsteps, const double *params, const double *pmin,
+                             const double *pmax, const double *stepsize, int ndata, const double *data,
+                             const double *uncert, const bartrt_mcmc_opts *opts, double *chain, double *chisq,
+                             double *models /* NULL */, long *naccept, long *nbad);
+/* Diagnostics: the sampler's draws of chains 0 .. nchains - 1 at iteration t, evaluated ON THE DEVICE (its log, sqrt,
+ * sin and cos): out[nchains][9 + npars] = the uniforms of r1, r2, z, gamma and acceptance, log of the acceptance
+ * uniform, the partners r1, r2, z (z = -1 with fewer than four chains) and the jitter normal of each parameter.
+ * Needs no engine. */
+int bartrt_mcmc_draws(unsigned long long seed, unsigned long long t, int nchains, int npars, double *out);
 /* Device-resident form; d_status and d_spec ([nwalkers][nwave]) may be NULL. */
 int bartrt_step_batch_dev(const double *d_params, int nwalkers, int npars,
                           double *d_bandflux, int *d_status, double *d_spec,
