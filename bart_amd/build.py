@@ -12,14 +12,16 @@ LIB = os.path.join(HERE, "libbartrt.so")
 CLI = os.path.join(HERE, "transit")
 SOURCES = ["rt_eclipse_angles.hip", "rt_eclipse_slant_ilp.hip", "rt_eclipse_qadj.hip", "rt_eclipse_i0.hip", "rt_eclipse_i1.hip", "rt_eclipse_i2.hip", "rt_eclipse_i0_ilp.hip", "rt_eclipse_i1_ilp.hip", "lbl.hip",
            "transit_geom.hip", "contrib.hip",
-           "kernels.hip", "capi.hip", "engine.hip", "step.hip", "comm.hip", "mcmc.hip", "share.hip", "svc.hip", "rtc.hip", "io.cpp"]   # longest first
-HEADERS = ["engine.hpp", "kernels.hpp", "rt_eclipse.hpp", "rt_launch.hpp", "rt_eclipse_unit.inc", "rt_eclipse_s1.hpp", "rt_eclipse_s1s.hpp", "rt_eclipse_qadj.hpp", "kernel_table.inc", "imw_tab.hpp", "integ.hpp", "step.hpp", "mcmc_core.hpp", "lbl.hpp", "voigt_coef.hpp", "expint_coef.hpp", "prep.hpp", "io.hpp", "share.hpp", "svc.hpp", "svc_core.hpp", "rtc.hpp", "contrib.hpp", "comm.hpp", "devbuf.hpp", "lds.hpp",
+           "kernels.hip", "capi.hip", "engine.hip", "step.hip", "comm.hip", "mcmc.hip", "fit.hip", "share.hip", "svc.hip", "rtc.hip", "io.cpp"]   # longest first
+HEADERS = ["engine.hpp", "kernels.hpp", "rt_eclipse.hpp", "rt_launch.hpp", "rt_eclipse_unit.inc", "rt_eclipse_s1.hpp", "rt_eclipse_s1s.hpp", "rt_eclipse_qadj.hpp", "kernel_table.inc", "imw_tab.hpp", "integ.hpp", "step.hpp", "mcmc_core.hpp", "fit_core.hpp", "lbl.hpp", "voigt_coef.hpp", "expint_coef.hpp", "prep.hpp", "io.hpp", "share.hpp", "svc.hpp", "svc_core.hpp", "rtc.hpp", "contrib.hpp", "comm.hpp", "devbuf.hpp", "lds.hpp",
            "transit_main.cpp", "../../include/bartrt.h"]
 
 
 # per-file compiler options (see the comment on rt_eclipse_fast in csrc/rt_eclipse.hpp)
 ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
-EXTRA_FLAGS = {"rt_eclipse_i0_ilp.hip": ILP, "rt_eclipse_i1_ilp.hip": ILP, "rt_eclipse_slant_ilp.hip": ILP}
+EXTRA_FLAGS = {"rt_eclipse_i0_ilp.hip": ILP, "rt_eclipse_i1_ilp.hip": ILP, "rt_eclipse_slant_ilp.hip": ILP,
+               # the optimiser's sums carry the same roundings on the device as in the host build of fit_core.hpp
+               "fit.hip": ["-ffp-contract=off"]}
 # rt_eclipse_angles.hip is compiled once per ray-grid size other than five that is wanted AHEAD OF TIME: (object name,
 # flags).  None by default since round 6: every BASELINE config and every reference example uses the five-angle grid
 # (examples/demo/BART_eclipse.cfg:135), the eight other sizes were 39 MB of objects, and hiprtc instantiates any size

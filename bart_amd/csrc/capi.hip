@@ -1008,6 +1008,58 @@ int bartrt_mcmc_draws(unsigned long long seed, unsigned long long t, int nchains
   });
 }
 
+// the caller's bartrt_fit_opts (maybe an older, shorter one) as FitOpts; zero fields read as the defaults
+static bool fit_opts_of(const bartrt_fit_opts *opts, FitOpts &m) {
+  bartrt_fit_opts o;
+  std::memset(&o, 0, sizeof o);
+  if (opts) {
+    if (opts->size < sizeof(opts->size)) return false;
+    std::memcpy(&o, opts, opts->size < sizeof o ? opts->size : sizeof o);
+  }
+  if (o.maxiter) m.maxiter = o.maxiter < 0 ? 0 : o.maxiter;
+  if (o.nrungs) m.nrungs = o.nrungs;
+  if (o.check) m.check = o.check;
+  if (o.fdstep != 0) m.fdstep = o.fdstep;
+  if (o.ftol != 0) m.ftol = o.ftol;
+  if (o.xtol != 0) m.xtol = o.xtol;
+  if (o.lambda0 != 0) m.lambda0 = o.lambda0;
+  m.prior = o.prior; m.priorlow = o.priorlow; m.priorup = o.priorup;
+  m.trace = o.trace;
+  return true;
+}
+
+int bartrt_fit(int nstarts, int npars, const double *starts, const double *pmin, const double *pmax,
+               const double *stepsize, int ndata, const double *data, const double *uncert,
+               const bartrt_fit_opts *opts, double *best, double *chisq, int *status, long *niter, long *nbad) {
+  NEED_ENGINE();
+  if (!g_eng->step) return fail(BARTRT_EINVAL, "fit: call bartrt_step_setup first");
+  if (!starts || !pmin || !pmax || !stepsize || !data || !uncert || !best || !chisq)
+    return fail(BARTRT_EINVAL, "fit: null buffer");
+  FitOpts m;
+  if (!fit_opts_of(opts, m)) return fail(BARTRT_EINVAL, "fit: set opts->size");
+  return guarded([&] {
+    fit_run(*g_eng, nstarts, npars, starts, pmin, pmax, stepsize, ndata, data, uncert, m, best, chisq, status, niter,
+            nbad);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_fit_probe(int nstarts, int npars, const double *pmin, const double *pmax, const double *stepsize,
+                     int ndata, const double *data, const double *uncert, const bartrt_fit_opts *opts,
+                     const double *x, const double *lambda, double *D, const double *cur, const double *pband,
+                     const int *pstatus, double *trial, int *valid) {
+  if (!pmin || !pmax || !stepsize || !data || !uncert || !x || !lambda || !D || !cur || !pband || !pstatus ||
+      !trial || !valid)
+    return fail(BARTRT_EINVAL, "bartrt_fit_probe: null buffer");
+  FitOpts m;
+  if (!fit_opts_of(opts, m)) return fail(BARTRT_EINVAL, "bartrt_fit_probe: set opts->size");
+  return guarded([&] {
+    fit_probe(nstarts, npars, pmin, pmax, stepsize, ndata, data, uncert, m, x, lambda, D, cur, pband, pstatus, trial,
+              valid);
+    return BARTRT_OK;
+  });
+}
+
 // ---- the ranks' communicator (comm.hip) -----------------------------------
 int bartrt_comm_get_unique_id(void *id) {
   // (needs no engine: rank 0 may ask before its bartrt_init; a chain-service client gets what every non-reference

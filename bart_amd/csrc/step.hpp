@@ -105,5 +105,27 @@ void mcmc_run_resident(Engine &e, int nchains, int npars, long nsteps, const dou
 // diagnostics (bartrt_mcmc_draws): the core's draws of chains 0 .. nchains - 1 at iteration t, evaluated on the
 // device: out[nchains][9 + npars] (mcmc_core.hpp, draws_row); needs no engine
 void mcmc_draws_probe(unsigned long long seed, unsigned long long t, int nchains, int npars, double *out);
+// Batched multi-start Levenberg-Marquardt fit in the box (fit.hip; arithmetic in fit_core.hpp): per iteration the
+// S * nfree forward-difference rows and the S * nrungs trial rows in one step_run_dev each, one fit_advance launch
+// (one wave per start) after either, no host wait but every `check` iterations.
+struct FitOpts {
+  long maxiter = 50, check = 4;
+  int nrungs = 4;
+  double fdstep = 1e-2, ftol = 1e-10, xtol = 1e-10, lambda0 = 1e-3;
+  const double *prior = nullptr, *priorlow = nullptr, *priorup = nullptr;   // [npars], all or none
+  double *trace = nullptr;   // [nstarts][maxiter + 1][npars + 4]: x, chisq, lambda, chosen rung, status after each pick
+};
+// starts, best [nstarts][npars]; chisq, status (fit_core.hpp: Status), niter [nstarts]; nbad[4] (status, niter and
+// nbad may be null).  Bad sizes, options or stepsizes: std::invalid_argument
+void fit_run(Engine &e, int nstarts, int npars, const double *starts, const double *pmin, const double *pmax,
+             const double *stepsize, int ndata, const double *data, const double *uncert, const FitOpts &opts,
+             double *best, double *chisq, int *status, long *niter, long *nbad);
+// diagnostics (bartrt_fit_probe): the solve phase of fit_advance once, on the device, for nstarts starts at x
+// [nstarts][npars] with damping lambda [nstarts] and scaling D [nstarts][npars] (updated in place), from the band
+// fluxes cur [nstarts][ndata] at x and pband [nstarts][nfree][ndata], pstatus [nstarts][nfree] of the forward-difference
+// rows: trial [nstarts][nrungs][npars] and valid [nstarts] (bit k: rung k).  Needs no engine
+void fit_probe(int nstarts, int npars, const double *pmin, const double *pmax, const double *stepsize, int ndata,
+               const double *data, const double *uncert, const FitOpts &opts, const double *x, const double *lambda,
+               double *D, const double *cur, const double *pband, const int *pstatus, double *trial, int *valid);
 
 }  // namespace bartrt

@@ -45,6 +45,10 @@ class SamplerConfig:
     priorup: np.ndarray | None = None
     thinning: int = 1
     savemodel: str | None = None
+    # read by retrieve (MC3's keys of the same names): a least-squares fit before the chain (fit.fit), and the
+    # uncertainties rescaled to a reduced chi-square of one at its optimum
+    leastsq: bool = False
+    chisqscale: bool = False
 
     @classmethod
     def from_cfg(cls, path: str, section: str = "MCMC") -> "SamplerConfig":
@@ -62,7 +66,9 @@ class SamplerConfig:
                    prior=arr("prior") if "prior" in d else None,
                    priorlow=arr("priorlow") if "priorlow" in d else None,
                    priorup=arr("priorup") if "priorup" in d else None,
-                   thinning=int(d.get("thinning", 1)), savemodel=d.get("savemodel") or None)
+                   thinning=int(d.get("thinning", 1)), savemodel=d.get("savemodel") or None,
+                   leastsq=d.get("leastsq", "False").strip() == "True",
+                   chisqscale=d.get("chisqscale", "False").strip() == "True")
 
 
 def gelman_rubin(chains: np.ndarray) -> np.ndarray:
@@ -77,11 +83,11 @@ def gelman_rubin(chains: np.ndarray) -> np.ndarray:
 
 def _check_stepsize(stepsize):
     """MC3 reads a negative stepsize as "shared with parameter -stepsize" (its
-    `stepsize` key, examples/demo/BART_eclipse.cfg:84-87); shared parameters are
-    not implemented here and must not be mistaken for fixed ones."""
+    `stepsize` key, examples/demo/BART_eclipse.cfg:84-87); run and run_native do
+    not implement shared parameters and must not mistake them for fixed ones."""
     if (np.asarray(stepsize) < 0).any():
-        raise ValueError("stepsize < 0 (a parameter shared with another one, in MC3's convention) "
-                         "is not supported: give every parameter its own stepsize, or 0 to fix it")
+        raise ValueError("stepsize < 0 (a parameter shared with another one, in MC3's convention) is served by "
+                         "run_resident and fit.fit alone: here give every parameter its own stepsize, or 0 to fix it")
 
 
 def run(model, cfg: SamplerConfig, log=None):

@@ -8,7 +8,9 @@
   3. retrieve them back with the batched sampler (all chains per GPU call),
   4. print truth, posterior mean and width per fitted parameter.
 
-    python examples/demo_retrieval.py [workdir] [--numit 200000] [--nchains 10]
+    python examples/demo_retrieval.py [workdir] [--numit 200000] [--nchains 10] [--leastsq]
+
+--leastsq starts away from the truth and runs the multi-start least-squares fit (bart_amd.fit) before the chain.
 """
 import argparse
 import os
@@ -27,6 +29,7 @@ def main():
     ap.add_argument("workdir", nargs="?", default=os.path.join(tempfile.gettempdir(), "bart_amd_demo"))
     ap.add_argument("--numit", type=int, default=200000)
     ap.add_argument("--nchains", type=int, default=10)
+    ap.add_argument("--leastsq", action="store_true", help="fit before the chain, from a start off the truth")
     a = ap.parse_args()
     names = ["log kappa", "log g1", "log g2", "alpha", "beta", "log CH4"]
     truth = np.array([-2.0, 0.0, 1.0, 0.0, 0.98, -0.5])          # BART_eclipse.cfg:80
@@ -42,6 +45,15 @@ def main():
             stepsize=np.array([0.01, 0.01, 0.0, 0.0, 0.001, 0.1]),   # :83
             data=depths, uncert=0.02 * depths, nchains=a.nchains, numit=a.numit,
             burnin=a.numit // a.nchains // 5, walk="snooker", seed=1)
+        if a.leastsq:
+            from bart_amd import fit
+            scfg.params = truth + np.array([0.3, -0.2, 0.0, 0.0, 0.02, -1.0])
+            t0 = time.perf_counter()
+            best = fit.fit(worker, scfg, nstarts=a.nchains, seed=1)
+            print("least-squares fit of %d starts in %.1f ms: %s" % (
+                a.nchains, 1e3 * (time.perf_counter() - t0), ", ".join(fit.STATUS[s] for s in best["status"])))
+            print("optimum (chisq %.3g): %s" % (best["best_chisq"], " ".join("%.4f" % p for p in best["bestp"])))
+            scfg.params = best["bestp"].copy()
         t0 = time.perf_counter()
         res = sampler.run_native(worker, scfg, log=print)
         dt = time.perf_counter() - t0

@@ -316,6 +316,44 @@ int bartrt_mcmc_run_resident(int nchains, int npars, long nsteps, const double *
  * uniform, the partners r1, r2, z (z = -1 with fewer than four chains) and the jitter normal of each parameter.
  * Needs no engine. */
 int bartrt_mcmc_draws(unsigned long long seed, unsigned long long t, int nchains, int npars, double *out);
+/* Least-squares fit before the chain (MC3's `leastsq`): nstarts independent Levenberg-Marquardt fits inside the box
+ * [pmin, pmax], advanced together on the GPU.  An iteration is two batched model launches -- the nstarts * nfree
+ * forward-difference rows of the Jacobians (h_j = fdstep * stepsize_j, the sign flipped at the upper bound), then the
+ * nstarts * nrungs trial points of a ladder of dampings lambda 10^(k-1) -- with one small kernel after each (one wave
+ * per start; bart_amd/csrc/fit_core.hpp states every decision).  The host waits only every `check` iterations.
+ * starts[nstarts][npars]; pmin, pmax, stepsize (0: fixed, -k: a copy of parameter k, as bartrt_mcmc_run_resident),
+ * data, uncert as bartrt_mcmc_run.  With the three prior arrays, every parameter with a non-zero priorlow or priorup
+ * adds the residual (p_j - prior_j) / width, the width of its side (a zero width does not constrain that side); chisq
+ * is the sum of squares of all residuals.  Results: best[nstarts][npars], chisq[nstarts], and (each may be NULL)
+ * status[nstarts] (BARTRT_FIT_*), niter[nstarts] iterations made, nbad[4] models rejected with status 1, 2, 3.
+ * opts may be NULL; set opts->size = sizeof(bartrt_fit_opts); a zero field reads as its default (maxiter 50: give a
+ * negative maxiter for none, nrungs 4 (1 to 8), check 4, fdstep 1e-2, ftol 1e-10, xtol 1e-10, lambda0 1e-3).
+ * trace (may be NULL): [nstarts][maxiter + 1][npars + 4] doubles, after the start's own model (record 0) and after
+ * every iteration: x, chisq, lambda, the rung taken (-1: none), status.  Records after every start has finished
+ * repeat the last.  At most 64 parameters.  Sharded engines and LOCKSTEP as for bartrt_mcmc_run_resident. */
+enum { BARTRT_FIT_RUNNING = 0, BARTRT_FIT_CONVERGED = 1, BARTRT_FIT_STALLED = 2, BARTRT_FIT_MAXITER = 3,
+       BARTRT_FIT_NO_START = 4 };
+typedef struct bartrt_fit_opts {
+  unsigned long size;                 /* sizeof(bartrt_fit_opts) of the caller */
+  long maxiter;
+  int nrungs;
+  long check;
+  double fdstep, ftol, xtol, lambda0;
+  const double *prior, *priorlow, *priorup;
+  double *trace;
+} bartrt_fit_opts;
+int bartrt_fit(int nstarts, int npars, const double *starts, const double *pmin, const double *pmax,
+               const double *stepsize, int ndata, const double *data, const double *uncert,
+               const bartrt_fit_opts *opts, double *best, double *chisq, int *status, long *niter, long *nbad);
+/* Diagnostics: the solve phase of the fit's kernel once ON THE DEVICE, for nstarts starts at x[nstarts][npars] with
+ * damping lambda[nstarts] and scaling D[nstarts][npars] (updated in place), from the band fluxes cur[nstarts][ndata]
+ * at x and pband[nstarts][nfree][ndata], pstatus[nstarts][nfree] of the forward-difference rows.  Gives
+ * trial[nstarts][nrungs][npars] and valid[nstarts] (bit k set: rung k factored).  Of opts it reads nrungs, fdstep and
+ * the priors.  Needs no engine. */
+int bartrt_fit_probe(int nstarts, int npars, const double *pmin, const double *pmax, const double *stepsize,
+                     int ndata, const double *data, const double *uncert, const bartrt_fit_opts *opts,
+                     const double *x, const double *lambda, double *D, const double *cur, const double *pband,
+                     const int *pstatus, double *trial, int *valid);
 /* Device-resident form; d_status and d_spec ([nwalkers][nwave]) may be NULL. */
 int bartrt_step_batch_dev(const double *d_params, int nwalkers, int npars,
                           double *d_bandflux, int *d_status, double *d_spec,
