@@ -606,6 +606,20 @@ int bartrt_get_lbl_extinction(const double *prof, int nprof, double *ext, int nl
   });
 }
 
+int bartrt_lbl_owners(const double *prof, int nprof, unsigned char *owners, int nlayers, int ntile) {
+  NEED_ENGINE();
+  Engine *e = g_eng;
+  if (!e->lbl) return fail(BARTRT_EINVAL, "lbl_owners: the engine was not set up with a line list");
+  if (!prof || !owners || nprof != (e->S + 1) * e->L || nlayers != e->L || ntile != (e->W() + 255) / 256)
+    return fail(BARTRT_EINVAL, "lbl_owners: bad shapes");
+  return guarded([&] {
+    e->ensure_walkers(1);
+    HIPCHK(hipMemcpy(e->d_prof, prof, sizeof(double) * nprof, hipMemcpyHostToDevice));
+    lbl_owners(*e, e->d_prof, 1, owners);
+    return BARTRT_OK;
+  });
+}
+
 int bartrt_voigt(const double *x, const double *y, double *k, long n) {
   if (n < 0 || (n > 0 && (!x || !y || !k))) return fail(BARTRT_EINVAL, "bartrt_voigt: bad arguments");
   return guarded([&] {

@@ -1148,6 +1148,39 @@ __global__ __launch_bounds__(256) void lbl_rt_eclipse_k(LblDev d, const double *
 }
 
 // ---------------------------------------------------------------------------
+// Diagnostics (bartrt_lbl_owners): which accumulation kernel writes a (state, 256-point tile).  One lane per
+// (state, tile).  Every kernel's claim is restated from ITS OWN early returns, each on its own -- the predicates
+// (narrow_state, mid_state, sv[1] > 1) are the ones the kernels call -- and the claims are counted: none is
+// kOwnerNone (the tile keeps whatever the buffer held), more than one sets kOwnerMulti.  Not an if-else ladder,
+// which could report neither.
+constexpr unsigned char kOwnerNone = 255, kOwnerMulti = 0x80;
+__global__ __launch_bounds__(256) void lbl_owner_map(LblDev d, AccArgs a, int fine_launched, unsigned char *own) {
+  const int ntile = (a.W + 255) / 256;
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)a.nstate * ntile) return;
+  const int st = (int)(idx / ntile), tile0 = (int)(idx % ntile) * 256;
+  const double *sv = a.state + (size_t)st * (2 + 3 * d.niso);
+  if (d.voigt_grid) {   // run_states launches lbl_accumulate_grid alone; it writes every point of every state
+    own[idx] = 4;
+    return;
+  }
+  const bool over = sv[1] > 1.0, narrow = narrow_state(d, a, sv, tile0), mid = mid_state(d, a, sv);
+  // lbl_accumulate: returns for an oversampled, a narrow, a mid state
+  const bool c_tile = !over && !narrow && !mid;
+  // lbl_accumulate_pairs: returns for an oversampled state and for one that is not narrow
+  const bool c_pair = !over && narrow;
+  // lbl_accumulate_fine (if launched at all): returns unless oversampled or mid, and for a mid state's narrow tiles
+  const bool c_fine = fine_launched && (over || mid) && !(mid && narrow);
+  const int claims = (int)c_tile + (int)c_pair + (int)c_fine;
+  unsigned char o = kOwnerNone;
+  if (c_fine) o = over ? 2 : 3;
+  if (c_pair) o = 1;
+  if (c_tile) o = 0;
+  if (claims > 1) o |= kOwnerMulti;
+  own[idx] = o;
+}
+
+// ---------------------------------------------------------------------------
 void lbl_init(Engine &e, const std::string &paths) {
   Lbl *b = new Lbl();
   delete e.lbl;
@@ -1332,6 +1365,12 @@ static void ensure_states(Engine &e, long nstate, bool need_ext) {
   b->cap_state = cap;
 }
 
+// BARTRT_MID_REACH, read once per process
+static int mid_reach_setting() {
+  static const int mid_reach = [] { const char *v = std::getenv("BARTRT_MID_REACH"); return v && *v ? std::max(0, atoi(v)) : kMidReach; }();
+  return mid_reach;
+}
+
 static void run_states(Engine &e, StateArgs &sa, AccArgs &aa, hipStream_t st) {
   Lbl *b = e.lbl;
   const LblDev &d = b->dev;
@@ -1349,8 +1388,7 @@ static void run_states(Engine &e, StateArgs &sa, AccArgs &aa, hipStream_t st) {
   HIPCHK(hipGetLastError());
   aa.W = e.W(); aa.nstate = sa.nstate; aa.wn = e.d_wn; aa.state = b->d_state; aa.smax = b->d_smax;
   aa.pair_reach = kPairReach;
-  static const int mid_reach = [] { const char *v = std::getenv("BARTRT_MID_REACH"); return v && *v ? std::max(0, atoi(v)) : kMidReach; }();
-  aa.mid_reach = mid_reach;
+  aa.mid_reach = mid_reach_setting();
   if (d.voigt_grid) {
     // width-grid mode: lay the states' profile tables out, size the buffer, tabulate, accumulate
     const long ns = sa.nstate;
@@ -1419,6 +1457,40 @@ void lbl_extinction(Engine &e, const double *d_prof, int nwalkers, hipStream_t s
   AccArgs aa{};
   aa.per_group = 0; aa.out = e.lbl->d_ext;
   run_states(e, sa, aa, st);
+}
+
+void lbl_owners(Engine &e, const double *d_prof, int nwalkers, unsigned char *own) {
+  Lbl *b = e.lbl;
+  const LblDev &d = b->dev;
+  const long nstate = (long)nwalkers * e.L;
+  ensure_states(e, nstate, false);
+  // the state vectors as run_states writes them for lbl_extinction
+  StateArgs sa{};
+  sa.nstate = (int)nstate; sa.table_mode = 0; sa.prof = d_prof;
+  sa.L = e.L; sa.S = e.S; sa.iH2 = e.iH2; sa.iHe = e.iHe;
+  sa.press = e.d_press; sa.mass = e.d_mass; sa.diam = e.d_diam;
+  sa.state = b->d_state;
+  sa.dvmax = b->d_dvmax;
+  hipStream_t st = e.stream;
+  HIPCHK(hipMemsetAsync(b->d_dvmax, 0, sizeof(int), st));
+  hipLaunchKernelGGL(lbl_states, dim3(sa.nstate), dim3(64), 0, st, sa, d);
+  HIPCHK(hipGetLastError());
+  int dvmax = 0;
+  HIPCHK(hipMemcpyAsync(&dvmax, b->d_dvmax, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  AccArgs aa{};
+  aa.W = e.W(); aa.nstate = sa.nstate; aa.wn = e.d_wn; aa.state = b->d_state;
+  aa.pair_reach = kPairReach;
+  aa.mid_reach = mid_reach_setting();
+  // run_states' conditions for launching lbl_accumulate_fine
+  const int fine_launched = (d.osamp > 1 || aa.mid_reach > 0) && (dvmax > 1 || aa.mid_reach > 0);
+  const long n = nstate * ((aa.W + 255) / 256);
+  DevBuf<unsigned char> d_own;
+  d_own.reserve((size_t)n);
+  hipLaunchKernelGGL(lbl_owner_map, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d, aa, fine_launched, d_own.get());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpy(own, d_own, (size_t)n, hipMemcpyDeviceToHost));
 }
 
 void lbl_rt_eclipse(Engine &e, const double *d_prof, int nwalkers, const RtArgs &r, hipStream_t st) {

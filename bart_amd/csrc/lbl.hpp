@@ -86,6 +86,11 @@ struct Lbl {
 void lbl_init(Engine &e, const std::string &paths);
 // ext[w][l][W_local] (atm layer order) for nwalkers profiles, into e.lbl->d_ext.
 void lbl_extinction(Engine &e, const double *d_prof, int nwalkers, hipStream_t st);
+// Diagnostics: own[w][l][ntile] (host; ntile = 256-point tiles of the local grid), the accumulation kernel that writes
+// each (state, tile) of lbl_extinction's output, by the kernels' own predicates on freshly computed state vectors:
+// 0 lbl_accumulate, 1 lbl_accumulate_pairs, 2 / 3 lbl_accumulate_fine (oversampled / mid reach), 4 lbl_accumulate_grid,
+// 255 none; bit 7: more than one.  Synchronises the engine's stream.
+void lbl_owners(Engine &e, const double *d_prof, int nwalkers, unsigned char *own);
 // Fused lazy form for eclipse spectra: per wavenumber tile the layers are
 // visited from the top, each layer's line extinction is summed when it is
 // reached, and the tile stops once every sample passed `toomuch` -- the deep,

@@ -101,6 +101,17 @@ def lbl_extinction(profile: np.ndarray) -> np.ndarray:
     return ext
 
 
+def lbl_owners(profile: np.ndarray) -> np.ndarray:
+    """Which accumulation kernel writes each (layer state, 256-point tile) of `lbl_extinction(profile)`:
+    uint8 [L, ntile], by the device's own rule on the state vectors the accumulation reads (diagnostics;
+    the codes are listed in include/bartrt.h, bartrt_lbl_owners)."""
+    prof = np.ascontiguousarray(profile, np.double).ravel()
+    lo, hi = local_range()
+    own = np.zeros((nlayers(), (hi - lo + 255) // 256), np.uint8)
+    _check(trm.lib().bartrt_lbl_owners(_ptr(prof), prof.size, _ptr(own), own.shape[0], own.shape[1]))
+    return own
+
+
 def voigt(x: np.ndarray, y: np.ndarray) -> np.ndarray:
     """Re w(x + i y) as the line-by-line kernels evaluate it (diagnostics; no engine needed)."""
     x, y = np.broadcast_arrays(np.asarray(x, np.double), np.asarray(y, np.double))

@@ -100,6 +100,7 @@ def lib():
         L.bartrt_get_tau_of.argtypes = [i, p, p, i, i]
         L.bartrt_get_intensity_of.argtypes = [i, p, i, i]
         L.bartrt_get_lbl_extinction.argtypes = [p, i, p, i, i]
+        L.bartrt_lbl_owners.argtypes = [p, i, p, i, i]
         L.bartrt_voigt.argtypes = [p, p, p, C.c_long]
         L.bartrt_expint_e2.argtypes = [p, p, C.c_long]
         L.bartrt_timing_end.argtypes = [C.POINTER(d), C.POINTER(i)]

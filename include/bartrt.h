@@ -585,6 +585,13 @@ int bartrt_cf_combine_dev(const double *d_slots, int nranks, int nwalkers, const
 int bartrt_get_lbl_extinction(const double *prof, int nprof, double *ext,
                               int nlayers, int nwave);
 
+/* Diagnostics, line-by-line engines only: which accumulation kernel writes each (layer, 256-point tile
+ * of the local grid) of bartrt_get_lbl_extinction(prof), owners[nlayers][ntile], ntile =
+ * (nwave_local + 255) / 256, decided by the kernels' own predicates on the state vectors the
+ * accumulation reads: 0 the tile kernel, 1 the pair kernel, 2 the line-major kernel (oversampled state),
+ * 3 the same (BARTRT_MID_REACH), 4 the width-grid kernel, 255 none; bit 7 set: more than one. */
+int bartrt_lbl_owners(const double *prof, int nprof, unsigned char *owners, int nlayers, int ntile);
+
 /* Diagnostics, no engine needed: the line-by-line kernels' Voigt function
  * K(x, y) = Re w(x + i y) (x >= 0: distance from the line centre in Doppler widths
  * / sqrt(ln 2); y > 0: Lorentz / Doppler width ratio) on n host (x, y) pairs. */
