@@ -216,6 +216,15 @@ void start_service(int argc, const char **argv, const InitArgs &ia) {
   g_cli = cli;
 }
 
+// a caller's options struct, maybe an older, shorter one: fields past its size read as zero.  False: size is not set
+template <class T>
+bool sized_copy(const T *opts, T *o) {
+  std::memset(o, 0, sizeof *o);
+  if (opts && opts->size < sizeof(opts->size)) return false;
+  if (opts) std::memcpy(o, opts, opts->size < sizeof *o ? opts->size : sizeof *o);
+  return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -970,17 +979,20 @@ int bartrt_step_batch(const double *params, int nwalkers, int npars,
   });
 }
 
+// ---- retrievals: the problem arguments of the four calls below travel on as one value (step.hpp) ----
+static bool stated(const RetrievalProblem &p) { return p.pmin && p.pmax && p.stepsize && p.data && p.uncert; }
+static int null_buffer(const char *who) { return fail(BARTRT_EINVAL, std::string(who) + ": null buffer"); }
+
 int bartrt_mcmc_run(int nchains, int npars, long nsteps, const double *params, const double *pmin,
                     const double *pmax, const double *stepsize, int ndata, const double *data,
                     const double *uncert, int snooker, unsigned long long seed, double *chain,
                     double *chisq, long *naccept, long *nbad) {
   NEED_ENGINE();
   if (!g_eng->step) return fail(BARTRT_EINVAL, "mcmc_run: call bartrt_step_setup first");
-  if (!params || !pmin || !pmax || !stepsize || !data || !uncert || !chain || !chisq)
-    return fail(BARTRT_EINVAL, "mcmc_run: null buffer");
+  const RetrievalProblem p{npars, ndata, 0, pmin, pmax, stepsize, data, uncert};
+  if (!stated(p) || !params || !chain || !chisq) return null_buffer("mcmc_run");
   return guarded([&] {
-    mcmc_run(*g_eng, nchains, npars, nsteps, params, pmin, pmax, stepsize, ndata, data, uncert,
-             snooker, seed, chain, chisq, naccept, nbad);
+    mcmc_run(*g_eng, p, nchains, nsteps, params, snooker, seed, chain, chisq, naccept, nbad);
     return BARTRT_OK;
   });
 }
@@ -991,25 +1003,19 @@ int bartrt_mcmc_run_resident(int nchains, int npars, long nsteps, const double *
                              double *models, long *naccept, long *nbad) {
   NEED_ENGINE();
   if (!g_eng->step) return fail(BARTRT_EINVAL, "mcmc_run_resident: call bartrt_step_setup first");
-  if (!params || !pmin || !pmax || !stepsize || !data || !uncert || !chain || !chisq)
-    return fail(BARTRT_EINVAL, "mcmc_run_resident: null buffer");
-  // the caller's struct may be an older, shorter one: fields past its size read as zero
+  RetrievalProblem p{npars, ndata, 0, pmin, pmax, stepsize, data, uncert};
+  if (!stated(p) || !params || !chain || !chisq) return null_buffer("mcmc_run_resident");
   bartrt_mcmc_opts o;
-  std::memset(&o, 0, sizeof o);
-  if (opts) {
-    if (opts->size < sizeof(opts->size)) return fail(BARTRT_EINVAL, "mcmc_run_resident: set opts->size");
-    std::memcpy(&o, opts, opts->size < sizeof o ? opts->size : sizeof o);
-  }
+  if (!sized_copy(opts, &o)) return fail(BARTRT_EINVAL, "mcmc_run_resident: set opts->size");
   McmcOpts m;
   m.snooker = o.snooker;
   m.seed = o.seed;
   m.thin = o.thin ? o.thin : 1;
   m.block = o.block ? o.block : 256;
-  m.prior = o.prior; m.priorlow = o.priorlow; m.priorup = o.priorup;
+  p.prior = o.prior; p.priorlow = o.priorlow; p.priorup = o.priorup;
   m.progress = o.progress; m.progress_user = o.progress_user;
   return guarded([&] {
-    mcmc_run_resident(*g_eng, nchains, npars, nsteps, params, pmin, pmax, stepsize, ndata, data, uncert, m, chain,
-                      chisq, models, naccept, nbad);
+    mcmc_run_resident(*g_eng, p, nchains, nsteps, params, m, chain, chisq, models, naccept, nbad);
     return BARTRT_OK;
   });
 }
@@ -1022,14 +1028,10 @@ int bartrt_mcmc_draws(unsigned long long seed, unsigned long long t, int nchains
   });
 }
 
-// the caller's bartrt_fit_opts (maybe an older, shorter one) as FitOpts; zero fields read as the defaults
-static bool fit_opts_of(const bartrt_fit_opts *opts, FitOpts &m) {
+// the caller's bartrt_fit_opts as FitOpts, zero fields read as the defaults, and its priors into the problem
+static bool fit_opts_of(const bartrt_fit_opts *opts, FitOpts &m, RetrievalProblem &p) {
   bartrt_fit_opts o;
-  std::memset(&o, 0, sizeof o);
-  if (opts) {
-    if (opts->size < sizeof(opts->size)) return false;
-    std::memcpy(&o, opts, opts->size < sizeof o ? opts->size : sizeof o);
-  }
+  if (!sized_copy(opts, &o)) return false;
   if (o.maxiter) m.maxiter = o.maxiter < 0 ? 0 : o.maxiter;
   if (o.nrungs) m.nrungs = o.nrungs;
   if (o.check) m.check = o.check;
@@ -1037,7 +1039,7 @@ static bool fit_opts_of(const bartrt_fit_opts *opts, FitOpts &m) {
   if (o.ftol != 0) m.ftol = o.ftol;
   if (o.xtol != 0) m.xtol = o.xtol;
   if (o.lambda0 != 0) m.lambda0 = o.lambda0;
-  m.prior = o.prior; m.priorlow = o.priorlow; m.priorup = o.priorup;
+  p.prior = o.prior; p.priorlow = o.priorlow; p.priorup = o.priorup;
   m.trace = o.trace;
   return true;
 }
@@ -1047,13 +1049,12 @@ int bartrt_fit(int nstarts, int npars, const double *starts, const double *pmin,
                const bartrt_fit_opts *opts, double *best, double *chisq, int *status, long *niter, long *nbad) {
   NEED_ENGINE();
   if (!g_eng->step) return fail(BARTRT_EINVAL, "fit: call bartrt_step_setup first");
-  if (!starts || !pmin || !pmax || !stepsize || !data || !uncert || !best || !chisq)
-    return fail(BARTRT_EINVAL, "fit: null buffer");
+  RetrievalProblem p{npars, ndata, 0, pmin, pmax, stepsize, data, uncert};
+  if (!stated(p) || !starts || !best || !chisq) return null_buffer("fit");
   FitOpts m;
-  if (!fit_opts_of(opts, m)) return fail(BARTRT_EINVAL, "fit: set opts->size");
+  if (!fit_opts_of(opts, m, p)) return fail(BARTRT_EINVAL, "fit: set opts->size");
   return guarded([&] {
-    fit_run(*g_eng, nstarts, npars, starts, pmin, pmax, stepsize, ndata, data, uncert, m, best, chisq, status, niter,
-            nbad);
+    fit_run(*g_eng, p, nstarts, starts, m, best, chisq, status, niter, nbad);
     return BARTRT_OK;
   });
 }
@@ -1062,14 +1063,13 @@ int bartrt_fit_probe(int nstarts, int npars, const double *pmin, const double *p
                      int ndata, const double *data, const double *uncert, const bartrt_fit_opts *opts,
                      const double *x, const double *lambda, double *D, const double *cur, const double *pband,
                      const int *pstatus, double *trial, int *valid) {
-  if (!pmin || !pmax || !stepsize || !data || !uncert || !x || !lambda || !D || !cur || !pband || !pstatus ||
-      !trial || !valid)
-    return fail(BARTRT_EINVAL, "bartrt_fit_probe: null buffer");
+  RetrievalProblem p{npars, ndata, 0, pmin, pmax, stepsize, data, uncert};
+  if (!stated(p) || !x || !lambda || !D || !cur || !pband || !pstatus || !trial || !valid)
+    return null_buffer("bartrt_fit_probe");
   FitOpts m;
-  if (!fit_opts_of(opts, m)) return fail(BARTRT_EINVAL, "bartrt_fit_probe: set opts->size");
+  if (!fit_opts_of(opts, m, p)) return fail(BARTRT_EINVAL, "bartrt_fit_probe: set opts->size");
   return guarded([&] {
-    fit_probe(nstarts, npars, pmin, pmax, stepsize, ndata, data, uncert, m, x, lambda, D, cur, pband, pstatus, trial,
-              valid);
+    fit_probe(p, nstarts, m, x, lambda, D, cur, pband, pstatus, trial, valid);
     return BARTRT_OK;
   });
 }

@@ -9,11 +9,10 @@
 #include <string>
 #include <vector>
 
-#include "../../include/bartrt.h"
-#include "comm.hpp"
 #include "engine.hpp"
 #include "fit_core.hpp"
 #include "lds.hpp"
+#include "retrieval_host.hpp"
 #include "step.hpp"
 
 namespace bartrt {
@@ -55,31 +54,25 @@ void launch_advance(const fit::Problem &p, int phase, long it, int *running, hip
   HIPCHK(hipGetLastError());
 }
 
-// sizes and options both entry points refuse; returns nfree
-int check_problem(const char *who, int nstarts, int npars, int ndata, const double *stepsize, const FitOpts &o) {
+// what both entry points refuse (e null: the probe, which has no engine); returns the problem with nfree counted
+Objective check_problem(const char *who, const Engine *e, const RetrievalProblem &p, int nstarts, const FitOpts &o) {
   const std::string w = who;
-  if (nstarts < 1 || nstarts > (1 << 20) || npars < 1 || ndata < 1)
+  if (nstarts < 1 || nstarts > (1 << 20) || p.npars < 1 || p.ndata < 1)
     throw std::invalid_argument(w + ": bad sizes (1 <= nstarts <= 2^20, npars >= 1, ndata >= 1)");
-  if (npars > fit::kMaxPars) throw std::invalid_argument(w + ": too many parameters (at most 64)");
+  if (p.npars > fit::kMaxPars) throw std::invalid_argument(w + ": too many parameters (at most 64)");
   if (o.nrungs < 1 || o.nrungs > fit::kMaxRungs) throw std::invalid_argument(w + ": 1 <= nrungs <= 8");
   if (o.maxiter < 0 || o.check < 1) throw std::invalid_argument(w + ": maxiter >= 0 and check >= 1");
   if (!(o.fdstep > 0) || !(o.ftol >= 0) || !(o.xtol >= 0) || !(o.lambda0 > 0))
     throw std::invalid_argument(w + ": fdstep and lambda0 must be positive, ftol and xtol not negative");
-  const bool priors = o.prior || o.priorlow || o.priorup;
-  if (priors && !(o.prior && o.priorlow && o.priorup))
-    throw std::invalid_argument(w + ": prior, priorlow and priorup come together");
-  int nfree = 0;
-  if (const int bad = mcmc::check_stepsize(npars, stepsize, &nfree))
-    throw std::invalid_argument(w + ": stepsize[" + std::to_string(bad - 1) + "] = " +
-                                std::to_string(stepsize[bad - 1]) + " shares parameter " + std::to_string(bad - 1) +
-                                " with a parameter that is out of range or itself shared");
-  if (nfree < 1) throw std::invalid_argument(w + ": no free parameter (every stepsize is <= 0)");
-  return nfree;
+  const Objective objective = check_retrieval(w, e, p);
+  if (objective.nfree < 1) throw std::invalid_argument(w + ": no free parameter (every stepsize is <= 0)");
+  return objective;
 }
 
 // the problem's constants and the starts' state in device memory
 struct DeviceFit {
-  DevBuf<double> consts, state, trace;
+  DeviceObjective consts;
+  DevBuf<double> state, trace;
   DevBuf<int> ints;
   DevBuf<long> longs;
   fit::Problem d{};
@@ -87,23 +80,12 @@ struct DeviceFit {
   int *mstatus = nullptr;
   size_t ntrace = 0;
 
-  DeviceFit(int S, int npars, int ndata, int nfree, const double *pmin, const double *pmax, const double *stepsize,
-            const double *data, const double *uncert, const FitOpts &o, bool want_trace) {
-    const size_t np = npars, nd = ndata, n = S, rows = fit::max_rows(S, nfree, o.nrungs);
-    const bool priors = o.prior != nullptr;
-    std::vector<double> c;
-    auto put = [&](const double *v, size_t m) { c.insert(c.end(), v, v + m); };
-    put(pmin, np); put(pmax, np); put(stepsize, np);
-    if (priors) { put(o.prior, np); put(o.priorlow, np); put(o.priorup, np); }
-    put(data, nd); put(uncert, nd);
-    consts.upload(c);
-    d.nstarts = S; d.npars = npars; d.ndata = ndata; d.nfree = nfree; d.nrungs = o.nrungs;
+  DeviceFit(int S, const Objective &objective, const FitOpts &o, bool want_trace) : consts(objective) {
+    const int nfree = objective.nfree;
+    const size_t np = objective.npars, nd = objective.ndata, n = S, rows = fit::max_rows(S, nfree, o.nrungs);
+    static_cast<Objective &>(d) = consts.d;
+    d.nstarts = S; d.nrungs = o.nrungs;
     d.maxiter = o.maxiter; d.fdstep = o.fdstep; d.ftol = o.ftol; d.xtol = o.xtol; d.lambda0 = o.lambda0;
-    const double *k = consts;
-    d.pmin = k; d.pmax = k + np; d.stepsize = k + 2 * np;
-    k += 3 * np;
-    if (priors) { d.prior = k; d.priorlow = k + np; d.priorup = k + 2 * np; k += 3 * np; }
-    d.data = k; d.uncert = k + nd;
     // x chisq lambda D cur jrows trows band
     const size_t total = n * np + n + n + n * np + n * nd + n * nfree * np + n * o.nrungs * np + rows * nd;
     // (these memsets run on the null stream; the engine's stream does not wait for that one.  Every caller follows
@@ -139,12 +121,11 @@ struct DeviceFit {
 
 }  // namespace
 
-void fit_probe(int nstarts, int npars, const double *pmin, const double *pmax, const double *stepsize, int ndata,
-               const double *data, const double *uncert, const FitOpts &o, const double *x, const double *lambda,
+void fit_probe(const RetrievalProblem &p, int nstarts, const FitOpts &o, const double *x, const double *lambda,
                double *D, const double *cur, const double *pband, const int *pstatus, double *trial, int *valid) {
-  const int nfree = check_problem("fit_probe", nstarts, npars, ndata, stepsize, o);
-  DeviceFit f(nstarts, npars, ndata, nfree, pmin, pmax, stepsize, data, uncert, o, false);
-  const size_t np = npars, nd = ndata, n = nstarts;
+  const Objective objective = check_problem("fit_probe", nullptr, p, nstarts, o);
+  DeviceFit f(nstarts, objective, o, false);
+  const size_t np = p.npars, nd = p.ndata, n = nstarts, nfree = objective.nfree;
   HIPCHK(hipMemcpy(f.d.x, x, sizeof(double) * n * np, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(f.d.lambda, lambda, sizeof(double) * n, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(f.d.D, D, sizeof(double) * n * np, hipMemcpyHostToDevice));
@@ -158,23 +139,18 @@ void fit_probe(int nstarts, int npars, const double *pmin, const double *pmax, c
   HIPCHK(hipMemcpy(D, f.d.D, sizeof(double) * n * np, hipMemcpyDeviceToHost));
 }
 
-void fit_run(Engine &e, int nstarts, int npars, const double *starts, const double *pmin, const double *pmax,
-             const double *stepsize, int ndata, const double *data, const double *uncert, const FitOpts &o,
-             double *best, double *chisq, int *status, long *niter, long *nbad) {
+void fit_run(Engine &e, const RetrievalProblem &p, int nstarts, const double *starts, const FitOpts &o, double *best,
+             double *chisq, int *status, long *niter, long *nbad) {
   if (!e.step) throw IoError{"fit: call step_setup first"};
-  const int nfree = check_problem("fit", nstarts, npars, ndata, stepsize, o);
-  if (ndata != e.step->nfilters) throw std::invalid_argument("fit: data length must equal the number of filters");
-  if (e.lbl && e.comm) throw CommError{BARTRT_ENOTSUP, "fit: line-by-line engines do not take the communicator's path"};
-  if (!e.comm && (e.lo != 0 || e.hi != e.Wfull))
-    throw IoError{"fit: the engine is sharded and has no communicator (engine.comm_init); use run()"};
+  const Objective objective = check_problem("fit", &e, p, nstarts, o);
 
-  const int S = nstarts, K = o.nrungs;
+  const int S = nstarts, K = o.nrungs, npars = p.npars, nfree = objective.nfree;
   const size_t np = npars, n = S;
   // the step's workspace grows (and waits for the device) here, not inside the loop
   step_ensure(e, (int)fit::max_rows(S, nfree, K));
-  DeviceFit f(S, npars, ndata, nfree, pmin, pmax, stepsize, data, uncert, o, o.trace != nullptr);
+  DeviceFit f(S, objective, o, o.trace != nullptr);
   std::vector<double> x0(starts, starts + n * np);
-  for (size_t s = 0; s < n; s++) mcmc::copy_shared(npars, stepsize, x0.data() + s * np);
+  for (size_t s = 0; s < n; s++) copy_shared(npars, p.stepsize, x0.data() + s * np);
   HIPCHK(hipMemcpy(f.d.x, x0.data(), sizeof(double) * n * np, hipMemcpyHostToDevice));
 
   PinBuf<int> running;
@@ -208,11 +184,8 @@ void fit_run(Engine &e, int nstarts, int npars, const double *starts, const doub
   if (status) HIPCHK(hipMemcpy(status, f.d.status, sizeof(int) * n, hipMemcpyDeviceToHost));
   if (niter) HIPCHK(hipMemcpy(niter, f.d.niter, sizeof(long) * n, hipMemcpyDeviceToHost));
   if (nbad) {
-    std::vector<long> counts(4 * n);
-    HIPCHK(hipMemcpy(counts.data(), f.d.nbad, sizeof(long) * 4 * n, hipMemcpyDeviceToHost));
     std::fill(nbad, nbad + 4, 0L);
-    for (size_t s = 0; s < n; s++)
-      for (int k = 1; k < 4; k++) nbad[k] += counts[4 * s + k];
+    add_counters(f.d.nbad, n, nbad);
   }
   if (o.trace) {
     // records past the last pick repeat it: every start had finished by then

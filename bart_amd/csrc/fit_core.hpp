@@ -3,8 +3,8 @@
 // call: the kernel (fit.hip: fit_advance) runs them one start per wave, and a host compiler alone builds them for the
 // CPU tests (tests/fit_core_host.cpp).
 //
-// PARAMETERS.  Free, fixed and shared as mcmc_core.hpp reads `stepsize` (mcmc::check_stepsize); shared parameters are
-// copied after every update and every perturbation.  The q-th free parameter is "column q"; nfree <= npars <= 64.
+// PARAMETERS.  Free, fixed and shared as retrieval.hpp reads `stepsize`; shared parameters are copied after every
+// update and every perturbation.  The q-th free parameter is "column q"; nfree <= npars <= 64.
 //
 // RESIDUALS.  Row f < ndata is (band_f - data_f) / uncert_f.  With prior arrays, every parameter j with a non-zero
 // priorlow[j] or priorup[j] adds the row (p_j - prior_j) / w, w = priorlow[j] below prior_j and priorup[j] above; a
@@ -34,27 +34,26 @@
 // barrier; on the host they run one after the other.  A phase reads what earlier phases wrote and writes only what
 // its lane owns, so the two orders give the same numbers.
 #pragma once
-#include "mcmc_core.hpp"
+#include "mcmc_core.hpp"   // (not used here: programs that include this header alone find the sampler's names through it)
+#include "retrieval.hpp"
 
-#define FIT_HD __host__ __device__ inline
-#define FIT_EXACT MCMC_EXACT
+#define FIT_HD RETRIEVAL_HD
+#define FIT_EXACT RETRIEVAL_EXACT
 
 namespace bartrt {
 namespace fit {
 
-constexpr int kMaxPars = mcmc::kMaxPars, kMaxRungs = 8;
+using bartrt::kMaxPars;
+constexpr int kMaxRungs = 8;
 constexpr int kLanes = 64, kLdA = 64, kLdW = 65;   // W's rows are padded: it is read along rows and along columns
 enum Status { kRunning = 0, kConverged = 1, kStalled = 2, kIterLimit = 3, kNoStart = 4 };
 constexpr double kLambdaMin = 1e-12, kLambdaMax = 1e12;
 
 // Every pointer is memory of the side that calls.
-struct Problem {
-  int nstarts, npars, ndata, nfree, nrungs;
+struct Problem : Objective {
+  int nstarts, nrungs;
   long maxiter;
   double fdstep, ftol, xtol, lambda0;
-  const double *pmin, *pmax, *stepsize;      // [npars]
-  const double *data, *uncert;               // [ndata]
-  const double *prior, *priorlow, *priorup;  // [npars], or all null
   // the starts' state
   double *x;        // [S][npars]
   double *chisq;    // [S]
@@ -167,7 +166,7 @@ FIT_HD void write_jacobian_rows(const Problem &p, int s) {
     for (int m = 0; m < np; m++) row[m] = x[m];
     if (p.status[s] != kRunning) continue;
     row[j] = x[j] + step_h(p, j, x[j]);
-    mcmc::copy_shared(np, p.stepsize, row);
+    copy_shared(np, p.stepsize, row);
   }
 }
 
@@ -185,7 +184,7 @@ FIT_HD void pick_start(const Problem &p, int s, long it) {
     p.niter[s] = 0;
     p.valid[s] = 0;
     p.lambda[s] = p.lambda0;
-    mcmc::copy_shared(np, p.stepsize, x);
+    copy_shared(np, p.stepsize, x);
     if (st != 0) {
       if (st >= 1 && st <= 3) nbad[st]++;
       p.status[s] = kNoStart;
@@ -379,7 +378,7 @@ FIT_HD void solve_start(const Problem &p, const Work &w, int s, Exec ex) {
         const int j = w.jidx[i];
         if (!w.frozen[i]) row[j] = fmin(fmax(x[j] + w.dlt[i], p.pmin[j]), p.pmax[j]);
       }
-      mcmc::copy_shared(np, p.stepsize, row);
+      copy_shared(np, p.stepsize, row);
     });
   }
   ex.each([&](int q) {

@@ -15,18 +15,19 @@
 #include <string>
 #include <vector>
 
-#include "../../include/bartrt.h"
-#include "comm.hpp"
 #include "engine.hpp"
 #include "mcmc_core.hpp"
+#include "retrieval_host.hpp"
 #include "step.hpp"
 
 namespace bartrt {
 
-void mcmc_run(Engine &e, int nch, int npars, long nsteps, const double *params, const double *pmin,
-              const double *pmax, const double *stepsize, int ndata, const double *data,
-              const double *uncert, int snooker, unsigned long long seed, double *chain,
-              double *chisq, long *naccept_out, long *nbad) {
+void mcmc_run(Engine &e, const RetrievalProblem &problem, int nch, long nsteps, const double *params, int snooker,
+              unsigned long long seed, double *chain, double *chisq, long *naccept_out, long *nbad) {
+  // (its own refusals, with their own error class, and its own chi-square: this loop is kept as it was)
+  const int npars = problem.npars, ndata = problem.ndata;
+  const double *pmin = problem.pmin, *pmax = problem.pmax, *stepsize = problem.stepsize;
+  const double *data = problem.data, *uncert = problem.uncert;
   if (!e.step) throw IoError{"mcmc_run: call step_setup first"};
   if (nch < 1 || npars < 1 || nsteps < 1) throw IoError{"mcmc_run: bad sizes"};
   if (ndata != e.step->nfilters) throw IoError{"mcmc_run: data length must equal the number of filters"};
@@ -217,55 +218,36 @@ void mcmc_draws_probe(unsigned long long seed, unsigned long long t, int nchains
   HIPCHK(hipMemcpy(out, d, sizeof(double) * n, hipMemcpyDeviceToHost));
 }
 
-void mcmc_run_resident(Engine &e, int nch, int npars, long nsteps, const double *params, const double *pmin,
-                       const double *pmax, const double *stepsize, int ndata, const double *data,
-                       const double *uncert, const McmcOpts &opts, double *chain, double *chisq, double *models,
-                       long *naccept_out, long *nbad) {
+void mcmc_run_resident(Engine &e, const RetrievalProblem &p, int nch, long nsteps, const double *params,
+                       const McmcOpts &opts, double *chain, double *chisq, double *models, long *naccept_out,
+                       long *nbad) {
+  const int npars = p.npars, ndata = p.ndata;
   if (!e.step) throw IoError{"mcmc_run_resident: call step_setup first"};
   if (nch < 1 || npars < 1 || nsteps < 1) throw std::invalid_argument("mcmc_run_resident: bad sizes");
   if (nch > mcmc::kMaxChains)
     throw std::invalid_argument("mcmc_run_resident: at most 1024 chains (one workgroup); more stay with mcmc_run");
   if (npars > mcmc::kMaxPars) throw std::invalid_argument("mcmc_run_resident: too many parameters (at most 64)");
   if (opts.thin < 1 || opts.block < 1) throw std::invalid_argument("mcmc_run_resident: thin and block must be >= 1");
-  if (ndata < 1 || ndata != e.step->nfilters)
-    throw std::invalid_argument("mcmc_run_resident: data length must equal the number of filters");
-  const bool priors = opts.prior || opts.priorlow || opts.priorup;
-  if (priors && !(opts.prior && opts.priorlow && opts.priorup))
-    throw std::invalid_argument("mcmc_run_resident: prior, priorlow and priorup come together");
-  int nfree = 0;
-  if (const int bad = mcmc::check_stepsize(npars, stepsize, &nfree))
-    throw std::invalid_argument("mcmc_run_resident: stepsize[" + std::to_string(bad - 1) + "] = " +
-                                std::to_string(stepsize[bad - 1]) + " shares parameter " +
-                                std::to_string(bad - 1) + " with a parameter that is out of range or itself shared");
-  if (e.lbl && e.comm)
-    throw CommError{BARTRT_ENOTSUP, "mcmc_run_resident: line-by-line engines do not take the communicator's path"};
+  const Objective objective = check_retrieval("mcmc_run_resident", &e, p);
 
   const long nkept = mcmc::kept_rows(nsteps, opts.thin);
   const size_t np = npars, nd = ndata, n = nch;
   // the start, on the host through step_run_host as mcmc_run makes it, then uploaded once
   std::vector<double> x(n * np), c(n), cur(n * nd);
   std::vector<int> status(n);
-  long nbad_start[4] = {0, 0, 0, 0};
+  long total[4] = {0, 0, 0, 0};   // accepted proposals, models rejected with status 1, 2, 3
   mcmc::State h{};
-  h.nch = nch; h.npars = npars; h.ndata = ndata; h.nfree = nfree; h.snooker = opts.snooker; h.seed = opts.seed;
-  h.nsteps = nsteps; h.thin = opts.thin;
-  h.pmin = pmin; h.pmax = pmax; h.stepsize = stepsize; h.data = data; h.uncert = uncert;
-  h.prior = opts.prior; h.priorlow = opts.priorlow; h.priorup = opts.priorup;
+  static_cast<Objective &>(h) = objective;
+  h.nch = nch; h.snooker = opts.snooker; h.seed = opts.seed; h.nsteps = nsteps; h.thin = opts.thin;
   h.x = x.data(); h.c = c.data(); h.cur = cur.data();
   auto model = [&](const double *rows, int m, double *band, int *st) { step_run_host(e, rows, m, npars, band, st); };
-  if (!mcmc::start_population(h, params, model, status.data(), nbad_start))
+  if (!mcmc::start_population(h, params, model, status.data(), total))
     throw IoError{"mcmc_run_resident: no chain starts on a physical model: check params/pmin/pmax"};
 
-  // constants: pmin pmax stepsize [prior priorlow priorup] data uncert
-  std::vector<double> consts;
-  auto put = [&](const double *v, size_t m) { consts.insert(consts.end(), v, v + m); };
-  put(pmin, np); put(pmax, np); put(stepsize, np);
-  if (priors) { put(opts.prior, np); put(opts.priorlow, np); put(opts.priorup, np); }
-  put(data, nd); put(uncert, nd);
-  DevBuf<double> d_consts, d_pop, d_out;
+  const DeviceObjective consts(objective);
+  DevBuf<double> d_pop, d_out;
   DevBuf<int> d_int;
   DevBuf<long> d_counts;
-  d_consts.upload(consts);
   // population: x c cur logjac prop band
   d_pop.reserve(n * np + n + n * nd + n + n * np + n * nd);
   d_int.reserve(2 * n);
@@ -275,11 +257,7 @@ void mcmc_run_resident(Engine &e, int nch, int npars, long nsteps, const double 
   HIPCHK(hipMemset(d_int, 0, sizeof(int) * 2 * n));
   HIPCHK(hipMemset(d_counts, 0, sizeof(long) * 4 * n));
   mcmc::State d = h;
-  const double *k = d_consts;
-  d.pmin = k; d.pmax = k + np; d.stepsize = k + 2 * np;
-  k += 3 * np;
-  if (priors) { d.prior = k; d.priorlow = k + np; d.priorup = k + 2 * np; k += 3 * np; }
-  d.data = k; d.uncert = k + nd;
+  static_cast<Objective &>(d) = consts.d;
   double *q = d_pop;
   d.x = q; q += n * np;
   d.c = q; q += n;
@@ -335,11 +313,7 @@ void mcmc_run_resident(Engine &e, int nch, int npars, long nsteps, const double 
   HIPCHK(hipMemcpy(chain, d.chain, sizeof(double) * rows * np, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(chisq, d.chisq, sizeof(double) * rows, hipMemcpyDeviceToHost));
   if (models) HIPCHK(hipMemcpy(models, d.models, sizeof(double) * rows * nd, hipMemcpyDeviceToHost));
-  std::vector<long> counts(4 * n);
-  HIPCHK(hipMemcpy(counts.data(), d_counts, sizeof(long) * 4 * n, hipMemcpyDeviceToHost));
-  long total[4] = {0, nbad_start[1], nbad_start[2], nbad_start[3]};
-  for (size_t i = 0; i < n; i++)
-    for (int s = 0; s < 4; s++) total[s] += counts[4 * i + s];
+  add_counters(d_counts, n, total);
   if (naccept_out) *naccept_out = total[0];
   if (nbad) {
     nbad[0] = 0;

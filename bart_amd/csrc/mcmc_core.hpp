@@ -21,33 +21,25 @@
 //   3 + j / 2   jitter normal of parameter j     jitter normal of parameter j + 1       (j even; DEMC moves and the
 //                                                                                        start, free parameters only)
 //
-// PARAMETERS.  stepsize[j] > 0: free.  stepsize[j] == 0: fixed at its configured value.  stepsize[j] = -k (MC3's
-// convention, k counted from 1): shared, a copy of parameter k - 1 in every proposal and start point; the target must
-// be in range and not itself shared.  nfree counts the free ones; the box [pmin, pmax] applies to them alone.
+// PARAMETERS.  Free, fixed and shared as retrieval.hpp reads `stepsize`; DEMC moves, jitter and the box touch the free
+// ones alone, and shared ones follow in every proposal and start point.
 //
 // CHI-SQUARE.  The data term is summed over the filters in index order.  With prior arrays and priorlow[j] != 0,
 // parameter j adds ((p_j - prior_j) / sigma)^2, sigma = priorlow[j] below prior_j and priorup[j] above.  The chisq the
 // loop keeps and writes out is the data term PLUS the prior terms.
 #pragma once
-#include <cmath>
-#include <cstdint>
+#include "retrieval.hpp"
 
-#ifndef __HIPCC__
-#define __host__
-#define __device__
-#endif
-#define MCMC_HD __host__ __device__ inline
-// the same roundings on the host and on the device: no multiply-add contraction in these functions
-#if defined(__clang__)
-#define MCMC_EXACT _Pragma("clang fp contract(off)")
-#else
-#define MCMC_EXACT
-#endif
+#define MCMC_HD RETRIEVAL_HD
+#define MCMC_EXACT RETRIEVAL_EXACT
 
 namespace bartrt {
 namespace mcmc {
 
-constexpr int kMaxPars = 64, kMaxChains = 1024;
+using bartrt::kMaxPars;         // (retrieval.hpp's, under the names this namespace has always given them)
+using bartrt::check_stepsize;
+using bartrt::copy_shared;
+constexpr int kMaxChains = 1024;
 constexpr unsigned kSlotPartners = 0, kSlotSnooker = 1, kSlotAccept = 2, kSlotJitter = 3;
 constexpr unsigned long long kStartT = 0xFFFFFFFFFFFFFF00ull;
 constexpr int kStartRounds = 20;
@@ -114,15 +106,11 @@ MCMC_HD int other(double u, int nch, int i, int a, int b) {
 
 // The run as the two halves of an iteration see it.  Every pointer is memory of the side that calls (device memory
 // in the kernel, host memory in host code).
-struct State {
-  // the problem
-  int nch, npars, ndata, nfree;
+struct State : Objective {
+  int nch;
   int snooker;                               // the walk asked for; it applies with more than three chains
   unsigned long long seed;
   long nsteps, thin;                         // rows t = thin - 1, 2 thin - 1, ... and the last iteration are written
-  const double *pmin, *pmax, *stepsize;      // [npars]
-  const double *data, *uncert;               // [ndata]
-  const double *prior, *priorlow, *priorup;  // [npars], or all null: uniform priors
   // the population, kept between the halves
   double *x;        // [nch][npars] current points
   double *c;        // [nch] their chisq (data + prior terms; inf: not on a physical model)
@@ -140,26 +128,6 @@ struct State {
 };
 
 MCMC_HD long kept_rows(long nsteps, long thin) { return (nsteps + thin - 1) / thin; }
-
-// 0, or 1 + the index of the first parameter whose shared target is out of range or itself shared; *nfree counted
-MCMC_HD int check_stepsize(int npars, const double *stepsize, int *nfree) {
-  int n = 0;
-  for (int j = 0; j < npars; j++) {
-    const double s = stepsize[j];
-    if (s > 0) n++;
-    if (s < 0) {
-      const double k = -s;
-      if (!(k >= 1.0 && k <= (double)npars) || k != (double)(int)k || stepsize[(int)k - 1] < 0) return j + 1;
-    }
-  }
-  if (nfree) *nfree = n;
-  return 0;
-}
-
-MCMC_HD void copy_shared(int npars, const double *stepsize, double *p) {
-  for (int j = 0; j < npars; j++)
-    if (stepsize[j] < 0) p[j] = p[(int)(-stepsize[j]) - 1];
-}
 
 MCMC_HD double prior_term(const State &s, const double *p) {
   MCMC_EXACT

@@ -2,6 +2,7 @@
 // code/BARTfunc.py:309-399), batched over walkers on the device.
 #pragma once
 #include "engine.hpp"
+#include "retrieval.hpp"
 
 namespace bartrt {
 
@@ -81,27 +82,25 @@ void step_run_host(Engine &e, const double *params, int n, int npars, double *ba
                    int *status);
 // diagnostics (bartrt_expint_e2): the T(p) kernels' exponential integral E_2 on n host values; needs no engine
 void step_expint_e2_probe(const double *x, double *out, long n);
-// DEMC / snooker over all chains, one step_run_host per iteration (mcmc.hip)
-void mcmc_run(Engine &e, int nchains, int npars, long nsteps, const double *params, const double *pmin,
-              const double *pmax, const double *stepsize, int ndata, const double *data,
-              const double *uncert, int snooker, unsigned long long seed, double *chain,
-              double *chisq, long *naccept, long *nbad);
+// A retrieval problem as a caller states it: retrieval.hpp's Objective on host memory, nothing checked and nfree not
+// counted yet.  The entry points below do that (retrieval_host.hpp: check_retrieval; std::invalid_argument).
+using RetrievalProblem = Objective;
+// DEMC / snooker over all chains, one step_run_host per iteration (mcmc.hip); takes no priors and no shared parameters
+void mcmc_run(Engine &e, const RetrievalProblem &p, int nchains, long nsteps, const double *params, int snooker,
+              unsigned long long seed, double *chain, double *chisq, long *naccept, long *nbad);
 // The same sampler resident on the GPU (mcmc.hip; arithmetic in mcmc_core.hpp): per iteration one mcmc_advance
 // launch and one step_run_dev, enqueued without a host wait, in blocks of `block` iterations, two blocks in flight.
 struct McmcOpts {
   int snooker = 0;
   unsigned long long seed = 0;
   long thin = 1, block = 256;
-  const double *prior = nullptr, *priorlow = nullptr, *priorup = nullptr;   // [npars], all or none
   void (*progress)(long iterations, long naccept, void *user) = nullptr;   // per finished block
   void *progress_user = nullptr;
 };
 // chain[nchains][nkept][npars], chisq[nchains][nkept], models[nchains][nkept][ndata] (may be null),
-// nkept = ceil(nsteps / thin).  Bad sizes or stepsizes: std::invalid_argument
-void mcmc_run_resident(Engine &e, int nchains, int npars, long nsteps, const double *params, const double *pmin,
-                       const double *pmax, const double *stepsize, int ndata, const double *data,
-                       const double *uncert, const McmcOpts &opts, double *chain, double *chisq, double *models,
-                       long *naccept, long *nbad);
+// nkept = ceil(nsteps / thin)
+void mcmc_run_resident(Engine &e, const RetrievalProblem &p, int nchains, long nsteps, const double *params,
+                       const McmcOpts &opts, double *chain, double *chisq, double *models, long *naccept, long *nbad);
 // diagnostics (bartrt_mcmc_draws): the core's draws of chains 0 .. nchains - 1 at iteration t, evaluated on the
 // device: out[nchains][9 + npars] (mcmc_core.hpp, draws_row); needs no engine
 void mcmc_draws_probe(unsigned long long seed, unsigned long long t, int nchains, int npars, double *out);
@@ -112,20 +111,17 @@ struct FitOpts {
   long maxiter = 50, check = 4;
   int nrungs = 4;
   double fdstep = 1e-2, ftol = 1e-10, xtol = 1e-10, lambda0 = 1e-3;
-  const double *prior = nullptr, *priorlow = nullptr, *priorup = nullptr;   // [npars], all or none
   double *trace = nullptr;   // [nstarts][maxiter + 1][npars + 4]: x, chisq, lambda, chosen rung, status after each pick
 };
 // starts, best [nstarts][npars]; chisq, status (fit_core.hpp: Status), niter [nstarts]; nbad[4] (status, niter and
-// nbad may be null).  Bad sizes, options or stepsizes: std::invalid_argument
-void fit_run(Engine &e, int nstarts, int npars, const double *starts, const double *pmin, const double *pmax,
-             const double *stepsize, int ndata, const double *data, const double *uncert, const FitOpts &opts,
+// nbad may be null)
+void fit_run(Engine &e, const RetrievalProblem &p, int nstarts, const double *starts, const FitOpts &opts,
              double *best, double *chisq, int *status, long *niter, long *nbad);
 // diagnostics (bartrt_fit_probe): the solve phase of fit_advance once, on the device, for nstarts starts at x
 // [nstarts][npars] with damping lambda [nstarts] and scaling D [nstarts][npars] (updated in place), from the band
 // fluxes cur [nstarts][ndata] at x and pband [nstarts][nfree][ndata], pstatus [nstarts][nfree] of the forward-difference
 // rows: trial [nstarts][nrungs][npars] and valid [nstarts] (bit k: rung k).  Needs no engine
-void fit_probe(int nstarts, int npars, const double *pmin, const double *pmax, const double *stepsize, int ndata,
-               const double *data, const double *uncert, const FitOpts &opts, const double *x, const double *lambda,
+void fit_probe(const RetrievalProblem &p, int nstarts, const FitOpts &opts, const double *x, const double *lambda,
                double *D, const double *cur, const double *pband, const int *pstatus, double *trial, int *valid);
 
 }  // namespace bartrt

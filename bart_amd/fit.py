@@ -10,6 +10,8 @@ import ctypes as C
 
 import numpy as np
 
+from .sampler import need_whole_grid_or_comm, problem_arrays
+
 STATUS = ("running", "converged", "stalled", "iteration limit", "no physical start")
 RUNNING, CONVERGED, STALLED, ITER_LIMIT, NO_START = range(5)
 
@@ -26,29 +28,16 @@ _a = lambda v: np.ascontiguousarray(v, np.double)
 _ptr = lambda v: v.ctypes.data_as(C.c_void_p)
 
 
-def _priors(cfg, npars, who):
-    given = [v is not None for v in (cfg.prior, cfg.priorlow, cfg.priorup)]
-    if not any(given):
-        return None
-    if not all(given):
-        raise ValueError("%s: prior, priorlow and priorup come together" % who)
-    pri = [_a(v) for v in (cfg.prior, cfg.priorlow, cfg.priorup)]
-    if any(v.shape != (npars,) for v in pri):
-        raise ValueError("%s: prior, priorlow and priorup have one value per parameter" % who)
-    return pri
-
-
-def _options(cfg, npars, who, opts):
+def _options(pri, who, opts):
     unknown = set(opts) - set(DEFAULTS)
     if unknown:
         raise TypeError("%s: unknown option(s) %s" % (who, ", ".join(sorted(unknown))))
     o = dict(DEFAULTS, **opts)
     st = FitOpts(size=C.sizeof(FitOpts), maxiter=o["maxiter"] if o["maxiter"] > 0 else -1, nrungs=o["nrungs"],
                  check=o["check"], fdstep=o["fdstep"], ftol=o["ftol"], xtol=o["xtol"], lambda0=o["lambda0"])
-    pri = _priors(cfg, npars, who)
     if pri is not None:
         st.prior, st.priorlow, st.priorup = (v.ctypes.data for v in pri)
-    return o, st, pri
+    return o, st
 
 
 def default_starts(cfg, nstarts: int, seed=None) -> np.ndarray:
@@ -85,22 +74,17 @@ def fit(worker, cfg, starts=None, nstarts=None, seed=None, **opts):
     against 2.5e-5, 2.564 against 3.350, 2.59988 against 2.60000), and most starts here run into the iteration limit
     on these degenerate problems.  Sixteen starts cost 2.27, 2.21 and 5.84 times one start, not "little more"; the
     best of the sixteen is better than the single start on every shape."""
-    from . import engine, transit_module as trm
-    lo, hi = engine.local_range()
-    if hi - lo != worker.nwave and engine.comm_info()["nranks"] == 0:
-        raise ValueError("fit: the engine is sharded and has no communicator (engine.comm_init); use run()")
-    par, pmin, pmax, step = _a(cfg.params), _a(cfg.pmin), _a(cfg.pmax), _a(cfg.stepsize)
-    data, unc = _a(cfg.data), _a(cfg.uncert)
+    from . import transit_module as trm
+    need_whole_grid_or_comm(worker, "fit")
+    par, pmin, pmax, step, data, unc, pri = problem_arrays(cfg, "fit")
     npars = len(par)
-    if any(v.shape != par.shape for v in (pmin, pmax, step)) or unc.shape != data.shape:
-        raise ValueError("fit: pmin, pmax and stepsize have one value per parameter, uncert one per datum")
     if starts is None:
         starts = default_starts(cfg, int(nstarts or cfg.nchains), seed)
     starts = _a(np.atleast_2d(starts))
     if starts.ndim != 2 or starts.shape[1] != npars or len(starts) < 1:
         raise ValueError("fit: starts is [nstarts, npars]")
     S = len(starts)
-    o, st, pri = _options(cfg, npars, "fit", opts)
+    o, st = _options(pri, "fit", opts)
     trace = np.zeros((S, max(o["maxiter"], 0) + 1, npars + 4))
     st.trace = trace.ctypes.data
     best, chisq = np.zeros((S, npars)), np.zeros(S)
@@ -123,10 +107,9 @@ def covariance(worker, cfg, p, fdstep: float = 1e-2):
     """``(J^T J)^-1`` at the point ``p`` over the free parameters, J the forward-difference Jacobian of the residuals
     (data rows, then prior rows) from one more batch of ``nfree + 1`` models: MC3's "best-fit uncertainties" are the
     square roots of its diagonal.  Steps as the fit takes them (``fdstep * stepsize``, backwards at the upper bound)."""
-    p, step = _a(p).copy(), _a(cfg.stepsize)
-    pmin, pmax, data, unc = _a(cfg.pmin), _a(cfg.pmax), _a(cfg.data), _a(cfg.uncert)
+    _, pmin, pmax, step, data, unc, pri = problem_arrays(cfg, "covariance")
+    p = _a(p).copy()
     free = np.where(step > 0)[0]
-    pri = _priors(cfg, len(p), "covariance")
 
     def shared(row):
         for j in np.where(step < 0)[0]:

@@ -90,6 +90,43 @@ def _check_stepsize(stepsize):
                          "run_resident and fit.fit alone: here give every parameter its own stepsize, or 0 to fix it")
 
 
+def problem_arrays(cfg, who: str):
+    """The retrieval problem of ``cfg`` as the library takes it: contiguous double arrays ``params, pmin, pmax,
+    stepsize, data, uncert`` and ``[prior, priorlow, priorup]`` (or None where ``cfg`` has no priors)."""
+    a = lambda v: np.ascontiguousarray(v, np.double)
+    par, pmin, pmax, step, data, unc = (a(v) for v in (cfg.params, cfg.pmin, cfg.pmax, cfg.stepsize, cfg.data, cfg.uncert))
+    given = [v is not None for v in (cfg.prior, cfg.priorlow, cfg.priorup)]
+    pri = None
+    if any(given):
+        if not all(given):
+            raise ValueError("%s: prior, priorlow and priorup come together" % who)
+        pri = [a(v) for v in (cfg.prior, cfg.priorlow, cfg.priorup)]
+        if any(v.shape != par.shape for v in pri):
+            raise ValueError("%s: prior, priorlow and priorup have one value per parameter" % who)
+    if any(v.shape != par.shape for v in (pmin, pmax, step)) or unc.shape != data.shape:
+        raise ValueError("%s: pmin, pmax and stepsize have one value per parameter, uncert one per datum" % who)
+    return par, pmin, pmax, step, data, unc, pri
+
+
+def need_whole_grid_or_comm(worker, who: str):
+    """The library's retrieval loops evaluate whole spectra: on a sharded engine only over its communicator."""
+    from . import engine
+    lo, hi = engine.local_range()
+    if hi - lo != worker.nwave and engine.comm_info()["nranks"] == 0:
+        raise ValueError("%s: the engine is sharded and has no communicator (engine.comm_init); use run()" % who)
+
+
+def _result(chain, chis, naccept, nsteps, nch, cfg, thin=1, **extra):
+    """The result dictionary of the three loops, from chain [nch, nkept, npars] and chis [nch, nkept] (every
+    ``thin``-th of ``nsteps`` iterations): best point, Gelman-Rubin statistic past the burn-in, acceptance rate."""
+    free = np.where(cfg.stepsize > 0)[0]
+    ib = np.unravel_index(np.argmin(chis), chis.shape)
+    post = chain[:, min(cfg.burnin // thin, chain.shape[1] - 1):]
+    gr = gelman_rubin(post[:, :, free]) if cfg.grtest and post.shape[1] > 3 and nch > 1 else None
+    return {"chain": chain, "chisq": chis, "bestp": chain[ib], "best_chisq": float(chis[ib]),
+            "accept_rate": naccept / (nsteps * nch), "grstat": gr, "free": free, **extra}
+
+
 def run(model, cfg: SamplerConfig, log=None):
     """model(params[nchains, npars]) -> bandflux[nchains, ndata] (-1 rows = rejected).
     Returns dict(chain [nchains, nsteps, npars], chisq [nchains, nsteps], bestp,
@@ -198,11 +235,7 @@ def run(model, cfg: SamplerConfig, log=None):
             if log is not None and (t + 1) % max(1, nsteps // 10) == 0:
                 log("step %d/%d  best chisq %.4f  acceptance %.2f" % (
                     t + 1, nsteps, float(np.min(chis[:, :t + 1])), naccept / ((t + 1) * nch)))
-    ib = np.unravel_index(np.argmin(chis), chis.shape)
-    post = chain[:, min(cfg.burnin, nsteps - 1):]
-    gr = gelman_rubin(post[:, :, free]) if cfg.grtest and post.shape[1] > 3 and nch > 1 else None
-    return {"chain": chain, "chisq": chis, "bestp": chain[ib], "best_chisq": float(chis[ib]),
-            "accept_rate": naccept / (nsteps * nch), "grstat": gr, "free": free}
+    return _result(chain, chis, naccept, nsteps, nch, cfg)
 
 
 def run_native(worker, cfg: SamplerConfig, log=None):
@@ -212,18 +245,13 @@ def run_native(worker, cfg: SamplerConfig, log=None):
     chains.  Needs an unsharded engine or, on a sharded one, the library's
     communicator (engine.comm_init): every rank then runs this same seeded loop
     in lockstep and gets the same chains.  Same result dictionary as :func:`run`."""
-    import ctypes as C
-    from . import engine, transit_module as trm
-    lo, hi = engine.local_range()
-    if hi - lo != worker.nwave and engine.comm_info()["nranks"] == 0:
-        raise ValueError("run_native: the engine is sharded and has no communicator (engine.comm_init); use run()")
+    from . import transit_module as trm
+    need_whole_grid_or_comm(worker, "run_native")
     nch = cfg.nchains
     _check_stepsize(cfg.stepsize)
     nsteps = max(1, int(np.ceil(cfg.numit / nch)))
-    npars = len(cfg.params)
-    a = lambda v: np.ascontiguousarray(v, np.double)
-    par, pmin, pmax, step = a(cfg.params), a(cfg.pmin), a(cfg.pmax), a(cfg.stepsize)
-    data, unc = a(cfg.data), a(cfg.uncert)
+    par, pmin, pmax, step, data, unc, _ = problem_arrays(cfg, "run_native")     # (this loop takes no priors)
+    npars = len(par)
     chain = np.zeros((nch, nsteps, npars))
     chis = np.zeros((nch, nsteps))
     nacc = C.c_long(0)
@@ -235,15 +263,10 @@ def run_native(worker, cfg: SamplerConfig, log=None):
         C.cast(C.byref(nacc), C.c_void_p), C.cast(nbad, C.c_void_p)))
     for k in (1, 2, 3):
         worker.nbad[k] += int(nbad[k])
-    free = np.where(cfg.stepsize > 0)[0]
     if log is not None:
         log("%d iterations of %d chains; best chisq %.4f  acceptance %.2f" % (
             nsteps, nch, float(chis.min()), nacc.value / (nsteps * nch)))
-    ib = np.unravel_index(np.argmin(chis), chis.shape)
-    post = chain[:, min(cfg.burnin, nsteps - 1):]
-    gr = gelman_rubin(post[:, :, free]) if cfg.grtest and post.shape[1] > 3 and nch > 1 else None
-    return {"chain": chain, "chisq": chis, "bestp": chain[ib], "best_chisq": float(chis[ib]),
-            "accept_rate": nacc.value / (nsteps * nch), "grstat": gr, "free": free}
+    return _result(chain, chis, nacc.value, nsteps, nch, cfg)
 
 
 class McmcOpts(C.Structure):
@@ -285,30 +308,18 @@ def run_resident(worker, cfg: SamplerConfig, log=None, block: int = 256):
     Returns the dictionary of :func:`run_native` (``chain`` [nchains, nkept, npars], ``chisq`` [nchains, nkept],
     nkept = ceil(nsteps / thinning)) plus ``models`` [nchains, nkept, ndata]: the band fluxes of each chain's current
     state at the kept iterations."""
-    from . import engine, transit_module as trm
-    lo, hi = engine.local_range()
-    if hi - lo != worker.nwave and engine.comm_info()["nranks"] == 0:
-        raise ValueError("run_resident: the engine is sharded and has no communicator (engine.comm_init); use run()")
+    from . import transit_module as trm
+    need_whole_grid_or_comm(worker, "run_resident")
     nch = cfg.nchains
     nsteps = max(1, int(np.ceil(cfg.numit / nch)))
     thin = max(1, int(cfg.thinning))
     nkept = -(-nsteps // thin)
-    npars = len(cfg.params)
-    a = lambda v: np.ascontiguousarray(v, np.double)
-    par, pmin, pmax, step = a(cfg.params), a(cfg.pmin), a(cfg.pmax), a(cfg.stepsize)
-    data, unc = a(cfg.data), a(cfg.uncert)
+    par, pmin, pmax, step, data, unc, pri = problem_arrays(cfg, "run_resident")
+    npars = len(par)
     ptr = lambda v: v.ctypes.data_as(C.c_void_p)
     opts = McmcOpts(size=C.sizeof(McmcOpts), snooker=int(cfg.walk == "snooker"), seed=cfg.seed, thin=thin, block=block)
-    given = [v is not None for v in (cfg.prior, cfg.priorlow, cfg.priorup)]
-    if any(given):
-        if not all(given):
-            raise ValueError("run_resident: prior, priorlow and priorup come together")
-        pri = [a(v) for v in (cfg.prior, cfg.priorlow, cfg.priorup)]
-        if any(v.shape != par.shape for v in pri):
-            raise ValueError("run_resident: prior, priorlow and priorup have one value per parameter")
+    if pri is not None:
         opts.prior, opts.priorlow, opts.priorup = (v.ctypes.data for v in pri)
-    if any(v.shape != par.shape for v in (pmin, pmax, step)) or unc.shape != data.shape:
-        raise ValueError("run_resident: pmin, pmax and stepsize have one value per parameter, uncert one per datum")
     if log is not None:
         report = PROGRESS(lambda it, acc, _: log("step %d/%d  acceptance %.2f" % (it, nsteps, acc / (it * nch))))
         opts.progress = C.cast(report, C.c_void_p)
@@ -323,12 +334,7 @@ def run_resident(worker, cfg: SamplerConfig, log=None, block: int = 256):
         C.cast(C.byref(nacc), C.c_void_p), C.cast(nbad, C.c_void_p)))
     for k in (1, 2, 3):
         worker.nbad[k] += int(nbad[k])
-    free = np.where(cfg.stepsize > 0)[0]
     if log is not None:
         log("%d iterations of %d chains; best chisq %.4f  acceptance %.2f" % (
             nsteps, nch, float(chis.min()), nacc.value / (nsteps * nch)))
-    ib = np.unravel_index(np.argmin(chis), chis.shape)
-    post = chain[:, min(cfg.burnin // thin, nkept - 1):]
-    gr = gelman_rubin(post[:, :, free]) if cfg.grtest and post.shape[1] > 3 and nch > 1 else None
-    return {"chain": chain, "chisq": chis, "bestp": chain[ib], "best_chisq": float(chis[ib]),
-            "accept_rate": nacc.value / (nsteps * nch), "grstat": gr, "free": free, "models": models}
+    return _result(chain, chis, nacc.value, nsteps, nch, cfg, thin, models=models)
