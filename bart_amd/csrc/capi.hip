@@ -1014,8 +1014,20 @@ int bartrt_mcmc_run_resident(int nchains, int npars, long nsteps, const double *
   m.block = o.block ? o.block : 256;
   p.prior = o.prior; p.priorlow = o.priorlow; p.priorup = o.priorup;
   m.progress = o.progress; m.progress_user = o.progress_user;
+  m.burnin = o.burnin; m.grcheck = o.grcheck; m.grthreshold = o.grthreshold; m.grexit = o.grexit;
+  m.grstat = o.grstat; m.grwhen = o.grwhen; m.ngr = o.ngr; m.ngr_out = o.ngr_out;
+  m.first = o.first; m.start = o.start; m.done = o.done;
   return guarded([&] {
     mcmc_run_resident(*g_eng, p, nchains, nsteps, params, m, chain, chisq, models, naccept, nbad);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_mcmc_gr(const double *chain, int nchains, long nkept, int npars, const double *stepsize, long r0, long r1,
+                   double threshold, double *psrf, double *triples, int *converged) {
+  if (!chain || !stepsize || !psrf || !triples || !converged) return null_buffer("bartrt_mcmc_gr");
+  return guarded([&] {
+    mcmc_gr_probe(chain, nchains, nkept, npars, stepsize, r0, r1, threshold, psrf, triples, converged);
     return BARTRT_OK;
   });
 }

@@ -10,12 +10,14 @@
 #include <algorithm>
 #include <cmath>
 #include <limits>
+#include <memory>
 #include <random>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "engine.hpp"
+#include "gr_core.hpp"
 #include "mcmc_core.hpp"
 #include "retrieval_host.hpp"
 #include "step.hpp"
@@ -193,6 +195,102 @@ __global__ void mcmc_draws_kernel(unsigned long long seed, unsigned long long t,
   if (i < nch) mcmc::draws_row(seed, t, nch, i, npars, out + (size_t)i * (mcmc::kDrawsHead + npars));
 }
 
+// ---- the Gelman-Rubin statistic of the chain in device memory (gr_core.hpp states every sum and its order) -----------
+// Leaf stage: one lane per (chain, tile, parameter), the parameter fastest, so the lanes of a wave read whole rows.
+// leafs[nch][ntiles][npars][3]; the lanes of parameters that are not free write nothing.
+__global__ __launch_bounds__(256) void mcmc_gr_leaf(const double *chain, int nch, long nkept, int npars,
+                                                    const double *stepsize, long r0, long r1, double *leafs) {
+  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const long nt = gr::tiles(r0, r1);
+  if (q >= (size_t)nch * nt * npars) return;
+  const int j = (int)(q % npars);
+  if (!(stepsize[j] > 0)) return;
+  const size_t ik = q / npars;
+  gr::leaf(chain, nkept, npars, r0, r1, (int)(ik / nt), (long)(ik % nt), j, leafs + q * 3);
+}
+
+// Merge stage: one lane per (chain, parameter), its tiles in ascending order.  triples[nch][npars][3].
+__global__ __launch_bounds__(256) void mcmc_gr_merge(const double *leafs, int nch, long nt, int npars,
+                                                     const double *stepsize, double *triples) {
+  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= (size_t)nch * npars) return;
+  const int j = (int)(q % npars);
+  const size_t i = q / npars;
+  double a[3] = {0.0, 0.0, 0.0};
+  if (stepsize[j] > 0) {
+    const double *t = leafs + (i * nt * npars + j) * 3;
+    a[0] = t[0]; a[1] = t[1]; a[2] = t[2];
+    for (long k = 1; k < nt; k++) gr::merge(a, t + (size_t)k * npars * 3);
+  }
+  for (int c = 0; c < 3; c++) triples[q * 3 + c] = a[c];
+}
+
+// Finisher: one workgroup, parameter j on lane j.  Writes the record the host reads (host-mapped, as mcmc_advance's
+// snap): rec_d = psrf[npars] then the triples; rec_w = converged, then the four counters summed over the chains as
+// they stand now (counts null: zeros).
+__global__ __launch_bounds__(gr::kFinishLanes) void mcmc_gr_finish(const double *triples, int nch, int npars,
+                                                                   const double *stepsize, double threshold,
+                                                                   const long *counts, double *rec_d, long *rec_w) {
+  __shared__ double psrf[kMaxPars];
+  const int j = threadIdx.x;
+  if (j < npars) {
+    psrf[j] = stepsize[j] > 0 ? gr::psrf_of(triples + (size_t)j * 3, (size_t)npars * 3, nch) : 0.0;
+    rec_d[j] = psrf[j];
+  }
+  for (size_t q = j; q < (size_t)nch * npars * 3; q += gr::kFinishLanes) rec_d[npars + q] = triples[q];
+  __syncthreads();
+  if (j == 0) rec_w[0] = gr::converged_of(psrf, stepsize, npars, threshold);
+  if (j >= 1 && j <= 4) {
+    long sum = 0;
+    if (counts)
+      for (int i = 0; i < nch; i++) sum += counts[(size_t)i * 4 + (j - 1)];
+    rec_w[j] = sum;
+  }
+}
+
+// The three launches of one test on `stream`, their scratch, and the host-mapped records: `slots` of them, each
+// psrf[npars] + triples[nch][npars][3] doubles and kRecWords words.
+struct GrTest {
+  static constexpr int kRecWords = 5;
+  int nch, npars;
+  DevBuf<double> leafs, triples;
+  PinBuf<double> rec_d;
+  PinBuf<long> rec_w;
+  double *rec_d_dev = nullptr;
+  long *rec_w_dev = nullptr;
+
+  size_t doubles() const { return (size_t)npars + (size_t)nch * npars * 3; }
+  GrTest(int nch_, int npars_, long maxrows, int slots) : nch(nch_), npars(npars_) {
+    leafs.reserve((size_t)nch * gr::tiles(0, maxrows) * npars * 3);
+    triples.reserve((size_t)nch * npars * 3);
+    rec_d.reserve(doubles() * slots);
+    rec_w.reserve((size_t)kRecWords * slots);
+    void *p = nullptr;
+    HIPCHK(hipHostGetDevicePointer(&p, rec_d.get(), 0));
+    rec_d_dev = static_cast<double *>(p);
+    HIPCHK(hipHostGetDevicePointer(&p, rec_w.get(), 0));
+    rec_w_dev = static_cast<long *>(p);
+  }
+  const double *psrf(int slot) const { return rec_d.get() + doubles() * slot; }
+  const long *words(int slot) const { return rec_w.get() + (size_t)kRecWords * slot; }
+  // rows [r0, r1) of the device chain[nch][nkept][npars]; gr::testable(nch, r0, r1) and r1 - r0 <= maxrows hold
+  void enqueue(const double *chain, long nkept, const double *stepsize, long r0, long r1, double threshold,
+               const long *counts, int slot, hipStream_t st) {
+    const long nt = gr::tiles(r0, r1);
+    const size_t lanes = (size_t)nch * nt * npars, pairs = (size_t)nch * npars;
+    hipLaunchKernelGGL(mcmc_gr_leaf, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, chain, nch, nkept, npars,
+                       stepsize, r0, r1, leafs.get());
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(mcmc_gr_merge, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, leafs.get(), nch, nt,
+                       npars, stepsize, triples.get());
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(mcmc_gr_finish, dim3(1), dim3(gr::kFinishLanes), 0, st, triples.get(), nch, npars, stepsize,
+                       gr::threshold_of(threshold), counts, rec_d_dev + doubles() * slot,
+                       rec_w_dev + (size_t)kRecWords * slot);
+    HIPCHK(hipGetLastError());
+  }
+};
+
 struct Events {
   hipEvent_t ev[2] = {nullptr, nullptr};
   Events() {
@@ -218,6 +316,28 @@ void mcmc_draws_probe(unsigned long long seed, unsigned long long t, int nchains
   HIPCHK(hipMemcpy(out, d, sizeof(double) * n, hipMemcpyDeviceToHost));
 }
 
+void mcmc_gr_probe(const double *chain, int nch, long nkept, int npars, const double *stepsize, long r0, long r1,
+                   double threshold, double *psrf, double *triples, int *converged) {
+  if (nch < 1 || nch > (1 << 20) || npars < 1 || npars > kMaxPars || nkept < 1)
+    throw std::invalid_argument("bartrt_mcmc_gr: 1 <= nchains <= 2^20, 1 <= npars <= 64 and nkept >= 1");
+  if (r0 < 0 || r1 < r0 || r1 > nkept || threshold < 0)
+    throw std::invalid_argument("bartrt_mcmc_gr: 0 <= r0 <= r1 <= nkept and threshold >= 0");
+  const size_t nt = (size_t)nch * npars * 3;
+  std::fill(psrf, psrf + npars, 0.0);
+  std::fill(triples, triples + nt, 0.0);
+  *converged = 0;
+  if (!gr::testable(nch, r0, r1)) return;   // no test: zeros
+  DevBuf<double> d_chain, d_step;
+  d_chain.upload(chain, (size_t)nch * nkept * npars);
+  d_step.upload(stepsize, npars);
+  GrTest test(nch, npars, r1 - r0, 1);
+  test.enqueue(d_chain, nkept, d_step, r0, r1, threshold, nullptr, 0, nullptr);
+  HIPCHK(hipDeviceSynchronize());
+  std::copy(test.psrf(0), test.psrf(0) + npars, psrf);
+  std::copy(test.psrf(0) + npars, test.psrf(0) + npars + nt, triples);
+  *converged = (int)test.words(0)[0];
+}
+
 void mcmc_run_resident(Engine &e, const RetrievalProblem &p, int nch, long nsteps, const double *params,
                        const McmcOpts &opts, double *chain, double *chisq, double *models, long *naccept_out,
                        long *nbad) {
@@ -228,6 +348,18 @@ void mcmc_run_resident(Engine &e, const RetrievalProblem &p, int nch, long nstep
     throw std::invalid_argument("mcmc_run_resident: at most 1024 chains (one workgroup); more stay with mcmc_run");
   if (npars > mcmc::kMaxPars) throw std::invalid_argument("mcmc_run_resident: too many parameters (at most 64)");
   if (opts.thin < 1 || opts.block < 1) throw std::invalid_argument("mcmc_run_resident: thin and block must be >= 1");
+  const long first = opts.first, B = opts.block;
+  if (first < 0 || (first > 0) != (opts.start != nullptr))
+    throw std::invalid_argument("mcmc_run_resident: first > 0 and start come together (a resumed run), or neither");
+  if (first % opts.thin != 0)
+    throw std::invalid_argument("mcmc_run_resident: first = " + std::to_string(first) + " is not a multiple of thin = " +
+                                std::to_string(opts.thin) + ": a run resumes on a kept row");
+  if (opts.grcheck < 0 || opts.burnin < 0 || opts.ngr < 0 || opts.grthreshold < 0)
+    throw std::invalid_argument("mcmc_run_resident: burnin, grcheck, grthreshold and ngr must be >= 0");
+  if (opts.grcheck > 0 && (opts.grcheck % B != 0 || B % opts.thin != 0))
+    throw std::invalid_argument("mcmc_run_resident: grcheck = " + std::to_string(opts.grcheck) +
+                                " must be a multiple of block = " + std::to_string(B) + ", and block of thin = " +
+                                std::to_string(opts.thin) + ": every test falls on a block end that is a kept row");
   const Objective objective = check_retrieval("mcmc_run_resident", &e, p);
 
   const long nkept = mcmc::kept_rows(nsteps, opts.thin);
@@ -239,9 +371,18 @@ void mcmc_run_resident(Engine &e, const RetrievalProblem &p, int nch, long nstep
   mcmc::State h{};
   static_cast<Objective &>(h) = objective;
   h.nch = nch; h.snooker = opts.snooker; h.seed = opts.seed; h.nsteps = nsteps; h.thin = opts.thin;
+  h.first = first;
   h.x = x.data(); h.c = c.data(); h.cur = cur.data();
   auto model = [&](const double *rows, int m, double *band, int *st) { step_run_host(e, rows, m, npars, band, st); };
-  if (!mcmc::start_population(h, params, model, status.data(), total))
+  if (opts.start) {
+    // a resumed run: the population is the last rows of the run before; c and cur come back from one model call on
+    // them, as start_population evaluates a round (the same bits: the model and chisq_of are the loop's own).  No
+    // draw is made and nothing is counted: the run before counted these models when it proposed them.
+    std::copy(opts.start, opts.start + n * np, x.begin());
+    model(h.x, nch, h.cur, status.data());
+    for (size_t i = 0; i < n; i++)
+      c[i] = status[i] == 0 ? mcmc::chisq_of(h, h.cur + i * nd, h.x + i * np) : INFINITY;
+  } else if (!mcmc::start_population(h, params, model, status.data(), total))
     throw IoError{"mcmc_run_resident: no chain starts on a physical model: check params/pmin/pmax"};
 
   const DeviceObjective consts(objective);
@@ -283,42 +424,87 @@ void mcmc_run_resident(Engine &e, const RetrievalProblem &p, int nch, long nstep
   void *snap_dev = nullptr;
   HIPCHK(hipHostGetDevicePointer(&snap_dev, snap.get(), 0));
   Events events;
-  const long B = opts.block, nblocks = (nsteps + B - 1) / B;
+  const long nblocks = (nsteps + B - 1) / B;
   const unsigned threads = (unsigned)((nch + 63) / 64 * 64);
+  // t counts this call's iterations; the kernel is given the global one
   auto launch = [&](long t, long *snap_slot) {
-    hipLaunchKernelGGL(mcmc_advance, dim3(1), dim3(threads), 0, e.stream, d, t, (int)(t > 0), (int)(t < nsteps),
-                       snap_slot);
+    hipLaunchKernelGGL(mcmc_advance, dim3(1), dim3(threads), 0, e.stream, d, first + t, (int)(t > 0),
+                       (int)(t < nsteps), snap_slot);
     HIPCHK(hipGetLastError());
     if (t < nsteps) step_run_dev(e, d.prop, nch, npars, d_band, d_status, nullptr, e.stream, nullptr);
   };
-  auto finished = [&](long b) {   // block b is done: wait for it and report
+  // Convergence tests: after block b, behind it on the stream, where its end T (iterations of this call) is a
+  // multiple of grcheck or the last one and the rows past the burn-in are enough for a test.  The rows of this call
+  // alone enter: kept row q is global iteration first + (q + 1) thin - 1, so the first one at or past burnin is
+  // (burnin - first) / thin.  One record per block in flight, read in finished(b).
+  const long r0 = std::max(0L, opts.burnin - first) / opts.thin;
+  auto test_rows = [&](long T) {   // the end of the row range of the test after T iterations, or 0: no test there
+    if (opts.grcheck == 0 || (T % opts.grcheck != 0 && T != nsteps)) return 0L;
+    const long r1 = mcmc::kept_rows(T, opts.thin);
+    return gr::testable(nch, r0, r1) ? r1 : 0L;
+  };
+  std::unique_ptr<GrTest> tests;
+  if (opts.grcheck > 0 && gr::testable(nch, r0, nkept)) tests.reset(new GrTest(nch, npars, nkept - r0, 2));
+  bool tested[2] = {false, false};
+  int ntests = 0;
+  long stop = -1, stop_counts[4] = {0, 0, 0, 0};   // grexit: the iterations the result holds, the counters there
+  auto finished = [&](long b) {   // block b is done: wait for it, report, read its test; true: stop here
     HIPCHK(hipEventSynchronize(events.ev[b % 2]));
-    if (!opts.progress) return;
-    long acc = 0;
-    for (size_t i = 0; i < n; i++) acc += snap.get()[(size_t)(b % 2) * n + i];
-    opts.progress(std::min((b + 1) * B, nsteps), acc, opts.progress_user);
+    const long T = std::min((b + 1) * B, nsteps);
+    if (opts.progress) {
+      long acc = 0;
+      for (size_t i = 0; i < n; i++) acc += snap.get()[(size_t)(b % 2) * n + i];
+      opts.progress(T, acc, opts.progress_user);
+    }
+    if (!tested[b % 2]) return false;
+    const int k = ntests++;
+    if (k < opts.ngr) {
+      if (opts.grstat) std::copy(tests->psrf(b % 2), tests->psrf(b % 2) + np, opts.grstat + (size_t)k * np);
+      if (opts.grwhen) opts.grwhen[k] = first + T;
+    }
+    const long *w = tests->words(b % 2);
+    if (!opts.grexit || !w[0]) return false;
+    stop = T;
+    std::copy(w + 1, w + 5, stop_counts);
+    return true;
   };
   launch(0, nullptr);
-  for (long b = 0; b < nblocks; b++) {
-    if (b >= 2) finished(b - 2);   // at most two blocks in flight
+  long enqueued = 0;
+  for (long b = 0; b < nblocks; b++, enqueued++) {
+    if (b >= 2 && finished(b - 2)) break;   // at most two blocks in flight
     const long last = std::min((b + 1) * B, nsteps);
     for (long t = b * B + 1; t <= last; t++)
       launch(t, t == last ? static_cast<long *>(snap_dev) + (size_t)(b % 2) * n : nullptr);
+    const long r1 = test_rows(last);
+    tested[b % 2] = r1 > 0;
+    if (r1 > 0)
+      tests->enqueue(d.chain, nkept, consts.d.stepsize, r0, r1, opts.grthreshold, d_counts, (int)(b % 2), e.stream);
     HIPCHK(hipEventRecord(events.ev[b % 2], e.stream));
   }
-  for (long b = std::max(0L, nblocks - 2); b < nblocks; b++) finished(b);
-  HIPCHK(hipStreamSynchronize(e.stream));
+  for (long b = std::max(0L, enqueued - 2); stop < 0 && b < enqueued; b++) finished(b);
+  HIPCHK(hipStreamSynchronize(e.stream));   // (after a stop: the blocks in flight run out; their rows are not copied)
 
-  const size_t rows = (size_t)nch * nkept;
-  HIPCHK(hipMemcpy(chain, d.chain, sizeof(double) * rows * np, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(chisq, d.chisq, sizeof(double) * rows, hipMemcpyDeviceToHost));
-  if (models) HIPCHK(hipMemcpy(models, d.models, sizeof(double) * rows * nd, hipMemcpyDeviceToHost));
-  add_counters(d_counts, n, total);
+  // the rows of the iterations done, chain by chain: the caller's arrays past them are not written
+  const long done = stop >= 0 ? stop : nsteps, kd = mcmc::kept_rows(done, opts.thin);
+  auto fetch = [&](double *to, const double *from, size_t width) {
+    if (kd == nkept) HIPCHK(hipMemcpy(to, from, sizeof(double) * n * nkept * width, hipMemcpyDeviceToHost));
+    else HIPCHK(hipMemcpy2D(to, sizeof(double) * nkept * width, from, sizeof(double) * nkept * width,
+                       sizeof(double) * kd * width, n, hipMemcpyDeviceToHost));
+  };
+  fetch(chain, d.chain, np);
+  fetch(chisq, d.chisq, 1);
+  if (models) fetch(models, d.models, nd);
+  if (stop >= 0)
+    for (int s = 0; s < 4; s++) total[s] += stop_counts[s];
+  else
+    add_counters(d_counts, n, total);
   if (naccept_out) *naccept_out = total[0];
   if (nbad) {
     nbad[0] = 0;
     for (int s = 1; s < 4; s++) nbad[s] = total[s];
   }
+  if (opts.ngr_out) *opts.ngr_out = ntests;
+  if (opts.done) *opts.done = done;
 }
 
 }  // namespace bartrt

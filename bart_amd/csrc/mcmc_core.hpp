@@ -7,7 +7,8 @@
 // GENERATOR.  Philox4x32-10 (Salmon et al. 2011).  key = (seed low word, seed high word); counter = (t low word,
 // t high word, chain, slot).  t is the iteration, 0 <= t < 2^63; the start of a run draws at t = kStartT + round
 // (round 0: the jittered start, rounds 1..20: the re-draws of chains that start on a rejected model).  No draw
-// depends on how many other draws were made, and the generator has no state anywhere.
+// depends on how many other draws were made, and the generator has no state anywhere: a run resumed at iteration t0
+// (State::first) makes the draws of the global iterations t0, t0 + 1, ... and none at kStartT.
 //
 // Each block of four words gives two uniforms, u0 from words (0, 1) and u1 from words (2, 3): the top 53 bits h of
 // the 64-bit number (word 0 high), u = (h + 0.5) 2^-53 in double arithmetic, and 1 - 2^-53 where that sum rounds to 1
@@ -111,6 +112,8 @@ struct State : Objective {
   int snooker;                               // the walk asked for; it applies with more than three chains
   unsigned long long seed;
   long nsteps, thin;                         // rows t = thin - 1, 2 thin - 1, ... and the last iteration are written
+  long first;                                // this call makes the global iterations first <= t < first + nsteps (a
+                                             // resumed run: first > 0, a multiple of thin); every rule reads the global t
   // the population, kept between the halves
   double *x;        // [nch][npars] current points
   double *c;        // [nch] their chisq (data + prior terms; inf: not on a physical model)
@@ -252,8 +255,8 @@ MCMC_HD void finish(const State &s, long t, int i) {
     s.c[i] = cp;
     s.counts[(size_t)i * 4]++;
   }
-  if ((t + 1) % s.thin != 0 && t != s.nsteps - 1) return;
-  const size_t row = (size_t)i * kept_rows(s.nsteps, s.thin) + (size_t)(t / s.thin);
+  if ((t + 1) % s.thin != 0 && t != s.first + s.nsteps - 1) return;
+  const size_t row = (size_t)i * kept_rows(s.nsteps, s.thin) + (size_t)((t - s.first) / s.thin);
   for (int j = 0; j < np; j++) s.chain[row * np + j] = xi[j];
   s.chisq[row] = s.c[i];
   if (s.models)

@@ -96,11 +96,26 @@ struct McmcOpts {
   long thin = 1, block = 256;
   void (*progress)(long iterations, long naccept, void *user) = nullptr;   // per finished block
   void *progress_user = nullptr;
+  // convergence tests between blocks (gr_core.hpp), exit and resume: include/bartrt.h has the rules
+  long burnin = 0, grcheck = 0;
+  double grthreshold = 0.0;
+  int grexit = 0;
+  double *grstat = nullptr;   // [ngr][npars]
+  long *grwhen = nullptr;     // [ngr]
+  int ngr = 0;
+  int *ngr_out = nullptr;
+  long first = 0;
+  const double *start = nullptr;   // [nchains][npars]
+  long *done = nullptr;
 };
 // chain[nchains][nkept][npars], chisq[nchains][nkept], models[nchains][nkept][ndata] (may be null),
-// nkept = ceil(nsteps / thin)
+// nkept = ceil(nsteps / thin); with grexit only the rows of the iterations done are written
 void mcmc_run_resident(Engine &e, const RetrievalProblem &p, int nchains, long nsteps, const double *params,
                        const McmcOpts &opts, double *chain, double *chisq, double *models, long *naccept, long *nbad);
+// diagnostics (bartrt_mcmc_gr): gr_core.hpp's statistic of a host chain[nchains][nkept][npars], rows [r0, r1),
+// evaluated on the device by the loop's own kernels: psrf[npars], triples[nchains][npars][3], *converged; needs no engine
+void mcmc_gr_probe(const double *chain, int nchains, long nkept, int npars, const double *stepsize, long r0, long r1,
+                   double threshold, double *psrf, double *triples, int *converged);
 // diagnostics (bartrt_mcmc_draws): the core's draws of chains 0 .. nchains - 1 at iteration t, evaluated on the
 // device: out[nchains][9 + npars] (mcmc_core.hpp, draws_row); needs no engine
 void mcmc_draws_probe(unsigned long long seed, unsigned long long t, int nchains, int npars, double *out);

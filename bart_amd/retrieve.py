@@ -21,6 +21,14 @@ least-squares fit first (fit.fit, ``--fit-starts N`` starts, default ``nchains``
 chi-square and the optimum's uncertainties, ``bestFit.txt`` holds the optimum instead of the chain's best sample, and
 the chain starts from it.  ``chisqscale = True`` (with ``leastsq`` only, as in MC3) then multiplies ``uncert`` by
 sqrt(best chisq / (ndata - nfree)).
+
+``--resident`` also honours ``grexit = True``: the Gelman-Rubin statistic is computed on the GPU between blocks of
+iterations (every test is logged) and the run stops at the first test that finds every free parameter converged.  It
+writes ``state.npz`` beside ``output.npy`` (iterations made, seed, nchains, thinning, walk, parameter count, accepted
+proposals, rejected models, best sample); ``--resident --resume`` reads both, refuses a configuration whose seed,
+nchains, thinning, walk or parameter count differ, continues the chain to ``numit`` with the draws an uninterrupted
+run would have made -- ``grexit`` applies again, to the new rows alone: set ``grexit = False`` to run to the end --
+and writes the concatenated ``output.npy``, the concatenated ``savemodel`` file and an appended ``MCMC.log``.
 """
 from __future__ import annotations
 
@@ -62,6 +70,34 @@ def least_squares(w, scfg, nstarts, log):
     return res
 
 
+STATE_KEYS = ("seed", "nchains", "thinning", "walk", "npars")     # what a resumed run must share with the run before
+
+
+def state_of(scfg):
+    return {"seed": int(scfg.seed), "nchains": int(scfg.nchains), "thinning": max(1, int(scfg.thinning)),
+            "walk": str(scfg.walk), "npars": len(scfg.params)}
+
+
+def load_state(out, scfg):
+    """output.npy and state.npz of the run before; ValueError naming the first key of STATE_KEYS that differs."""
+    try:
+        chain = np.load(os.path.join(out, "output.npy"))
+        with np.load(os.path.join(out, "state.npz")) as f:
+            state = {k: f[k][()] for k in f.files}
+    except OSError as err:
+        raise ValueError("--resume: no run to resume in %s (%s)" % (out, err))
+    now = state_of(scfg)
+    for k in STATE_KEYS:
+        if str(state[k]) != str(now[k]):
+            raise ValueError("--resume: `%s` is %s in the configuration and %s in the run to resume (%s): a chain "
+                             "continues under the settings it began with" % (k, now[k], state[k], out))
+    kept = -(-int(state["iterations"]) // now["thinning"])
+    if chain.shape != (now["nchains"], kept, now["npars"]) or int(state["iterations"]) % now["thinning"]:
+        raise ValueError("--resume: output.npy %r does not hold the %d iterations state.npz speaks of, or they do not "
+                         "end on a kept row" % (chain.shape, int(state["iterations"])))
+    return chain, state
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("-c", "--config_file", required=True)
@@ -75,6 +111,8 @@ def main(argv=None):
     ap.add_argument("--resident", action="store_true",
                     help="run the sampler resident on the GPU (sampler.run_resident): reproducible draws, shared "
                          "parameters, priors, thinning and the `savemodel` array of the configuration")
+    ap.add_argument("--resume", action="store_true",
+                    help="with --resident: continue the run whose output.npy and state.npz lie in the output directory")
     ap.add_argument("--leastsq", action="store_true",
                     help="run the multi-start least-squares fit before the chain (fit.fit), as `leastsq = True` in "
                          "the configuration does")
@@ -112,36 +150,71 @@ def main(argv=None):
         engine.comm_init()
     if a.resident and not native:
         ap.error("--resident runs the native way: not with --python-loop, and on several ranks only with --native-sharded")
+    if a.resume and not a.resident:
+        ap.error("--resume continues a --resident run")
+    before = None
+    if a.resume:
+        if scfg.chisqscale:
+            ap.error("--resume: chisqscale rescales the uncertainties from a fit this run does not repeat")
+        try:
+            before = load_state(out, scfg)
+        except ValueError as err:
+            w.close()
+            ap.error(str(err))
+        log("resuming after %d iterations" % int(before[1]["iterations"]))
+        leastsq = False                      # (the chain continues from its own rows, not from an optimum)
     fitted = None
     if leastsq:
         if not native:
             ap.error("leastsq / chisqscale run the native way: not with --python-loop, and on several ranks only with "
                      "--native-sharded")
         fitted = least_squares(w, scfg, a.fit_starts, log)
-    if a.resident:
+    if a.resident and before is not None:
+        res = sampler.run_resident(w, scfg, log=log, first=int(before[1]["iterations"]), start=before[0][:, -1])
+    elif a.resident:
         res = sampler.run_resident(w, scfg, log=log)
     else:
         res = sampler.run_native(w, scfg, log=log) if native else sampler.run(w.step, scfg, log=log)
     dt = time.perf_counter() - t0
-    nmodel = scfg.nchains * max(1, int(np.ceil(scfg.numit / scfg.nchains)))   # (a thinned chain holds fewer rows)
+    nmodel = scfg.nchains * res.get("done", max(1, int(np.ceil(scfg.numit / scfg.nchains))))   # (a thinned chain holds fewer rows)
     log("%d models in %.2f s (%.0f models/s); acceptance %.3f; best chisq %.4f" % (
         nmodel, dt, nmodel / dt, res["accept_rate"], res["best_chisq"]))
     if res["grstat"] is not None:
         log("Gelman-Rubin: " + " ".join("%.3f" % g for g in res["grstat"]))
     log("Bad iterations due to temperature %d, abundance %d, energy %d" % (
         w.nbad[1], w.nbad[2], w.nbad[3]))
+    state = None
+    if a.resident:
+        state = dict(state_of(scfg), iterations=res["done"], naccept=res["accepted"],
+                     nbad=np.array([w.nbad[1], w.nbad[2], w.nbad[3]]), best_chisq=res["best_chisq"], bestp=res["bestp"])
+    if before is not None:
+        # the whole run: the rows, counts and best sample of both calls
+        old = before[1]
+        res["chain"] = np.concatenate([before[0], res["chain"]], axis=1)
+        state.update(iterations=int(old["iterations"]) + res["done"], naccept=int(old["naccept"]) + res["accepted"],
+                     nbad=old["nbad"] + state["nbad"])
+        if float(old["best_chisq"]) <= res["best_chisq"]:
+            res["best_chisq"], res["bestp"] = float(old["best_chisq"]), old["bestp"]
+            state.update(best_chisq=res["best_chisq"], bestp=res["bestp"])
     if rank == 0:
         os.makedirs(out, exist_ok=True)
         np.save(os.path.join(out, "output.npy"), res["chain"])
+        if state is not None:
+            np.savez(os.path.join(out, "state.npz"), **state)
         with open(os.path.join(out, "bestFit.txt"), "w") as f:
             top = fitted if fitted is not None else res    # the optimum, not the chain's best sample
             f.write("# best-fit parameters, chisq = %.6f\n" % top["best_chisq"])
             f.write(" ".join("%.8g" % p for p in top["bestp"]) + "\n")
         if a.resident and native and scfg.savemodel:
             # MC3's layout of `savemodel`: [nchains, ndata, nkept]
-            np.save(os.path.join(out, os.path.basename(scfg.savemodel)),
-                    np.ascontiguousarray(res["models"].transpose(0, 2, 1)))
-        with open(os.path.join(out, "MCMC.log"), "w") as f:
+            name = os.path.join(out, os.path.basename(scfg.savemodel))
+            if not name.endswith(".npy"):
+                name += ".npy"               # (the name np.save gives it)
+            models = np.ascontiguousarray(res["models"].transpose(0, 2, 1))
+            if before is not None and os.path.exists(name):
+                models = np.concatenate([np.load(name), models], axis=2)
+            np.save(name, models)
+        with open(os.path.join(out, "MCMC.log"), "a" if before is not None else "w") as f:
             f.write("\n".join(lines) + "\n")
     if fitted is not None:
         res["fit"] = fitted

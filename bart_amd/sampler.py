@@ -49,6 +49,11 @@ class SamplerConfig:
     # uncertainties rescaled to a reduced chi-square of one at its optimum
     leastsq: bool = False
     chisqscale: bool = False
+    # read by run_resident alone: stop at the first Gelman-Rubin test that finds convergence (MC3's `grexit`); a test
+    # every `grcheck` iterations (None: the multiple of the block nearest above nsteps / 10) against `grthreshold`
+    grexit: bool = False
+    grcheck: int | None = None
+    grthreshold: float = 1.01
 
     @classmethod
     def from_cfg(cls, path: str, section: str = "MCMC") -> "SamplerConfig":
@@ -68,7 +73,10 @@ class SamplerConfig:
                    priorup=arr("priorup") if "priorup" in d else None,
                    thinning=int(d.get("thinning", 1)), savemodel=d.get("savemodel") or None,
                    leastsq=d.get("leastsq", "False").strip() == "True",
-                   chisqscale=d.get("chisqscale", "False").strip() == "True")
+                   chisqscale=d.get("chisqscale", "False").strip() == "True",
+                   grexit=d.get("grexit", "False").strip() == "True",
+                   grcheck=int(d["grcheck"]) if "grcheck" in d else None,
+                   grthreshold=float(d.get("grthreshold", 1.01)))
 
 
 def gelman_rubin(chains: np.ndarray) -> np.ndarray:
@@ -79,6 +87,30 @@ def gelman_rubin(chains: np.ndarray) -> np.ndarray:
     B = n * mean_c.var(axis=0, ddof=1)
     with np.errstate(divide="ignore", invalid="ignore"):
         return np.sqrt(((n - 1) / n * W + B / n) / W)
+
+
+def gelman_rubin_dev(chain: np.ndarray, stepsize, r0: int = 0, r1: int | None = None, threshold: float = 0.0):
+    """The resident loop's convergence test once on the device (``bartrt_mcmc_gr``; csrc/gr_core.hpp states the
+    formula and the order of every sum): chain [nchains, nkept, npars], rows [r0, r1) of every chain ->
+    (psrf [npars], 0 where ``stepsize <= 0``; triples [nchains, npars, 3] = n, mean, sum of squared deviations;
+    converged).  Needs no engine."""
+    from . import transit_module as trm
+    chain = np.ascontiguousarray(chain, np.double)
+    step = np.ascontiguousarray(stepsize, np.double)
+    nch, nkept, npars = chain.shape
+    if step.shape != (npars,):
+        raise ValueError("gelman_rubin_dev: stepsize has one value per parameter")
+    psrf, triples, conv = np.zeros(npars), np.zeros((nch, npars, 3)), C.c_int(0)
+    ptr = lambda v: v.ctypes.data_as(C.c_void_p)
+    trm.check(trm.lib().bartrt_mcmc_gr(ptr(chain), nch, C.c_long(nkept), npars, ptr(step), C.c_long(r0),
+                                       C.c_long(nkept if r1 is None else r1), float(threshold), ptr(psrf),
+                                       ptr(triples), C.cast(C.byref(conv), C.c_void_p)))
+    return psrf, triples, bool(conv.value)
+
+
+def _grexit_ignored(cfg, log, who):
+    if cfg.grexit and log is not None:
+        log("%s: grexit is honoured by run_resident alone; this loop runs all of numit" % who)
 
 
 def _check_stepsize(stepsize):
@@ -116,12 +148,13 @@ def need_whole_grid_or_comm(worker, who: str):
         raise ValueError("%s: the engine is sharded and has no communicator (engine.comm_init); use run()" % who)
 
 
-def _result(chain, chis, naccept, nsteps, nch, cfg, thin=1, **extra):
+def _result(chain, chis, naccept, nsteps, nch, cfg, thin=1, burnin=None, **extra):
     """The result dictionary of the three loops, from chain [nch, nkept, npars] and chis [nch, nkept] (every
-    ``thin``-th of ``nsteps`` iterations): best point, Gelman-Rubin statistic past the burn-in, acceptance rate."""
+    ``thin``-th of ``nsteps`` iterations): best point, Gelman-Rubin statistic past the burn-in (``burnin`` iterations
+    of this chain; None: cfg.burnin), acceptance rate."""
     free = np.where(cfg.stepsize > 0)[0]
     ib = np.unravel_index(np.argmin(chis), chis.shape)
-    post = chain[:, min(cfg.burnin // thin, chain.shape[1] - 1):]
+    post = chain[:, min((cfg.burnin if burnin is None else burnin) // thin, chain.shape[1] - 1):]
     gr = gelman_rubin(post[:, :, free]) if cfg.grtest and post.shape[1] > 3 and nch > 1 else None
     return {"chain": chain, "chisq": chis, "bestp": chain[ib], "best_chisq": float(chis[ib]),
             "accept_rate": naccept / (nsteps * nch), "grstat": gr, "free": free, **extra}
@@ -133,6 +166,7 @@ def run(model, cfg: SamplerConfig, log=None):
     best_chisq, accept_rate, grstat)."""
     rng = np.random.default_rng(cfg.seed)
     _check_stepsize(cfg.stepsize)
+    _grexit_ignored(cfg, log, "run")
     free = np.where(cfg.stepsize > 0)[0]
     nfree, nch = len(free), cfg.nchains
     nsteps = max(1, int(np.ceil(cfg.numit / nch)))
@@ -249,6 +283,7 @@ def run_native(worker, cfg: SamplerConfig, log=None):
     need_whole_grid_or_comm(worker, "run_native")
     nch = cfg.nchains
     _check_stepsize(cfg.stepsize)
+    _grexit_ignored(cfg, log, "run_native")
     nsteps = max(1, int(np.ceil(cfg.numit / nch)))
     par, pmin, pmax, step, data, unc, _ = problem_arrays(cfg, "run_native")     # (this loop takes no priors)
     npars = len(par)
@@ -273,7 +308,10 @@ class McmcOpts(C.Structure):
     """``bartrt_mcmc_opts`` of include/bartrt.h."""
     _fields_ = [("size", C.c_ulong), ("snooker", C.c_int), ("seed", C.c_ulonglong), ("thin", C.c_long),
                 ("block", C.c_long), ("prior", C.c_void_p), ("priorlow", C.c_void_p), ("priorup", C.c_void_p),
-                ("progress", C.c_void_p), ("progress_user", C.c_void_p)]
+                ("progress", C.c_void_p), ("progress_user", C.c_void_p),
+                ("burnin", C.c_long), ("grcheck", C.c_long), ("grthreshold", C.c_double), ("grexit", C.c_int),
+                ("grstat", C.c_void_p), ("grwhen", C.c_void_p), ("ngr", C.c_int), ("ngr_out", C.c_void_p),
+                ("first", C.c_long), ("start", C.c_void_p), ("done", C.c_void_p)]
 
 
 PROGRESS = C.CFUNCTYPE(None, C.c_long, C.c_long, C.c_void_p)
@@ -289,7 +327,7 @@ def draws(seed: int, t: int, nchains: int, npars: int) -> np.ndarray:
     return out
 
 
-def run_resident(worker, cfg: SamplerConfig, log=None, block: int = 256):
+def run_resident(worker, cfg: SamplerConfig, log=None, block: int = 256, first: int = 0, start=None):
     """The sampler resident on the GPU through ``bartrt_mcmc_run_resident`` (csrc/mcmc.hip, csrc/mcmc_core.hpp):
     population, chi-squares and counters stay in device memory and an iteration is one small sampler launch plus the
     model's launches, enqueued without a host wait, ``block`` iterations at a time.  Its draws come from a
@@ -300,29 +338,64 @@ def run_resident(worker, cfg: SamplerConfig, log=None, block: int = 256):
     1024 chains and 64 parameters.  Sharded engines as :func:`run_native`: with the library's communicator every rank
     makes this call in lockstep and gets the same chains.
 
+    Convergence.  With ``cfg.grtest`` the Gelman-Rubin statistic of the rows past ``cfg.burnin`` is computed on the
+    device every ``cfg.grcheck`` iterations and after the last one (csrc/gr_core.hpp; default spacing: the multiple
+    of ``block`` nearest above nsteps / 10; ``block`` itself is lowered to a given ``cfg.grcheck`` and raised to a
+    multiple of the thinning, which changes no byte of the chain), and with ``cfg.grexit`` the run stops at the first test in which every free parameter lies
+    below ``cfg.grthreshold``.  ``first`` / ``start`` resume a run: ``start`` [nchains, npars] are the last rows of
+    the run before, ``first`` (a multiple of the thinning) the iterations it made; the call continues to the same
+    total ceil(numit / nchains) with the draws of those iterations, so that the rows of both calls together are the
+    bytes of one uninterrupted run.  The tests of a resumed call see that call's rows alone.
+
     Speed: SLOWER than :func:`run_native` as measured (MEASUREMENTS.md row 17; one MI355X, ten chains, snooker):
     7 745 against 9 045 iterations/s on the headline shape, 10 948 against 15 528 on the WASP-12b shape, 11 163
     against 14 896 on the demo shape -- the one-lane-per-chain sampler launch costs more than the host round trip it
-    removes.  Opt-in for what else it gives; :func:`run_native` stays the default.
+    removes.  Opt-in for what else it gives; :func:`run_native` stays the default.  What the convergence tests cost
+    at their default spacing: about 1 % on the headline shape at 400 iterations (two tests), no more than the loop's
+    own run-to-run spread (MEASUREMENTS.md row 21).
 
     Returns the dictionary of :func:`run_native` (``chain`` [nchains, nkept, npars], ``chisq`` [nchains, nkept],
-    nkept = ceil(nsteps / thinning)) plus ``models`` [nchains, nkept, ndata]: the band fluxes of each chain's current
-    state at the kept iterations."""
+    nkept = ceil(done / thinning)) plus ``models`` [nchains, nkept, ndata]: the band fluxes of each chain's current
+    state at the kept iterations; ``done``: the iterations this call made; ``grhistory``: (when [ntests] global
+    iteration counts, psrf [ntests, npars]); ``converged``: whether the last test made found convergence; ``accepted``: the proposals accepted in those
+    iterations."""
     from . import transit_module as trm
     need_whole_grid_or_comm(worker, "run_resident")
     nch = cfg.nchains
-    nsteps = max(1, int(np.ceil(cfg.numit / nch)))
+    total = max(1, int(np.ceil(cfg.numit / nch)))
+    first = int(first)
+    nsteps = total - first
+    if nsteps < 1:
+        raise ValueError("run_resident: the run before already made %d of %d iterations" % (first, total))
     thin = max(1, int(cfg.thinning))
     nkept = -(-nsteps // thin)
     par, pmin, pmax, step, data, unc, pri = problem_arrays(cfg, "run_resident")
     npars = len(par)
     ptr = lambda v: v.ctypes.data_as(C.c_void_p)
-    opts = McmcOpts(size=C.sizeof(McmcOpts), snooker=int(cfg.walk == "snooker"), seed=cfg.seed, thin=thin, block=block)
+    grcheck = 0
+    if cfg.grtest and nch > 1:
+        if cfg.grcheck:                      # a spacing of the caller's: no block is longer than it
+            block = min(block, int(cfg.grcheck))
+        block = -(-block // thin) * thin
+        grcheck = int(cfg.grcheck) if cfg.grcheck else max(1, -(-nsteps // (10 * block))) * block
+    opts = McmcOpts(size=C.sizeof(McmcOpts), snooker=int(cfg.walk == "snooker"), seed=cfg.seed, thin=thin, block=block,
+                    burnin=int(cfg.burnin), grcheck=grcheck, grthreshold=float(cfg.grthreshold),
+                    grexit=int(bool(cfg.grexit)), first=first)
     if pri is not None:
         opts.prior, opts.priorlow, opts.priorup = (v.ctypes.data for v in pri)
+    if start is not None:
+        start = np.ascontiguousarray(start, np.double)
+        if start.shape != (nch, npars):
+            raise ValueError("run_resident: start holds one row per chain")
+        opts.start = start.ctypes.data
     if log is not None:
-        report = PROGRESS(lambda it, acc, _: log("step %d/%d  acceptance %.2f" % (it, nsteps, acc / (it * nch))))
+        report = PROGRESS(lambda it, acc, _: log("step %d/%d  acceptance %.2f" % (first + it, total, acc / (it * nch))))
         opts.progress = C.cast(report, C.c_void_p)
+    ngr = nsteps // grcheck + 1 if grcheck > 0 else 0
+    grstat, grwhen = np.zeros((max(ngr, 1), npars)), np.zeros(max(ngr, 1), np.int64)
+    made, done = C.c_int(0), C.c_long(0)
+    opts.grstat, opts.grwhen, opts.ngr = grstat.ctypes.data, grwhen.ctypes.data, ngr
+    opts.ngr_out, opts.done = C.addressof(made), C.addressof(done)
     chain = np.zeros((nch, nkept, npars))
     chis = np.zeros((nch, nkept))
     models = np.zeros((nch, nkept, len(data)))
@@ -334,7 +407,22 @@ def run_resident(worker, cfg: SamplerConfig, log=None, block: int = 256):
         C.cast(C.byref(nacc), C.c_void_p), C.cast(nbad, C.c_void_p)))
     for k in (1, 2, 3):
         worker.nbad[k] += int(nbad[k])
+    # the rows of the iterations done (all of them unless grexit stopped the run)
+    kd = -(-done.value // thin)
+    chain, chis, models = (np.ascontiguousarray(v[:, :kd]) for v in (chain, chis, models))
+    when, psrf = grwhen[:made.value].copy(), grstat[:made.value].copy()
+    free = step > 0
+    last_ok = lambda r: bool(free.any() and np.all(np.isfinite(r[free])) and np.all(r[free] < cfg.grthreshold))
+    converged = made.value > 0 and last_ok(psrf[-1])
     if log is not None:
+        for k in range(made.value):
+            log("Gelman-Rubin after %d iterations: %s" % (when[k], " ".join("%.4f" % g for g in psrf[k][free])))
+            if last_ok(psrf[k]):
+                log("All parameters have converged to within %.3g%% of unity." % (100.0 * (cfg.grthreshold - 1.0)))
+        if done.value < nsteps:
+            log("grexit: stopped after %d of %d iterations" % (first + done.value, total))
         log("%d iterations of %d chains; best chisq %.4f  acceptance %.2f" % (
-            nsteps, nch, float(chis.min()), nacc.value / (nsteps * nch)))
-    return _result(chain, chis, nacc.value, nsteps, nch, cfg, thin, models=models)
+            done.value, nch, float(chis.min()), nacc.value / (done.value * nch)))
+    return _result(chain, chis, nacc.value, done.value, nch, cfg, thin, burnin=max(0, cfg.burnin - first),
+                   models=models, done=done.value, grhistory=(when, psrf), converged=converged,
+                   accepted=nacc.value)

@@ -295,8 +295,34 @@ int bartrt_mcmc_run(int nchains, int npars, long nsteps, const double *params, c
  * At most 1024 chains and 64 parameters (BARTRT_EINVAL beyond; larger populations stay with bartrt_mcmc_run).
  * Sharded engines: whatever the step serves.  LOCKSTEP as for bartrt_mcmc_run: with a communicator attached every
  * rank makes this call with the same arguments, the step's all-gather leaves the same band-flux bits on every rank,
- * so every rank advances the same population and writes the same chain.  Chain-service clients and line-by-line
- * engines with a communicator: BARTRT_ENOTSUP. */
+ * so every rank advances the same population and writes the same chain.  The convergence tests below read that
+ * chain and nothing else: every rank computes the same statistic bits, takes the same decision at the same block,
+ * and has issued the same collectives when it stops.  Chain-service clients and line-by-line engines with a
+ * communicator: BARTRT_ENOTSUP.
+ *
+ * CONVERGENCE TESTS (MC3's grtest / grexit).  grcheck = n > 0: after every n iterations of this call, and after the
+ * last one, the Gelman-Rubin statistic of the rows so far is computed ON THE DEVICE from the chain where it lies
+ * (bart_amd/csrc/gr_core.hpp states the formula and the fixed order of every sum), enqueued behind the block that
+ * ends there.  n must be a multiple of block, and block of thin (BARTRT_EINVAL otherwise), so that every test falls
+ * on a block end whose state is a kept row.  Rows of global iterations t < burnin never enter; a test needs two
+ * chains and four rows, and where there are fewer none is made or recorded.  Test k is recorded in
+ * grstat[k][npars] (0 for parameters that are not free) and grwhen[k] (the GLOBAL iteration count at the test) while
+ * k < ngr; *ngr_out is the number of tests made.  grthreshold 0 reads as 1.01 (MC3's "within 1% of unity", as we
+ * recall it).  A test finds convergence when every free parameter's statistic is finite and below the threshold.
+ * grexit != 0: the call stops at the first test that finds convergence, at iteration count T of this call:
+ * *done = T (otherwise nsteps), chain / chisq / models hold the ceil(T / thin) rows of each chain up to there at the
+ * places they have in the full arrays -- THE ARRAYS KEEP THEIR FULL SHAPE [nchains][nkept] AND ARE NOT WRITTEN PAST
+ * THOSE ROWS -- and naccept / nbad are the counts as they stood at T.  A test's record is read when the host next
+ * waits for its block, so up to two further blocks have been enqueued by then; their iterations are discarded, and
+ * the stopping point does not depend on timing.
+ *
+ * RESUME.  first = t0 > 0 with start[nchains][npars] (the last rows of the run before; both or neither, and t0 a
+ * multiple of thin: BARTRT_EINVAL otherwise) makes the global iterations t0 ... t0 + nsteps - 1 with the draws of
+ * those t; the start's draws are not made and params is not read.  Every rule that reads t -- the gamma = 1 move
+ * every tenth iteration, the thinning rule -- uses the global value.  The chains' chi-squares and band fluxes are
+ * rebuilt by one model call on the rows of start (a row the model rejects: chisq inf).  A run of N iterations, and a
+ * run of N1 followed by a resumed run of N - N1, write the same bytes.  The tests of a resumed call see that call's
+ * rows alone (t >= max(burnin, t0)): they know nothing of the run before. */
 typedef struct bartrt_mcmc_opts {
   unsigned long size;                 /* sizeof(bartrt_mcmc_opts) of the caller */
   int snooker;                        /* 0: demc, 1: snooker */
@@ -306,6 +332,17 @@ typedef struct bartrt_mcmc_opts {
   const double *prior, *priorlow, *priorup;
   void (*progress)(long iterations, long naccept, void *user);
   void *progress_user;
+  long burnin;                        /* rows of global iterations t < burnin enter no test */
+  long grcheck;                       /* a test every grcheck iterations and after the last; 0: none */
+  double grthreshold;                 /* 0 reads as 1.01 */
+  int grexit;                         /* stop at the first test that finds convergence */
+  double *grstat;                     /* [ngr][npars], may be NULL */
+  long *grwhen;                       /* [ngr], may be NULL */
+  int ngr;
+  int *ngr_out;                       /* tests made, may be NULL */
+  long first;                         /* resume: the global iteration this call starts at */
+  const double *start;                /* resume: [nchains][npars] */
+  long *done;                         /* iterations of this call the result holds, may be NULL */
 } bartrt_mcmc_opts;
 int bartrt_mcmc_run_resident(int nchains, int npars, long nsteps, const double *params, const double *pmin,
                              const double *pmax, const double *stepsize, int ndata, const double *data,
@@ -316,6 +353,14 @@ int bartrt_mcmc_run_resident(int nchains, int npars, long nsteps, const double *
  * uniform, the partners r1, r2, z (z = -1 with fewer than four chains) and the jitter normal of each parameter.
  * Needs no engine. */
 int bartrt_mcmc_draws(unsigned long long seed, unsigned long long t, int nchains, int npars, double *out);
+/* Diagnostics: the resident loop's convergence test once ON THE DEVICE, by its own kernels, on a host
+ * chain[nchains][nkept][npars], rows [r0, r1) of every chain: psrf[npars] (0 for parameters that are not free:
+ * stepsize[j] <= 0), triples[nchains][npars][3] = (n, mean, sum of squared deviations) of every chain and free
+ * parameter, *converged as bartrt_mcmc_run_resident decides it (threshold 0 reads as 1.01).  Fewer than two chains
+ * or four rows: no test, every output zero.  The bits are those of a host build of bart_amd/csrc/gr_core.hpp.  At
+ * most 64 parameters.  Needs no engine. */
+int bartrt_mcmc_gr(const double *chain, int nchains, long nkept, int npars, const double *stepsize, long r0, long r1,
+                   double threshold, double *psrf, double *triples, int *converged);
 /* Least-squares fit before the chain (MC3's `leastsq`): nstarts independent Levenberg-Marquardt fits inside the box
  * [pmin, pmax], advanced together on the GPU.  An iteration is two batched model launches -- the nstarts * nfree
  * forward-difference rows of the Jacobians (h_j = fdstep * stepsize_j, the sign flipped at the upper bound), then the

@@ -3,7 +3,7 @@ iteration) in its three forms: the Python loop (sampler.run), the native host lo
 resident on the GPU (sampler.run_resident).
 
     python tools/retrieval_rate.py                        WASP-12b shape, 10 and 32 chains, every loop
-    python tools/retrieval_rate.py --shape headline|wasp|demo [--loops native,resident] [--repeat 3]
+    python tools/retrieval_rate.py --shape headline|wasp|demo [--loops native,resident,resident_nogr] [--repeat 3]
                                                           ten chains, snooker, 400 iterations after a warm-up run
 
 Shapes: headline = 100 layers x 1e4 samples, 4 molecules, 10 filters, energy balance (the bench's step); wasp = the
@@ -11,6 +11,7 @@ WASP-12b retrieval grid (2424 samples, 4 molecules, 4 filters; BASELINE config 4
 examples/demo (2501 samples, CH4, 10 filters).  With BARTRT_LIBPATH naming a library built from an earlier commit
 (tools/ab_build.py) the resident row is left out: that library does not have the call."""
 import argparse
+import dataclasses
 import json
 import os
 import sys
@@ -49,9 +50,12 @@ w = BARTfunc.Worker(BARTfunc.WorkerConfig.from_cfg(cfg))
 data = w.step(truth)[0]
 loops = {"python": ("python loop", lambda c: sampler.run(w.step, c)),
          "native": ("native loop", lambda c: sampler.run_native(w, c)),
-         "resident": ("resident loop", lambda c: sampler.run_resident(w, c))}
+         "resident": ("resident loop", lambda c: sampler.run_resident(w, c)),
+         # (the same loop without its Gelman-Rubin tests between blocks)
+         "resident_nogr": ("resident loop, grtest off", lambda c: sampler.run_resident(w, dataclasses.replace(c, grtest=False)))}
 if not hasattr(trm.lib(), "bartrt_mcmc_run_resident"):
     loops.pop("resident")
+    loops.pop("resident_nogr")
 build_id = trm.lib().bartrt_build_id().decode()
 for nch in ((10, 32) if a.shape is None else (10,)):
     numit = 400 * nch
