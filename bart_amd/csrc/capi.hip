@@ -1017,6 +1017,7 @@ int bartrt_mcmc_run_resident(int nchains, int npars, long nsteps, const double *
   m.burnin = o.burnin; m.grcheck = o.grcheck; m.grthreshold = o.grthreshold; m.grexit = o.grexit;
   m.grstat = o.grstat; m.grwhen = o.grwhen; m.ngr = o.ngr; m.ngr_out = o.ngr_out;
   m.first = o.first; m.start = o.start; m.done = o.done;
+  m.walk = o.walk;
   return guarded([&] {
     mcmc_run_resident(*g_eng, p, nchains, nsteps, params, m, chain, chisq, models, naccept, nbad);
     return BARTRT_OK;
@@ -1036,6 +1037,32 @@ int bartrt_mcmc_draws(unsigned long long seed, unsigned long long t, int nchains
   if (!out) return fail(BARTRT_EINVAL, "bartrt_mcmc_draws: null buffer");
   return guarded([&] {
     mcmc_draws_probe(seed, t, nchains, npars, out);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_grid_run(int nrows, int npars, long nsteps, const double *params, const double *pmin, const double *pmax,
+                    const double *stepsize, const bartrt_grid_opts *opts, long *nbad) {
+  NEED_ENGINE();
+  if (!g_eng->step) return fail(BARTRT_EINVAL, "grid_run: call bartrt_step_setup first");
+  if (!params || !pmin || !pmax || !stepsize) return null_buffer("grid_run");
+  bartrt_grid_opts o;
+  if (!opts || !sized_copy(opts, &o)) return fail(BARTRT_EINVAL, "grid_run: opts with opts->size set and a sink");
+  GridOpts g;
+  g.seed = o.seed; g.chunk = o.chunk; g.first = o.first;
+  g.spectra = o.spectra != 0; g.f32 = o.f32 != 0;
+  g.sink = o.sink; g.user = o.user;
+  return guarded([&] {
+    const int rc = grid_run(*g_eng, nrows, npars, nsteps, params, pmin, pmax, stepsize, g, nbad);
+    return rc ? fail(rc, "grid_run: the sink stopped the run with " + std::to_string(rc)) : BARTRT_OK;
+  });
+}
+
+int bartrt_grid_draws(unsigned long long seed, unsigned long long t, int nrows, int npars, const double *params,
+                      const double *pmin, const double *pmax, const double *stepsize, double *out) {
+  if (!params || !pmin || !pmax || !stepsize || !out) return null_buffer("bartrt_grid_draws");
+  return guarded([&] {
+    grid_draws_probe(seed, t, nrows, npars, params, pmin, pmax, stepsize, out);
     return BARTRT_OK;
   });
 }

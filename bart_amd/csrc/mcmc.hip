@@ -348,6 +348,11 @@ void mcmc_run_resident(Engine &e, const RetrievalProblem &p, int nch, long nstep
     throw std::invalid_argument("mcmc_run_resident: at most 1024 chains (one workgroup); more stay with mcmc_run");
   if (npars > mcmc::kMaxPars) throw std::invalid_argument("mcmc_run_resident: too many parameters (at most 64)");
   if (opts.thin < 1 || opts.block < 1) throw std::invalid_argument("mcmc_run_resident: thin and block must be >= 1");
+  if (opts.walk == mcmc::kWalkUnif)
+    throw std::invalid_argument("mcmc_run_resident: walk = 3 (unif) is not a chain: bartrt_grid_run makes model grids");
+  if (opts.walk != 0 && opts.walk != mcmc::kWalkMrw)
+    throw std::invalid_argument("mcmc_run_resident: walk = " + std::to_string(opts.walk) +
+                                " is not one of 0 (demc / snooker) and 2 (mrw)");
   const long first = opts.first, B = opts.block;
   if (first < 0 || (first > 0) != (opts.start != nullptr))
     throw std::invalid_argument("mcmc_run_resident: first > 0 and start come together (a resumed run), or neither");
@@ -372,6 +377,7 @@ void mcmc_run_resident(Engine &e, const RetrievalProblem &p, int nch, long nstep
   static_cast<Objective &>(h) = objective;
   h.nch = nch; h.snooker = opts.snooker; h.seed = opts.seed; h.nsteps = nsteps; h.thin = opts.thin;
   h.first = first;
+  h.walk = opts.walk;
   h.x = x.data(); h.c = c.data(); h.cur = cur.data();
   auto model = [&](const double *rows, int m, double *band, int *st) { step_run_host(e, rows, m, npars, band, st); };
   if (opts.start) {

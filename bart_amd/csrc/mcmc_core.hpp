@@ -1,6 +1,6 @@
-// The sampler's arithmetic, stated once for host and device: the counter-based random draws, the DEMC and snooker
-// moves, shared parameters, Gaussian priors and the acceptance rule of the resident loop (mcmc.hip: mcmc_advance,
-// mcmc_run_resident).  Plain inline functions on plain pointers, no HIP call: the kernel runs them one chain per
+// The sampler's arithmetic, stated once for host and device: the counter-based random draws, the DEMC, snooker and
+// Metropolis random-walk moves, shared parameters, Gaussian priors and the acceptance rule of the resident loop
+// (mcmc.hip: mcmc_advance, mcmc_run_resident).  Plain inline functions on plain pointers, no HIP call: the kernel runs them one chain per
 // lane, the host runs them for the start of a run, and a host compiler alone builds them for the CPU tests
 // (tests/mcmc_core_host.cpp).
 //
@@ -19,8 +19,18 @@
 //   0           partner r1                       partner r2
 //   1           snooker's third chain z          snooker's gamma = 1.2 + u1
 //   2           acceptance uniform               (unused)
-//   3 + j / 2   jitter normal of parameter j     jitter normal of parameter j + 1       (j even; DEMC moves and the
-//                                                                                        start, free parameters only)
+//   3 + j / 2   jitter normal of parameter j     jitter normal of parameter j + 1       (j even; DEMC and mrw moves and
+//                                                                                        the start, free parameters only)
+//
+// The model grids of `walk = unif` (grid_core.hpp) read the same jitter slots as UNIFORMS: u0 for parameter j, u1 for
+// parameter j + 1, no Box-Muller.
+//
+// WALKS.  State::walk = 0: DEMC or, with State::snooker and more than three chains, snooker (every tenth iteration a
+// DEMC move with gamma = 1).  walk = kWalkMrw: Metropolis random walk, prop_j = x_j + stepsize_j n_j for every free
+// parameter j with the jitter normal n_j of the table, logjac = 0; no partner is drawn (slots 0 and 1 go unread), no
+// rule of the move reads t, and any number of chains >= 1 will do: the chains do not see one another.  kWalkUnif is
+// not a walk of this loop (no data, no acceptance): grid_core.hpp and grid.hip serve it.  Whatever the walk, the box
+// test, shared parameters, the acceptance rule, priors, thinning and the output rows are the one common path below.
 //
 // PARAMETERS.  Free, fixed and shared as retrieval.hpp reads `stepsize`; DEMC moves, jitter and the box touch the free
 // ones alone, and shared ones follow in every proposal and start point.
@@ -44,6 +54,7 @@ constexpr int kMaxChains = 1024;
 constexpr unsigned kSlotPartners = 0, kSlotSnooker = 1, kSlotAccept = 2, kSlotJitter = 3;
 constexpr unsigned long long kStartT = 0xFFFFFFFFFFFFFF00ull;
 constexpr int kStartRounds = 20;
+constexpr int kWalkMrw = 2, kWalkUnif = 3;   // State::walk (0: as State::snooker says); MC3's `walk` keys mrw and unif
 
 struct Words {
   uint32_t w[4];
@@ -128,6 +139,7 @@ struct State : Objective {
   // results
   double *chain, *chisq;  // [nch][nkept][npars], [nch][nkept]
   double *models;         // [nch][nkept][ndata] band fluxes of the chains' current states, or null
+  int walk;               // 0: DEMC / snooker as `snooker` says; kWalkMrw: Metropolis random walk
 };
 
 MCMC_HD long kept_rows(long nsteps, long thin) { return (nsteps + thin - 1) / thin; }
@@ -180,14 +192,25 @@ MCMC_HD void start_point(const State &s, int round, int i, const double *params,
   copy_shared(s.npars, s.stepsize, xi);
 }
 
-// First half of iteration t for chain i: the proposal from the population x into row i of prop.  A proposal outside
-// the box is not sent to the model: the row gets the chain's current point and inside[i] = 0.
-MCMC_HD void propose(const State &s, long t, int i) {
+// The moves: from chain i's point xi into pi, which holds a copy of xi; free parameters only.  Returns logjac.
+// Metropolis random walk: every free parameter moves by its own stepsize times its jitter normal.
+MCMC_HD double move_mrw(const State &s, long t, int i, const double *xi, double *pi) {
+  MCMC_EXACT
+  for (int j = 0; j < s.npars; j += 2) {
+    const bool f0 = s.stepsize[j] > 0, f1 = j + 1 < s.npars && s.stepsize[j + 1] > 0;
+    if (!f0 && !f1) continue;
+    double n0, n1;
+    normals(s.seed, (unsigned long long)t, i, kSlotJitter + j / 2, n0, n1);
+    if (f0) pi[j] = xi[j] + s.stepsize[j] * n0;
+    if (f1) pi[j + 1] = xi[j + 1] + s.stepsize[j + 1] * n1;
+  }
+  return 0.0;
+}
+
+// DEMC and snooker: the moves that read the population
+MCMC_HD double move_population(const State &s, long t, int i, const double *xi, double *pi) {
   MCMC_EXACT
   const int nch = s.nch, np = s.npars;
-  const double *xi = s.x + (size_t)i * np;
-  double *pi = s.prop + (size_t)i * np;
-  for (int j = 0; j < np; j++) pi[j] = xi[j];
   double u0, u1;
   uniforms(s.seed, (unsigned long long)t, i, kSlotPartners, u0, u1);
   const int r1 = nch > 1 ? other(u0, nch, i, -1, -1) : i;
@@ -224,6 +247,19 @@ MCMC_HD void propose(const State &s, long t, int i) {
       if (f1) pi[j + 1] = xi[j + 1] + gam * (x1[j + 1] - x2[j + 1]) + 1e-3 * s.stepsize[j + 1] * n1;
     }
   }
+  return logjac;
+}
+
+// First half of iteration t for chain i: the proposal from the population x into row i of prop.  A proposal outside
+// the box is not sent to the model: the row gets the chain's current point and inside[i] = 0.
+MCMC_HD void propose(const State &s, long t, int i) {
+  MCMC_EXACT
+  const int np = s.npars;
+  const double *xi = s.x + (size_t)i * np;
+  double *pi = s.prop + (size_t)i * np;
+  for (int j = 0; j < np; j++) pi[j] = xi[j];
+  // (one walk per run: the branch is the same for every chain)
+  const double logjac = s.walk == kWalkMrw ? move_mrw(s, t, i, xi, pi) : move_population(s, t, i, xi, pi);
   int in = 1;
   for (int j = 0; j < np; j++)
     if (s.stepsize[j] > 0) in = in && pi[j] >= s.pmin[j] && pi[j] <= s.pmax[j];

@@ -107,6 +107,7 @@ struct McmcOpts {
   long first = 0;
   const double *start = nullptr;   // [nchains][npars]
   long *done = nullptr;
+  int walk = 0;   // 0: demc / snooker as `snooker` says; mcmc::kWalkMrw: Metropolis random walk
 };
 // chain[nchains][nkept][npars], chisq[nchains][nkept], models[nchains][nkept][ndata] (may be null),
 // nkept = ceil(nsteps / thin); with grexit only the rows of the iterations done are written
@@ -119,6 +120,26 @@ void mcmc_gr_probe(const double *chain, int nchains, long nkept, int npars, cons
 // diagnostics (bartrt_mcmc_draws): the core's draws of chains 0 .. nchains - 1 at iteration t, evaluated on the
 // device: out[nchains][9 + npars] (mcmc_core.hpp, draws_row); needs no engine
 void mcmc_draws_probe(unsigned long long seed, unsigned long long t, int nchains, int npars, double *out);
+// Model grids (MC3's `walk = unif`; grid.hip, samples in grid_core.hpp): per iteration nrows parameter vectors drawn
+// uniformly in the box, one step_run_dev on them and their model rows packed into a chunk slot, enqueued without a
+// host wait; chunks of `chunk` iterations copied to pinned memory and handed to `sink`, two chunks in flight.
+struct GridOpts {
+  unsigned long long seed = 0;
+  long chunk = 0, first = 0;   // iterations per chunk (0: the whole run); the global iteration of this call's first
+  int spectra = 0, f32 = 0;    // whole spectra [Wfull] instead of band fluxes [nfilters]; rows as float
+  // chunk k: global iterations t0 .. t0 + niter - 1; params [niter][nrows][npars], status [niter][nrows], rows
+  // [niter][nrows][width] (double or float); non-zero: stop
+  int (*sink)(long k, long t0, long niter, const double *params, const int *status, const void *rows,
+              void *user) = nullptr;
+  void *user = nullptr;
+};
+// 0, or what the sink returned when it stopped the run; nbad[4] (may be null): rows rejected with status 1, 2, 3
+int grid_run(Engine &e, int nrows, int npars, long nsteps, const double *params, const double *pmin,
+             const double *pmax, const double *stepsize, const GridOpts &opts, long *nbad);
+// diagnostics (bartrt_grid_draws): the samples of iteration t, rows 0 .. nrows - 1, evaluated on the device:
+// out[nrows][npars]; needs no engine
+void grid_draws_probe(unsigned long long seed, unsigned long long t, int nrows, int npars, const double *params,
+                      const double *pmin, const double *pmax, const double *stepsize, double *out);
 // Batched multi-start Levenberg-Marquardt fit in the box (fit.hip; arithmetic in fit_core.hpp): per iteration the
 // S * nfree forward-difference rows and the S * nrungs trial rows in one step_run_dev each, one fit_advance launch
 // (one wave per start) after either, no host wait but every `check` iterations.

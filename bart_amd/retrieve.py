@@ -29,6 +29,14 @@ proposals, rejected models, best sample); ``--resident --resume`` reads both, re
 nchains, thinning, walk or parameter count differ, continues the chain to ``numit`` with the draws an uninterrupted
 run would have made -- ``grexit`` applies again, to the new rows alone: set ``grexit = False`` to run to the end --
 and writes the concatenated ``output.npy``, the concatenated ``savemodel`` file and an appended ``MCMC.log``.
+``--resident`` is also the loop that serves ``walk = mrw``; the other two refuse it.
+
+``walk = unif`` makes a MODEL GRID instead of a chain (sampler.run_grid; INTEGRATION.md, "Model grids"): parameters
+drawn uniformly in [pmin, pmax], no ``data`` / ``uncert`` needed, every model kept whole.  It writes ``output.npy``
+(the parameters, [nchains, niter, npars]), ``status.npy`` ([nchains, niter]) and the models under the name of
+``savemodel``: one file [nchains, width, niter] with ``modelper = 0``, else ``<stem>/<stem>_<k, five digits>.npy`` of
+``modelper`` iterations each, written as the chunks arrive.  Whole spectra by default; ``--grid-bands`` keeps band
+fluxes, ``--grid-f32`` writes float.
 """
 from __future__ import annotations
 
@@ -67,6 +75,43 @@ def least_squares(w, scfg, nstarts, log):
         factor = float(np.sqrt(res["best_chisq"] / (ndata - nfree)))
         scfg.uncert = np.asarray(scfg.uncert, float) * factor
         log("chisqscale: uncertainties multiplied by %.6g (reduced chisq %.6g)" % (factor, factor * factor))
+    return res
+
+
+def model_grid(w, scfg, a, out, rank, log):
+    """`walk = unif`: the grid through sampler.run_grid and its files (the module's docstring has the layout).
+    Returns run_grid's dictionary of the collected run, or its counts where the models went to chunk files."""
+    stem = os.path.basename(scfg.savemodel)
+    stem = stem[:-4] if stem.endswith(".npy") else stem
+    kw = dict(spectra=not a.grid_bands, f32=a.grid_f32)
+    t0 = time.perf_counter()
+    if rank == 0:
+        os.makedirs(out, exist_ok=True)
+    if scfg.modelper > 0:
+        pars, stats = [], []
+        if rank == 0:
+            os.makedirs(os.path.join(out, stem), exist_ok=True)
+
+        def sink(k, t0_, params, status, models):
+            pars.append(params.copy())
+            stats.append(status.copy())
+            if rank == 0:                # MC3's layout of a model file: [nchains, width, iterations]
+                np.save(os.path.join(out, stem, "%s_%05d.npy" % (stem, k)),
+                        np.ascontiguousarray(models.transpose(1, 2, 0)))
+        res = sampler.run_grid(w, scfg, sink=sink, **kw)
+        res["params"] = np.ascontiguousarray(np.concatenate(pars, axis=0).swapaxes(0, 1))
+        res["status"] = np.ascontiguousarray(np.concatenate(stats, axis=0).swapaxes(0, 1))
+    else:
+        res = sampler.run_grid(w, scfg, **kw)
+        if rank == 0:
+            np.save(os.path.join(out, stem + ".npy"), np.ascontiguousarray(res["models"].transpose(0, 2, 1)))
+    dt = time.perf_counter() - t0
+    nmodel = res["status"].size
+    log("%d models in %.2f s (%.0f models/s); %d of them rejected" % (nmodel, dt, nmodel / dt, sum(res["nbad"])))
+    log("Bad iterations due to temperature %d, abundance %d, energy %d" % (w.nbad[1], w.nbad[2], w.nbad[3]))
+    if rank == 0:
+        np.save(os.path.join(out, "output.npy"), res["params"])
+        np.save(os.path.join(out, "status.npy"), res["status"])
     return res
 
 
@@ -117,6 +162,9 @@ def main(argv=None):
                     help="run the multi-start least-squares fit before the chain (fit.fit), as `leastsq = True` in "
                          "the configuration does")
     ap.add_argument("--fit-starts", type=int, default=None, help="starts of that fit (default: nchains)")
+    ap.add_argument("--grid-bands", action="store_true",
+                    help="with walk = unif: keep the band fluxes of every model instead of its whole spectrum")
+    ap.add_argument("--grid-f32", action="store_true", help="with walk = unif: write the models as float")
     a = ap.parse_args(argv)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -131,6 +179,21 @@ def main(argv=None):
     if a.numit:
         scfg.numit = a.numit
     leastsq = a.leastsq or scfg.leastsq
+    unif = scfg.walk == "unif"
+    if unif:
+        for on, what in ((leastsq, "leastsq"), (scfg.chisqscale, "chisqscale"), (scfg.grexit, "grexit"),
+                         (a.resume, "--resume")):
+            if on:
+                ap.error("walk = unif makes a model grid, not a chain: %s does not apply" % what)
+        if not scfg.savemodel:
+            ap.error("walk = unif keeps every model: name their file with `savemodel`")
+        if a.python_loop or (world > 1 and not a.native_sharded):
+            ap.error("walk = unif runs the native way: not with --python-loop, and on several ranks only with "
+                     "--native-sharded")
+    elif a.grid_bands or a.grid_f32:
+        ap.error("--grid-bands and --grid-f32 go with walk = unif")
+    if scfg.walk == "mrw" and not a.resident:
+        ap.error("walk = mrw is served by the resident loop: add --resident")
     if scfg.chisqscale and not leastsq:
         ap.error("chisqscale = True scales the uncertainties by the least-squares optimum's chi-square: it comes with "
                  "leastsq = True (or --leastsq)")
@@ -148,6 +211,17 @@ def main(argv=None):
     if native and world > 1:
         from . import engine
         engine.comm_init()
+    if unif:
+        res = model_grid(w, scfg, a, out, rank, log)
+        if rank == 0:
+            with open(os.path.join(out, "MCMC.log"), "w") as f:
+                f.write("\n".join(lines) + "\n")
+        w.close()
+        if world > 1:
+            import torch.distributed as dist
+            dist.barrier()
+            dist.destroy_process_group()
+        return res
     if a.resident and not native:
         ap.error("--resident runs the native way: not with --python-loop, and on several ranks only with --native-sharded")
     if a.resume and not a.resident:

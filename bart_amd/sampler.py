@@ -54,6 +54,8 @@ class SamplerConfig:
     grexit: bool = False
     grcheck: int | None = None
     grthreshold: float = 1.01
+    # read by run_grid alone (`walk = unif`; MC3's key of the same name): iterations per chunk and per model file
+    modelper: int = 0
 
     @classmethod
     def from_cfg(cls, path: str, section: str = "MCMC") -> "SamplerConfig":
@@ -62,8 +64,11 @@ class SamplerConfig:
         cp.read([path])
         d = dict(cp.items(section))
         arr = lambda k: np.array([float(x) for x in d[k].split()])
+        # a model grid (`walk = unif`) has no data: the reference fills the two keys with dummies, here they go unread
+        none = np.zeros(0) if d.get("walk", "demc") == "unif" else None
+        obs = lambda k: arr(k) if none is None or k in d else none
         return cls(params=arr("params"), pmin=arr("pmin"), pmax=arr("pmax"),
-                   stepsize=arr("stepsize"), data=arr("data"), uncert=arr("uncert"),
+                   stepsize=arr("stepsize"), data=obs("data"), uncert=obs("uncert"),
                    nchains=int(d.get("nchains", 10)), numit=int(float(d.get("numit", 10000))),
                    burnin=int(d.get("burnin", 500)), walk=d.get("walk", "demc"),
                    grtest=d.get("grtest", "True").strip() == "True",
@@ -76,7 +81,8 @@ class SamplerConfig:
                    chisqscale=d.get("chisqscale", "False").strip() == "True",
                    grexit=d.get("grexit", "False").strip() == "True",
                    grcheck=int(d["grcheck"]) if "grcheck" in d else None,
-                   grthreshold=float(d.get("grthreshold", 1.01)))
+                   grthreshold=float(d.get("grthreshold", 1.01)),
+                   modelper=int(float(d.get("modelper", 0))))
 
 
 def gelman_rubin(chains: np.ndarray) -> np.ndarray:
@@ -122,6 +128,13 @@ def _check_stepsize(stepsize):
                          "run_resident and fit.fit alone: here give every parameter its own stepsize, or 0 to fix it")
 
 
+def _check_walk(walk, who: str):
+    """run and run_native serve DEMC and snooker.  MC3's other two walks are not DEMC under another name."""
+    if walk in ("mrw", "unif"):
+        raise ValueError("%s: walk = %s is not served by this loop (it would run DEMC in its place): "
+                         "run_resident serves mrw (retrieve --resident), run_grid serves unif" % (who, walk))
+
+
 def problem_arrays(cfg, who: str):
     """The retrieval problem of ``cfg`` as the library takes it: contiguous double arrays ``params, pmin, pmax,
     stepsize, data, uncert`` and ``[prior, priorlow, priorup]`` (or None where ``cfg`` has no priors)."""
@@ -164,6 +177,7 @@ def run(model, cfg: SamplerConfig, log=None):
     """model(params[nchains, npars]) -> bandflux[nchains, ndata] (-1 rows = rejected).
     Returns dict(chain [nchains, nsteps, npars], chisq [nchains, nsteps], bestp,
     best_chisq, accept_rate, grstat)."""
+    _check_walk(cfg.walk, "run")
     rng = np.random.default_rng(cfg.seed)
     _check_stepsize(cfg.stepsize)
     _grexit_ignored(cfg, log, "run")
@@ -279,6 +293,7 @@ def run_native(worker, cfg: SamplerConfig, log=None):
     chains.  Needs an unsharded engine or, on a sharded one, the library's
     communicator (engine.comm_init): every rank then runs this same seeded loop
     in lockstep and gets the same chains.  Same result dictionary as :func:`run`."""
+    _check_walk(cfg.walk, "run_native")
     from . import transit_module as trm
     need_whole_grid_or_comm(worker, "run_native")
     nch = cfg.nchains
@@ -311,10 +326,12 @@ class McmcOpts(C.Structure):
                 ("progress", C.c_void_p), ("progress_user", C.c_void_p),
                 ("burnin", C.c_long), ("grcheck", C.c_long), ("grthreshold", C.c_double), ("grexit", C.c_int),
                 ("grstat", C.c_void_p), ("grwhen", C.c_void_p), ("ngr", C.c_int), ("ngr_out", C.c_void_p),
-                ("first", C.c_long), ("start", C.c_void_p), ("done", C.c_void_p)]
+                ("first", C.c_long), ("start", C.c_void_p), ("done", C.c_void_p),
+                ("walk", C.c_int)]
 
 
 PROGRESS = C.CFUNCTYPE(None, C.c_long, C.c_long, C.c_void_p)
+WALK_MRW = 2    # bartrt_mcmc_opts.walk (include/bartrt.h: BARTRT_WALK_MRW)
 
 
 def draws(seed: int, t: int, nchains: int, npars: int) -> np.ndarray:
@@ -332,7 +349,8 @@ def run_resident(worker, cfg: SamplerConfig, log=None, block: int = 256, first: 
     population, chi-squares and counters stay in device memory and an iteration is one small sampler launch plus the
     model's launches, enqueued without a host wait, ``block`` iterations at a time.  Its draws come from a
     counter-based generator keyed by ``cfg.seed``: a run can be restated draw for draw (tests/mcmc_restate.py); the
-    stream is not :func:`run_native`'s.  Of the three loops only this one takes shared parameters (``stepsize = -k``:
+    stream is not :func:`run_native`'s.  ``cfg.walk``: ``demc``, ``snooker`` or ``mrw`` (Metropolis random walk: every
+    free parameter moves by its stepsize times a normal, no partner chains; only this loop serves it).  Of the three loops only this one takes shared parameters (``stepsize = -k``:
     a copy of parameter k, counted from 1), Gaussian priors (``prior``, ``priorlow``, ``priorup``; ``chisq`` then
     holds the data term plus the prior terms), ``thinning`` and the per-sample band fluxes of ``savemodel``.  At most
     1024 chains and 64 parameters.  Sharded engines as :func:`run_native`: with the library's communicator every rank
@@ -360,6 +378,8 @@ def run_resident(worker, cfg: SamplerConfig, log=None, block: int = 256, first: 
     iteration counts, psrf [ntests, npars]); ``converged``: whether the last test made found convergence; ``accepted``: the proposals accepted in those
     iterations."""
     from . import transit_module as trm
+    if cfg.walk == "unif":
+        raise ValueError("run_resident: walk = unif is not a chain: run_grid makes model grids")
     need_whole_grid_or_comm(worker, "run_resident")
     nch = cfg.nchains
     total = max(1, int(np.ceil(cfg.numit / nch)))
@@ -380,7 +400,7 @@ def run_resident(worker, cfg: SamplerConfig, log=None, block: int = 256, first: 
         grcheck = int(cfg.grcheck) if cfg.grcheck else max(1, -(-nsteps // (10 * block))) * block
     opts = McmcOpts(size=C.sizeof(McmcOpts), snooker=int(cfg.walk == "snooker"), seed=cfg.seed, thin=thin, block=block,
                     burnin=int(cfg.burnin), grcheck=grcheck, grthreshold=float(cfg.grthreshold),
-                    grexit=int(bool(cfg.grexit)), first=first)
+                    grexit=int(bool(cfg.grexit)), first=first, walk=WALK_MRW if cfg.walk == "mrw" else 0)
     if pri is not None:
         opts.prior, opts.priorlow, opts.priorup = (v.ctypes.data for v in pri)
     if start is not None:
@@ -426,3 +446,116 @@ def run_resident(worker, cfg: SamplerConfig, log=None, block: int = 256, first: 
     return _result(chain, chis, nacc.value, done.value, nch, cfg, thin, burnin=max(0, cfg.burnin - first),
                    models=models, done=done.value, grhistory=(when, psrf), converged=converged,
                    accepted=nacc.value)
+
+
+class GridOpts(C.Structure):
+    """``bartrt_grid_opts`` of include/bartrt.h."""
+    _fields_ = [("size", C.c_ulong), ("seed", C.c_ulonglong), ("chunk", C.c_long), ("first", C.c_long),
+                ("spectra", C.c_int), ("f32", C.c_int), ("sink", C.c_void_p), ("user", C.c_void_p)]
+
+
+SINK = C.CFUNCTYPE(C.c_int, C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+
+
+def grid_draws(seed: int, t: int, nrows: int, params, pmin, pmax, stepsize) -> np.ndarray:
+    """The samples of iteration ``t`` of a model grid, rows 0 .. nrows - 1, evaluated on the device
+    (``bartrt_grid_draws``; csrc/grid_core.hpp): [nrows, npars].  Needs no engine."""
+    from . import transit_module as trm
+    par, lo, hi, step = (np.ascontiguousarray(v, np.double) for v in (params, pmin, pmax, stepsize))
+    if any(v.shape != par.shape for v in (lo, hi, step)):
+        raise ValueError("grid_draws: pmin, pmax and stepsize have one value per parameter")
+    out = np.zeros((nrows, len(par)))
+    ptr = lambda v: v.ctypes.data_as(C.c_void_p)
+    trm.check(trm.lib().bartrt_grid_draws(C.c_ulonglong(seed), C.c_ulonglong(t), nrows, len(par), ptr(par), ptr(lo),
+                                          ptr(hi), ptr(step), ptr(out)))
+    return out
+
+
+def run_grid(worker, cfg: SamplerConfig, sink=None, spectra=True, f32=False, first=0, chunk=None):
+    """A model grid (MC3's ``walk = unif``) through ``bartrt_grid_run`` (csrc/grid.hip, csrc/grid_core.hpp):
+    niter = ceil(numit / nchains) iterations of ``cfg.nchains`` parameter vectors drawn uniformly in
+    [``cfg.pmin``, ``cfg.pmax``] (fixed and shared parameters as in :func:`run_resident`), each evaluated by the batched
+    model and kept with its WHOLE model row: the spectrum on the engine's grid (``spectra``, the default, what the
+    reference's model files hold) or the band fluxes, as double or (``f32``) float.  A row the model rejects is -1 in
+    every entry and carries its status (1 temperature, 2 abundance, 3 energy).  ``cfg.data`` / ``cfg.uncert`` are not
+    read.  The draws are the counter-based generator's, keyed by ``cfg.seed``: sample (t, row) depends on nothing
+    else, so ``first`` (with ``cfg.numit`` still the whole grid's) makes the iterations first .. niter - 1 alone, the
+    bytes they have in the whole grid.
+
+    The run goes in chunks of ``chunk`` iterations (default ``cfg.modelper``), two in flight on the device.  With a
+    callable ``sink(k, t0, params, status, models)`` every chunk is forwarded as numpy VIEWS, valid during the call
+    only -- params [n, nchains, npars], status [n, nchains], models [n, nchains, width], the iteration first, t0 the
+    chunk's first global iteration; ``modelper = 0`` then means one chunk holding the whole run -- and the function
+    returns ``{"nbad": [3], "models": count}``.  Returning a true value from the sink stops the run
+    (``"stopped": True``); an exception raised in it stops the run and is raised again here.  With ``sink=None``
+    everything is collected (in chunks of at most 256 iterations where ``modelper`` is 0) and returned as ``{"params":
+    [nchains, niter, npars], "status": [nchains, niter], "models": [nchains, niter, width], "nbad": [3]}``.
+
+    Sharded engines as :func:`run_native`: with the library's communicator every rank makes this call in lockstep and
+    every rank receives the same whole rows.
+
+    Speed as measured (MEASUREMENTS.md row 22; one MI355X, headline grid of 100 layers x 1e4 wavenumbers, chunks of
+    16 iterations, a sink that discards; in brackets the ratio to a bare loop of ``bartrt_step_batch_dev`` on the same
+    row count, which draws, packs and hands over nothing).  Whole spectra as double: 61 254 models/s at 10 rows
+    (0.71), 101 006 at 64 (0.70), 113 448 at 256 (0.705).  As float: 64 921 (0.75), 116 261 (0.80), 129 317 (0.80).
+    Band fluxes: 69 974 (0.81), 134 437 (0.93), 152 424 (0.95).  The chunk copies run on the engine's one stream
+    behind the kernels; a second stream for them is the follow-up that row names."""
+    from . import transit_module as trm
+    need_whole_grid_or_comm(worker, "run_grid")
+    nch = int(cfg.nchains)
+    total = max(1, int(np.ceil(cfg.numit / nch)))
+    first = int(first)
+    niter = total - first
+    if niter < 1 or first < 0:
+        raise ValueError("run_grid: first = %d leaves none of the grid's %d iterations" % (first, total))
+    par, pmin, pmax, step = (np.ascontiguousarray(v, np.double) for v in (cfg.params, cfg.pmin, cfg.pmax, cfg.stepsize))
+    if any(v.shape != par.shape for v in (pmin, pmax, step)):
+        raise ValueError("run_grid: pmin, pmax and stepsize have one value per parameter")
+    npars = len(par)
+    width = int(worker.nwave if spectra else worker.nfilters)
+    if chunk is None:
+        chunk = max(0, int(cfg.modelper))
+        if sink is None and chunk == 0:
+            chunk = min(niter, 256)
+    dtype = np.float32 if f32 else np.double
+    kept, failure = [], []
+    state = {"models": 0, "stopped": False}
+
+    def view(addr, shape, dt):
+        n = int(np.prod(shape))
+        return np.frombuffer((C.c_char * (n * np.dtype(dt).itemsize)).from_address(addr), dtype=dt).reshape(shape)
+
+    def forward(k, t0, n, p_par, p_st, p_rows, _):
+        try:
+            a = (view(p_par, (n, nch, npars), np.double), view(p_st, (n, nch), np.int32),
+                 view(p_rows, (n, nch, width), dtype))
+            state["models"] += n * nch
+            if sink is None:
+                kept.append(tuple(v.copy() for v in a))
+                return 0
+            if sink(k, t0, *a):
+                state["stopped"] = True
+                return 1
+            return 0
+        except BaseException as err:          # (no exception crosses the C frames: kept, and raised after the call)
+            failure.append(err)
+            return 1
+
+    cb = SINK(forward)
+    opts = GridOpts(size=C.sizeof(GridOpts), seed=cfg.seed, chunk=chunk, first=first, spectra=int(bool(spectra)),
+                    f32=int(bool(f32)), sink=C.cast(cb, C.c_void_p))
+    nbad = (C.c_long * 4)()
+    ptr = lambda v: v.ctypes.data_as(C.c_void_p)
+    rc = trm.lib().bartrt_grid_run(nch, npars, C.c_long(niter), ptr(par), ptr(pmin), ptr(pmax), ptr(step),
+                                   C.cast(C.byref(opts), C.c_void_p), C.cast(nbad, C.c_void_p))
+    if failure:
+        raise failure[0]
+    if not state["stopped"]:
+        trm.check(rc)
+    for k in (1, 2, 3):
+        worker.nbad[k] += int(nbad[k])
+    counts = [int(nbad[k]) for k in (1, 2, 3)]
+    if sink is not None:
+        return {"nbad": counts, "models": state["models"], "stopped": state["stopped"]}
+    cat = lambda j: np.ascontiguousarray(np.concatenate([c[j] for c in kept], axis=0).swapaxes(0, 1))
+    return {"params": cat(0), "status": cat(1), "models": cat(2), "nbad": counts}

@@ -322,7 +322,15 @@ int bartrt_mcmc_run(int nchains, int npars, long nsteps, const double *params, c
  * every tenth iteration, the thinning rule -- uses the global value.  The chains' chi-squares and band fluxes are
  * rebuilt by one model call on the rows of start (a row the model rejects: chisq inf).  A run of N iterations, and a
  * run of N1 followed by a resumed run of N - N1, write the same bytes.  The tests of a resumed call see that call's
- * rows alone (t >= max(burnin, t0)): they know nothing of the run before. */
+ * rows alone (t >= max(burnin, t0)): they know nothing of the run before.
+ *
+ * WALKS.  walk = 0: demc or snooker, as `snooker` says.  walk = BARTRT_WALK_MRW (2; MC3's `walk = mrw`): Metropolis
+ * random walk -- every free parameter of a proposal moves by stepsize_j times the jitter normal of the draw table,
+ * no partner chain is drawn, no rule of the move reads the iteration, and one chain is enough.  Box, shared
+ * parameters, priors, thinning, models, the convergence tests and resume are as above.  walk = BARTRT_WALK_UNIF (3;
+ * MC3's `walk = unif`) is not a chain: BARTRT_EINVAL here, bartrt_grid_run serves it.  Any other value:
+ * BARTRT_EINVAL. */
+enum { BARTRT_WALK_MRW = 2, BARTRT_WALK_UNIF = 3 };
 typedef struct bartrt_mcmc_opts {
   unsigned long size;                 /* sizeof(bartrt_mcmc_opts) of the caller */
   int snooker;                        /* 0: demc, 1: snooker */
@@ -343,6 +351,7 @@ typedef struct bartrt_mcmc_opts {
   long first;                         /* resume: the global iteration this call starts at */
   const double *start;                /* resume: [nchains][npars] */
   long *done;                         /* iterations of this call the result holds, may be NULL */
+  int walk;                           /* 0: as `snooker` says; 2: mrw (BARTRT_WALK_MRW) */
 } bartrt_mcmc_opts;
 int bartrt_mcmc_run_resident(int nchains, int npars, long nsteps, const double *params, const double *pmin,
                              const double *pmax, const double *stepsize, int ndata, const double *data,
@@ -361,6 +370,50 @@ int bartrt_mcmc_draws(unsigned long long seed, unsigned long long t, int nchains
  * most 64 parameters.  Needs no engine. */
 int bartrt_mcmc_gr(const double *chain, int nchains, long nkept, int npars, const double *stepsize, long r0, long r1,
                    double threshold, double *psrf, double *triples, int *converged);
+/* MODEL GRIDS (MC3's `walk = unif`, the reference's way to the training sets of surrogate models,
+ * code/makecfg.py:177-190): nsteps iterations of nrows parameter vectors drawn uniformly in [pmin, pmax], each
+ * evaluated by the batched model and handed to the caller WITH ITS WHOLE MODEL ROW.  No data, no chi-square, no
+ * acceptance.  Sample (t, i) -- global iteration t = first + 0 .. first + nsteps - 1, row i -- has free parameter j
+ * at pmin_j + u_j (pmax_j - pmin_j), u_j the uniform of the sampler's jitter slot of parameter j
+ * (bart_amd/csrc/grid_core.hpp; mcmc_core.hpp has the table), held to the box; fixed parameters (stepsize 0) keep
+ * params[j], shared ones (stepsize -k) copy parameter k - 1.  A sample depends on (seed, t, i) and the box alone:
+ * `first` makes any stretch of a grid again, bit for bit.
+ * An iteration is three things on the engine's stream, enqueued without a host wait: the draw, the step, and a pack
+ * of the model rows into the chunk's slot -- as float with f32, and -1 IN EVERY ENTRY of a row the model rejects
+ * (status 1 temperature, 2 abundance, 3 energy balance).  Every `chunk` iterations (0: the whole run in one chunk) the
+ * slot is copied to pinned host memory; the host enqueues chunk k + 1, then waits for chunk k and calls
+ *     sink(k, t0, niter, params[niter][nrows][npars], status[niter][nrows], rows[niter][nrows][width], user)
+ * ON THE CALLING THREAD, once per chunk, k ascending, t0 the chunk's first GLOBAL iteration, width = nfilters
+ * (spectra = 0) or the whole grid's sample count (spectra = 1), rows double or (f32) float.  THE BUFFERS ARE VALID
+ * DURING THE CALL ONLY.  A non-zero return stops the run: the chunk in flight runs out and is not handed over, and the
+ * call returns that value (bartrt_last_error names it; a sink that wants to tell its stop from the library's errors
+ * returns a positive value).  nbad (may be NULL): nbad[1..3] rows rejected with status 1, 2, 3 in the chunks handed
+ * over.  A chunk costs two device and two pinned host slots of chunk * nrows * (npars * 8 + 4 + width * 4 or 8)
+ * bytes each; one that cannot be allocated is BARTRT_EINVAL naming the bytes.
+ * BARTRT_EINVAL: nrows outside 1 .. 65535, npars outside 1 .. 64, nsteps < 1, chunk < 0, first < 0, pmin_j > pmax_j on
+ * a free parameter, a bad shared parameter, no sink, spectra = 0 without filters, the carry-over of
+ * bartrt_step_set_carry switched on.  Sharded engines: WITHOUT a communicator refused (BARTRT_EIO, the step's rule: no
+ * rank holds a whole row).  WITH one (bartrt_comm_init) every rank makes the call in LOCKSTEP with the same arguments;
+ * in `spectra` mode the step's all-gather leaves the whole spectra on every rank, so EVERY RANK'S sink receives the
+ * same whole rows [width = the whole grid], bit for bit -- a caller that writes files lets one rank write.  Line-by-line
+ * engines with a communicator and chain-service clients: BARTRT_ENOTSUP. */
+typedef struct bartrt_grid_opts {
+  unsigned long size;                 /* sizeof(bartrt_grid_opts) of the caller */
+  unsigned long long seed;
+  long chunk;                         /* iterations per chunk; 0: the whole run */
+  long first;                         /* global iteration of this call's first one */
+  int spectra;                        /* 0: band fluxes, width = nfilters; 1: whole spectra, width = nwave */
+  int f32;                            /* model rows as float */
+  int (*sink)(long k, long t0, long niter, const double *params /*[niter][nrows][npars]*/,
+              const int *status /*[niter][nrows]*/, const void *rows /*[niter][nrows][width]*/, void *user);
+  void *user;
+} bartrt_grid_opts;
+int bartrt_grid_run(int nrows, int npars, long nsteps, const double *params, const double *pmin,
+                    const double *pmax, const double *stepsize, const bartrt_grid_opts *opts, long *nbad);
+/* Diagnostics: the samples of iteration t, rows 0 .. nrows - 1, evaluated ON THE DEVICE by the grid's own kernel:
+ * out[nrows][npars].  Needs no engine. */
+int bartrt_grid_draws(unsigned long long seed, unsigned long long t, int nrows, int npars, const double *params,
+                      const double *pmin, const double *pmax, const double *stepsize, double *out);
 /* Least-squares fit before the chain (MC3's `leastsq`): nstarts independent Levenberg-Marquardt fits inside the box
  * [pmin, pmax], advanced together on the GPU.  An iteration is two batched model launches -- the nstarts * nfree
  * forward-difference rows of the Jacobians (h_j = fdstep * stepsize_j, the sign flipped at the upper bound), then the
