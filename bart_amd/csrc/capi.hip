@@ -997,6 +997,21 @@ int bartrt_mcmc_run(int nchains, int npars, long nsteps, const double *params, c
   });
 }
 
+// the options of the two resident calls (the priors of the single call travel in its problem)
+static McmcOpts mcmc_opts_of(const bartrt_mcmc_opts &o) {
+  McmcOpts m;
+  m.snooker = o.snooker;
+  m.seed = o.seed;
+  m.thin = o.thin ? o.thin : 1;
+  m.block = o.block ? o.block : 256;
+  m.progress = o.progress; m.progress_user = o.progress_user;
+  m.burnin = o.burnin; m.grcheck = o.grcheck; m.grthreshold = o.grthreshold; m.grexit = o.grexit;
+  m.grstat = o.grstat; m.grwhen = o.grwhen; m.ngr = o.ngr; m.ngr_out = o.ngr_out;
+  m.first = o.first; m.start = o.start; m.done = o.done;
+  m.walk = o.walk;
+  return m;
+}
+
 int bartrt_mcmc_run_resident(int nchains, int npars, long nsteps, const double *params, const double *pmin,
                              const double *pmax, const double *stepsize, int ndata, const double *data,
                              const double *uncert, const bartrt_mcmc_opts *opts, double *chain, double *chisq,
@@ -1007,19 +1022,43 @@ int bartrt_mcmc_run_resident(int nchains, int npars, long nsteps, const double *
   if (!stated(p) || !params || !chain || !chisq) return null_buffer("mcmc_run_resident");
   bartrt_mcmc_opts o;
   if (!sized_copy(opts, &o)) return fail(BARTRT_EINVAL, "mcmc_run_resident: set opts->size");
-  McmcOpts m;
-  m.snooker = o.snooker;
-  m.seed = o.seed;
-  m.thin = o.thin ? o.thin : 1;
-  m.block = o.block ? o.block : 256;
   p.prior = o.prior; p.priorlow = o.priorlow; p.priorup = o.priorup;
-  m.progress = o.progress; m.progress_user = o.progress_user;
-  m.burnin = o.burnin; m.grcheck = o.grcheck; m.grthreshold = o.grthreshold; m.grexit = o.grexit;
-  m.grstat = o.grstat; m.grwhen = o.grwhen; m.ngr = o.ngr; m.ngr_out = o.ngr_out;
-  m.first = o.first; m.start = o.start; m.done = o.done;
-  m.walk = o.walk;
+  const McmcOpts m = mcmc_opts_of(o);
   return guarded([&] {
     mcmc_run_resident(*g_eng, p, nchains, nsteps, params, m, chain, chisq, models, naccept, nbad);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_mcmc_run_resident_groups(int ngroups, const bartrt_mcmc_group *groups, int nchains, int npars, long nsteps,
+                                    int ndata, const bartrt_mcmc_opts *opts, double *chain, double *chisq,
+                                    double *models, long *naccept, long *nbad, int *converged_at) {
+  NEED_ENGINE();
+  const std::string who = "mcmc_run_resident_groups";
+  if (!g_eng->step) return fail(BARTRT_EINVAL, who + ": call bartrt_step_setup first");
+  if (ngroups < 1) return fail(BARTRT_EINVAL, who + ": ngroups = " + std::to_string(ngroups) + ": at least one group");
+  if (!groups || !chain || !chisq) return null_buffer(who.c_str());
+  bartrt_mcmc_opts o;
+  if (!sized_copy(opts, &o)) return fail(BARTRT_EINVAL, who + ": set opts->size");
+  if (o.seed || o.prior || o.priorlow || o.priorup || o.start)
+    return fail(BARTRT_EINVAL, who + ": opts->seed, prior, priorlow, priorup and start are not read here: every group "
+                                     "carries its own (bartrt_mcmc_group)");
+  // the array's stride is the caller's sizeof(bartrt_mcmc_group): every element says the same
+  const unsigned long stride = groups[0].size;
+  std::vector<McmcGroup> gs((size_t)ngroups);
+  for (int g = 0; g < ngroups; g++) {
+    const auto *at = reinterpret_cast<const bartrt_mcmc_group *>(reinterpret_cast<const char *>(groups) + (size_t)g * stride);
+    bartrt_mcmc_group c;
+    if (stride < sizeof(c.size) || at->size != stride || !sized_copy(at, &c))
+      return fail(BARTRT_EINVAL, who + ": group " + std::to_string(g) + ": set size = sizeof(bartrt_mcmc_group) in every group");
+    gs[g].p = RetrievalProblem{npars, ndata, 0, c.pmin, c.pmax, c.stepsize, c.data, c.uncert, c.prior, c.priorlow, c.priorup};
+    gs[g].params = c.params; gs[g].seed = c.seed; gs[g].start = c.start;
+    if (!stated(gs[g].p) || (!c.params && !c.start)) return null_buffer((who + ": group " + std::to_string(g)).c_str());
+  }
+  const McmcOpts m = mcmc_opts_of(o);
+  return guarded([&] {
+    mcmc_run_resident_groups(*g_eng, ngroups, gs.data(), nchains, nsteps, m, chain, chisq, models, naccept, nbad,
+                             converged_at);
     return BARTRT_OK;
   });
 }

@@ -190,6 +190,21 @@ __global__ __launch_bounds__(mcmc::kMaxChains) void mcmc_advance(mcmc::State s, 
   if (propose_next && i < s.nch) mcmc::propose(s, t, i);
 }
 
+// The same launch for several independent retrievals (mcmc_core.hpp: GROUPS): workgroup g reads group g's State from
+// device memory -- a uniform address, so the wave holds it in scalar registers as it holds mcmc_advance's argument --
+// and lane i is chain i of that group.  No lane reads or writes a row of another group.  snap: [ngroups][nch].
+__global__ __launch_bounds__(mcmc::kMaxChains) void mcmc_advance_groups(const mcmc::State *groups, long t,
+                                                                        int finish_prev, int propose_next, long *snap) {
+  const mcmc::State s = groups[blockIdx.x];
+  const int i = threadIdx.x;
+  if (finish_prev && i < s.nch) {
+    mcmc::finish(s, t - 1, i);
+    if (snap) snap[(size_t)blockIdx.x * s.nch + i] = s.counts[(size_t)i * 4];
+  }
+  __syncthreads();
+  if (propose_next && i < s.nch) mcmc::propose(s, t, i);
+}
+
 __global__ void mcmc_draws_kernel(unsigned long long seed, unsigned long long t, int nch, int npars, double *out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < nch) mcmc::draws_row(seed, t, nch, i, npars, out + (size_t)i * (mcmc::kDrawsHead + npars));
@@ -338,95 +353,119 @@ void mcmc_gr_probe(const double *chain, int nch, long nkept, int npars, const do
   *converged = (int)test.words(0)[0];
 }
 
-void mcmc_run_resident(Engine &e, const RetrievalProblem &p, int nch, long nsteps, const double *params,
-                       const McmcOpts &opts, double *chain, double *chisq, double *models, long *naccept_out,
-                       long *nbad) {
-  const int npars = p.npars, ndata = p.ndata;
-  if (!e.step) throw IoError{"mcmc_run_resident: call step_setup first"};
-  if (nch < 1 || npars < 1 || nsteps < 1) throw std::invalid_argument("mcmc_run_resident: bad sizes");
-  if (nch > mcmc::kMaxChains)
-    throw std::invalid_argument("mcmc_run_resident: at most 1024 chains (one workgroup); more stay with mcmc_run");
-  if (npars > mcmc::kMaxPars) throw std::invalid_argument("mcmc_run_resident: too many parameters (at most 64)");
-  if (opts.thin < 1 || opts.block < 1) throw std::invalid_argument("mcmc_run_resident: thin and block must be >= 1");
+namespace {
+
+// The resident loop over G groups of nch chains each (mcmc_core.hpp: GROUPS); mcmc_run_resident is its G = 1 under its
+// own name and through its own kernel (by_value: mcmc_advance on the one State; else mcmc_advance_groups on the array
+// of them).  Outputs per group: naccept [G], nbad [G][4], converged_at [G] (each may be null).
+void resident_loop(Engine &e, const std::string &who, int G, const McmcGroup *groups, int nch, long nsteps,
+                   const McmcOpts &opts, bool by_value, double *chain, double *chisq, double *models, long *naccept_out,
+                   long *nbad, int *converged_at) {
+  const int npars = groups[0].p.npars, ndata = groups[0].p.ndata;
+  if (npars < 1 || nsteps < 1) throw std::invalid_argument(who + ": bad sizes");
+  if (npars > mcmc::kMaxPars) throw std::invalid_argument(who + ": too many parameters (at most 64)");
+  if (opts.thin < 1 || opts.block < 1) throw std::invalid_argument(who + ": thin and block must be >= 1");
   if (opts.walk == mcmc::kWalkUnif)
-    throw std::invalid_argument("mcmc_run_resident: walk = 3 (unif) is not a chain: bartrt_grid_run makes model grids");
+    throw std::invalid_argument(who + ": walk = 3 (unif) is not a chain: bartrt_grid_run makes model grids");
   if (opts.walk != 0 && opts.walk != mcmc::kWalkMrw)
-    throw std::invalid_argument("mcmc_run_resident: walk = " + std::to_string(opts.walk) +
+    throw std::invalid_argument(who + ": walk = " + std::to_string(opts.walk) +
                                 " is not one of 0 (demc / snooker) and 2 (mrw)");
   const long first = opts.first, B = opts.block;
-  if (first < 0 || (first > 0) != (opts.start != nullptr))
-    throw std::invalid_argument("mcmc_run_resident: first > 0 and start come together (a resumed run), or neither");
+  for (int g = 0; g < G; g++)
+    if (first < 0 || (first > 0) != (groups[g].start != nullptr))
+      throw std::invalid_argument(who + ": first > 0 and start come together (a resumed run), or neither");
   if (first % opts.thin != 0)
-    throw std::invalid_argument("mcmc_run_resident: first = " + std::to_string(first) + " is not a multiple of thin = " +
+    throw std::invalid_argument(who + ": first = " + std::to_string(first) + " is not a multiple of thin = " +
                                 std::to_string(opts.thin) + ": a run resumes on a kept row");
   if (opts.grcheck < 0 || opts.burnin < 0 || opts.ngr < 0 || opts.grthreshold < 0)
-    throw std::invalid_argument("mcmc_run_resident: burnin, grcheck, grthreshold and ngr must be >= 0");
+    throw std::invalid_argument(who + ": burnin, grcheck, grthreshold and ngr must be >= 0");
   if (opts.grcheck > 0 && (opts.grcheck % B != 0 || B % opts.thin != 0))
-    throw std::invalid_argument("mcmc_run_resident: grcheck = " + std::to_string(opts.grcheck) +
+    throw std::invalid_argument(who + ": grcheck = " + std::to_string(opts.grcheck) +
                                 " must be a multiple of block = " + std::to_string(B) + ", and block of thin = " +
                                 std::to_string(opts.thin) + ": every test falls on a block end that is a kept row");
-  const Objective objective = check_retrieval("mcmc_run_resident", &e, p);
+  std::vector<Objective> objective;
+  if (by_value) objective.push_back(check_retrieval(who, &e, groups[0].p));
+  else {
+    std::vector<Objective> stated;
+    for (int g = 0; g < G; g++) stated.push_back(groups[g].p);
+    objective = check_groups(who, G, nch, stated.data(),
+                             [&](const std::string &name, const Objective &p) { return check_retrieval(name, &e, p); });
+  }
 
   const long nkept = mcmc::kept_rows(nsteps, opts.thin);
-  const size_t np = npars, nd = ndata, n = nch;
+  const size_t np = npars, nd = ndata, n = nch, N = (size_t)G * n;   // n: a group's chains, N: the rows of a launch
   // the start, on the host through step_run_host as mcmc_run makes it, then uploaded once
-  std::vector<double> x(n * np), c(n), cur(n * nd);
-  std::vector<int> status(n);
-  long total[4] = {0, 0, 0, 0};   // accepted proposals, models rejected with status 1, 2, 3
+  std::vector<double> x(N * np), c(N), cur(N * nd);
+  std::vector<int> status(N);
+  std::vector<long> total(4 * (size_t)G, 0);   // per group: accepted proposals, models rejected with status 1, 2, 3
   mcmc::State h{};
-  static_cast<Objective &>(h) = objective;
-  h.nch = nch; h.snooker = opts.snooker; h.seed = opts.seed; h.nsteps = nsteps; h.thin = opts.thin;
+  h.nch = nch; h.snooker = opts.snooker; h.nsteps = nsteps; h.thin = opts.thin;
   h.first = first;
   h.walk = opts.walk;
   h.x = x.data(); h.c = c.data(); h.cur = cur.data();
+  std::vector<mcmc::State> hs;
+  for (int g = 0; g < G; g++) hs.push_back(mcmc::group_state(h, g, objective[g], groups[g].seed));
   auto model = [&](const double *rows, int m, double *band, int *st) { step_run_host(e, rows, m, npars, band, st); };
-  if (opts.start) {
+  if (first > 0) {
     // a resumed run: the population is the last rows of the run before; c and cur come back from one model call on
-    // them, as start_population evaluates a round (the same bits: the model and chisq_of are the loop's own).  No
-    // draw is made and nothing is counted: the run before counted these models when it proposed them.
-    std::copy(opts.start, opts.start + n * np, x.begin());
-    model(h.x, nch, h.cur, status.data());
-    for (size_t i = 0; i < n; i++)
-      c[i] = status[i] == 0 ? mcmc::chisq_of(h, h.cur + i * nd, h.x + i * np) : INFINITY;
-  } else if (!mcmc::start_population(h, params, model, status.data(), total))
-    throw IoError{"mcmc_run_resident: no chain starts on a physical model: check params/pmin/pmax"};
+    // them, as start_groups evaluates a round (the same bits: the model and chisq_of are the loop's own).  No draw is
+    // made and nothing is counted: the run before counted these models when it proposed them.
+    for (int g = 0; g < G; g++) std::copy(groups[g].start, groups[g].start + n * np, hs[g].x);
+    model(h.x, (int)N, h.cur, status.data());
+    for (int g = 0; g < G; g++)
+      for (size_t i = 0; i < n; i++)
+        hs[g].c[i] = status[g * n + i] == 0 ? mcmc::chisq_of(hs[g], hs[g].cur + i * nd, hs[g].x + i * np) : INFINITY;
+  } else {
+    std::vector<const double *> params;
+    for (int g = 0; g < G; g++) params.push_back(groups[g].params);
+    std::vector<char> ok(G);
+    mcmc::start_groups(hs.data(), G, params.data(), model, status.data(), total.data(), ok.data());
+    for (int g = 0; g < G; g++)
+      if (!ok[g])
+        throw IoError{who + (by_value ? "" : ": group " + std::to_string(g)) +
+                      ": no chain starts on a physical model: check params/pmin/pmax"};
+  }
 
-  const DeviceObjective consts(objective);
+  std::vector<std::unique_ptr<DeviceObjective>> consts;
+  for (int g = 0; g < G; g++) consts.emplace_back(new DeviceObjective(objective[g]));
   DevBuf<double> d_pop, d_out;
   DevBuf<int> d_int;
   DevBuf<long> d_counts;
   // population: x c cur logjac prop band
-  d_pop.reserve(n * np + n + n * nd + n + n * np + n * nd);
-  d_int.reserve(2 * n);
-  d_counts.reserve(4 * n);
-  d_out.reserve((size_t)nch * nkept * (np + 1 + (models ? nd : 0)));
+  d_pop.reserve(N * np + N + N * nd + N + N * np + N * nd);
+  d_int.reserve(2 * N);
+  d_counts.reserve(4 * N);
+  d_out.reserve(N * nkept * (np + 1 + (models ? nd : 0)));
   HIPCHK(hipMemset(d_pop, 0, sizeof(double) * d_pop.count()));
-  HIPCHK(hipMemset(d_int, 0, sizeof(int) * 2 * n));
-  HIPCHK(hipMemset(d_counts, 0, sizeof(long) * 4 * n));
-  mcmc::State d = h;
-  static_cast<Objective &>(d) = consts.d;
+  HIPCHK(hipMemset(d_int, 0, sizeof(int) * 2 * N));
+  HIPCHK(hipMemset(d_counts, 0, sizeof(long) * 4 * N));
+  mcmc::State d = h;   // the heads of the common arrays; with one group, that group's State but for its problem
   double *q = d_pop;
-  d.x = q; q += n * np;
-  d.c = q; q += n;
-  d.cur = q; q += n * nd;
-  d.logjac = q; q += n;
-  d.prop = q; q += n * np;
+  d.x = q; q += N * np;
+  d.c = q; q += N;
+  d.cur = q; q += N * nd;
+  d.logjac = q; q += N;
+  d.prop = q; q += N * np;
   double *d_band = q;
   d.band = d_band;
   d.inside = d_int;
-  int *d_status = d_int + n;
+  int *d_status = d_int + N;
   d.status = d_status;
   d.counts = d_counts;
   d.chain = d_out;
-  d.chisq = d.chain + (size_t)nch * nkept * np;
-  d.models = models ? d.chisq + (size_t)nch * nkept : nullptr;
-  HIPCHK(hipMemcpy(d.x, x.data(), sizeof(double) * n * np, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d.c, c.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d.cur, cur.data(), sizeof(double) * n * nd, hipMemcpyHostToDevice));
+  d.chisq = d.chain + N * nkept * np;
+  d.models = models ? d.chisq + N * nkept : nullptr;
+  HIPCHK(hipMemcpy(d.x, x.data(), sizeof(double) * N * np, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d.c, c.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d.cur, cur.data(), sizeof(double) * N * nd, hipMemcpyHostToDevice));
+  std::vector<mcmc::State> ds;
+  for (int g = 0; g < G; g++) ds.push_back(mcmc::group_state(d, g, consts[g]->d, groups[g].seed));
+  DevBuf<mcmc::State> d_groups;
+  if (!by_value) d_groups.upload(ds);
 
   // accept counts at the end of a block, one slot per block in flight
   PinBuf<long> snap;
-  snap.reserve(2 * n);
+  snap.reserve(2 * N);
   void *snap_dev = nullptr;
   HIPCHK(hipHostGetDevicePointer(&snap_dev, snap.get(), 0));
   Events events;
@@ -434,15 +473,20 @@ void mcmc_run_resident(Engine &e, const RetrievalProblem &p, int nch, long nstep
   const unsigned threads = (unsigned)((nch + 63) / 64 * 64);
   // t counts this call's iterations; the kernel is given the global one
   auto launch = [&](long t, long *snap_slot) {
-    hipLaunchKernelGGL(mcmc_advance, dim3(1), dim3(threads), 0, e.stream, d, first + t, (int)(t > 0),
-                       (int)(t < nsteps), snap_slot);
+    if (by_value)
+      hipLaunchKernelGGL(mcmc_advance, dim3(1), dim3(threads), 0, e.stream, ds[0], first + t, (int)(t > 0),
+                         (int)(t < nsteps), snap_slot);
+    else
+      hipLaunchKernelGGL(mcmc_advance_groups, dim3((unsigned)G), dim3(threads), 0, e.stream, d_groups.get(), first + t,
+                         (int)(t > 0), (int)(t < nsteps), snap_slot);
     HIPCHK(hipGetLastError());
-    if (t < nsteps) step_run_dev(e, d.prop, nch, npars, d_band, d_status, nullptr, e.stream, nullptr);
+    if (t < nsteps) step_run_dev(e, d.prop, (int)N, npars, d_band, d_status, nullptr, e.stream, nullptr);
   };
   // Convergence tests: after block b, behind it on the stream, where its end T (iterations of this call) is a
   // multiple of grcheck or the last one and the rows past the burn-in are enough for a test.  The rows of this call
   // alone enter: kept row q is global iteration first + (q + 1) thin - 1, so the first one at or past burnin is
-  // (burnin - first) / thin.  One record per block in flight, read in finished(b).
+  // (burnin - first) / thin.  Every group is tested on its own slice of the chain by launches of its own (one scratch,
+  // reused in stream order); one record per group and block in flight, read in finished(b).
   const long r0 = std::max(0L, opts.burnin - first) / opts.thin;
   auto test_rows = [&](long T) {   // the end of the row range of the test after T iterations, or 0: no test there
     if (opts.grcheck == 0 || (T % opts.grcheck != 0 && T != nsteps)) return 0L;
@@ -450,28 +494,38 @@ void mcmc_run_resident(Engine &e, const RetrievalProblem &p, int nch, long nstep
     return gr::testable(nch, r0, r1) ? r1 : 0L;
   };
   std::unique_ptr<GrTest> tests;
-  if (opts.grcheck > 0 && gr::testable(nch, r0, nkept)) tests.reset(new GrTest(nch, npars, nkept - r0, 2));
+  if (opts.grcheck > 0 && gr::testable(nch, r0, nkept)) tests.reset(new GrTest(nch, npars, nkept - r0, 2 * G));
   bool tested[2] = {false, false};
   int ntests = 0;
-  long stop = -1, stop_counts[4] = {0, 0, 0, 0};   // grexit: the iterations the result holds, the counters there
+  long stop = -1;   // grexit: the iterations the result holds
+  std::vector<long> stop_counts(4 * (size_t)G, 0);   // and the groups' counters there
+  if (converged_at) std::fill(converged_at, converged_at + G, -1);
   auto finished = [&](long b) {   // block b is done: wait for it, report, read its test; true: stop here
     HIPCHK(hipEventSynchronize(events.ev[b % 2]));
     const long T = std::min((b + 1) * B, nsteps);
     if (opts.progress) {
       long acc = 0;
-      for (size_t i = 0; i < n; i++) acc += snap.get()[(size_t)(b % 2) * n + i];
+      for (size_t i = 0; i < N; i++) acc += snap.get()[(size_t)(b % 2) * N + i];
       opts.progress(T, acc, opts.progress_user);
     }
     if (!tested[b % 2]) return false;
     const int k = ntests++;
-    if (k < opts.ngr) {
-      if (opts.grstat) std::copy(tests->psrf(b % 2), tests->psrf(b % 2) + np, opts.grstat + (size_t)k * np);
-      if (opts.grwhen) opts.grwhen[k] = first + T;
+    bool all = true;
+    for (int g = 0; g < G; g++) {
+      const int slot = (int)(b % 2) * G + g;
+      if (k < opts.ngr && opts.grstat)
+        std::copy(tests->psrf(slot), tests->psrf(slot) + np, opts.grstat + ((size_t)k * G + g) * np);
+      const bool conv = tests->words(slot)[0] != 0;
+      if (conv && converged_at && converged_at[g] < 0) converged_at[g] = k;
+      all = all && conv;
     }
-    const long *w = tests->words(b % 2);
-    if (!opts.grexit || !w[0]) return false;
+    if (k < opts.ngr && opts.grwhen) opts.grwhen[k] = first + T;
+    if (!opts.grexit || !all) return false;
     stop = T;
-    std::copy(w + 1, w + 5, stop_counts);
+    for (int g = 0; g < G; g++) {
+      const long *w = tests->words((int)(b % 2) * G + g);
+      std::copy(w + 1, w + 5, stop_counts.begin() + 4 * (size_t)g);
+    }
     return true;
   };
   launch(0, nullptr);
@@ -480,11 +534,13 @@ void mcmc_run_resident(Engine &e, const RetrievalProblem &p, int nch, long nstep
     if (b >= 2 && finished(b - 2)) break;   // at most two blocks in flight
     const long last = std::min((b + 1) * B, nsteps);
     for (long t = b * B + 1; t <= last; t++)
-      launch(t, t == last ? static_cast<long *>(snap_dev) + (size_t)(b % 2) * n : nullptr);
+      launch(t, t == last ? static_cast<long *>(snap_dev) + (size_t)(b % 2) * N : nullptr);
     const long r1 = test_rows(last);
     tested[b % 2] = r1 > 0;
     if (r1 > 0)
-      tests->enqueue(d.chain, nkept, consts.d.stepsize, r0, r1, opts.grthreshold, d_counts, (int)(b % 2), e.stream);
+      for (int g = 0; g < G; g++)
+        tests->enqueue(ds[g].chain, nkept, consts[g]->d.stepsize, r0, r1, opts.grthreshold, ds[g].counts,
+                       (int)(b % 2) * G + g, e.stream);
     HIPCHK(hipEventRecord(events.ev[b % 2], e.stream));
   }
   for (long b = std::max(0L, enqueued - 2); stop < 0 && b < enqueued; b++) finished(b);
@@ -493,24 +549,53 @@ void mcmc_run_resident(Engine &e, const RetrievalProblem &p, int nch, long nstep
   // the rows of the iterations done, chain by chain: the caller's arrays past them are not written
   const long done = stop >= 0 ? stop : nsteps, kd = mcmc::kept_rows(done, opts.thin);
   auto fetch = [&](double *to, const double *from, size_t width) {
-    if (kd == nkept) HIPCHK(hipMemcpy(to, from, sizeof(double) * n * nkept * width, hipMemcpyDeviceToHost));
+    if (kd == nkept) HIPCHK(hipMemcpy(to, from, sizeof(double) * N * nkept * width, hipMemcpyDeviceToHost));
     else HIPCHK(hipMemcpy2D(to, sizeof(double) * nkept * width, from, sizeof(double) * nkept * width,
-                       sizeof(double) * kd * width, n, hipMemcpyDeviceToHost));
+                       sizeof(double) * kd * width, N, hipMemcpyDeviceToHost));
   };
   fetch(chain, d.chain, np);
   fetch(chisq, d.chisq, 1);
   if (models) fetch(models, d.models, nd);
-  if (stop >= 0)
-    for (int s = 0; s < 4; s++) total[s] += stop_counts[s];
-  else
-    add_counters(d_counts, n, total);
-  if (naccept_out) *naccept_out = total[0];
-  if (nbad) {
-    nbad[0] = 0;
-    for (int s = 1; s < 4; s++) nbad[s] = total[s];
+  for (int g = 0; g < G; g++) {
+    long *tg = total.data() + 4 * (size_t)g;
+    if (stop >= 0)
+      for (int s = 0; s < 4; s++) tg[s] += stop_counts[4 * (size_t)g + s];
+    else
+      add_counters(ds[g].counts, n, tg);
+    if (naccept_out) naccept_out[g] = tg[0];
+    if (nbad) {
+      nbad[4 * (size_t)g] = 0;
+      for (int s = 1; s < 4; s++) nbad[4 * (size_t)g + s] = tg[s];
+    }
   }
   if (opts.ngr_out) *opts.ngr_out = ntests;
   if (opts.done) *opts.done = done;
+}
+
+}  // namespace
+
+void mcmc_run_resident(Engine &e, const RetrievalProblem &p, int nch, long nsteps, const double *params,
+                       const McmcOpts &opts, double *chain, double *chisq, double *models, long *naccept_out,
+                       long *nbad) {
+  if (!e.step) throw IoError{"mcmc_run_resident: call step_setup first"};
+  if (nch < 1) throw std::invalid_argument("mcmc_run_resident: bad sizes");
+  if (nch > mcmc::kMaxChains)
+    throw std::invalid_argument("mcmc_run_resident: at most 1024 chains (one workgroup); more stay with mcmc_run");
+  const McmcGroup one{p, params, opts.seed, opts.start};
+  resident_loop(e, "mcmc_run_resident", 1, &one, nch, nsteps, opts, true, chain, chisq, models, naccept_out, nbad,
+                nullptr);
+}
+
+void mcmc_run_resident_groups(Engine &e, int ngroups, const McmcGroup *groups, int nch, long nsteps,
+                              const McmcOpts &opts, double *chain, double *chisq, double *models, long *naccept,
+                              long *nbad, int *converged_at) {
+  const std::string who = "mcmc_run_resident_groups";
+  if (!e.step) throw IoError{who + ": call step_setup first"};
+  if (ngroups < 1) throw std::invalid_argument(who + ": ngroups = " + std::to_string(ngroups) + ": at least one group");
+  for (int g = 1; g < ngroups; g++)
+    if (groups[g].p.npars != groups[0].p.npars || groups[g].p.ndata != groups[0].p.ndata)
+      throw std::invalid_argument(who + ": every group has the same npars and ndata");
+  resident_loop(e, who, ngroups, groups, nch, nsteps, opts, false, chain, chisq, models, naccept, nbad, converged_at);
 }
 
 }  // namespace bartrt

@@ -1,6 +1,6 @@
 // The sampler's arithmetic, stated once for host and device: the counter-based random draws, the DEMC, snooker and
 // Metropolis random-walk moves, shared parameters, Gaussian priors and the acceptance rule of the resident loop
-// (mcmc.hip: mcmc_advance, mcmc_run_resident).  Plain inline functions on plain pointers, no HIP call: the kernel runs them one chain per
+// (mcmc.hip: mcmc_advance, mcmc_advance_groups).  Plain inline functions on plain pointers, no HIP call: the kernel runs them one chain per
 // lane, the host runs them for the start of a run, and a host compiler alone builds them for the CPU tests
 // (tests/mcmc_core_host.cpp).
 //
@@ -299,34 +299,89 @@ MCMC_HD void finish(const State &s, long t, int i) {
     for (int f = 0; f < nd; f++) s.models[row * nd + f] = ci[f];
 }
 
+// GROUPS.  Several independent retrievals of one shape (nch chains, npars parameters, ndata data each) advance in one
+// loop over common arrays: x, prop, band, status, cur, c, logjac, inside and counts hold G nch rows, group g's from row
+// g nch on; chain, chisq and models are [G][nch][nkept]...  `all` carries the call's common fields and the heads of those
+// arrays; group g's State is its own problem and seed over its slices, and chain i of the group is row i of each: every
+// rule above runs on it as on a run of its own (draws keyed by the group's seed and the LOCAL chain index, partners
+// from the group alone).  A null array of `all` stays null.
+MCMC_HD State group_state(const State &all, int g, const Objective &o, unsigned long long seed) {
+  State s = all;
+  static_cast<Objective &>(s) = o;
+  s.seed = seed;
+  const size_t r = (size_t)g * all.nch, k = r * (size_t)kept_rows(all.nsteps, all.thin), np = o.npars, nd = o.ndata;
+#define MCMC_SLICE(field, n) if (s.field) s.field += (n)
+  MCMC_SLICE(x, r * np); MCMC_SLICE(c, r); MCMC_SLICE(cur, r * nd); MCMC_SLICE(logjac, r); MCMC_SLICE(inside, r);
+  MCMC_SLICE(counts, r * 4); MCMC_SLICE(prop, r * np); MCMC_SLICE(band, r * nd); MCMC_SLICE(status, r);
+  MCMC_SLICE(chain, k * np); MCMC_SLICE(chisq, k); MCMC_SLICE(models, k * nd);
+#undef MCMC_SLICE
+  return s;
+}
+
+// what one loop takes: every group one workgroup of at most kMaxChains lanes, and no more than kMaxChains rows in all
+MCMC_HD bool groups_fit(long ngroups, long nch) {
+  return ngroups >= 1 && nch >= 1 && nch <= kMaxChains && ngroups * nch <= kMaxChains;
+}
+
 // Host code.  The start of a run: the configured point jittered by the stepsizes, chains that start on a rejected
-// model re-drawn up to kStartRounds times, every round one model call on all chains.  model(rows [n][npars], n,
-// band [n][ndata], status [n]) is the batched model; status [nch] is scratch.  Fills x, c and cur; counts the
-// rejected models in nbad[1..3] (null: not counted).  False: no chain starts on a physical model.
+// model re-drawn up to kStartRounds times, every round ONE model call on the chains of all groups.  gs [ngroups] are
+// group_state's (slices of common arrays, gs[0] at their head), params[g] group g's configured point.
+// model(rows [n][npars], n, band [n][ndata], status [n]) is the batched model; status [ngroups nch] is scratch.  A
+// group whose chains all stand on a model is left alone in the later rounds (its rows are evaluated again with the
+// rest and not read), so it gets the start of a run of its own.  Fills x, c and cur; counts the rejected models in
+// nbad[g][1..3] (null: not counted).  ok[g] = 0: no chain of group g starts on a physical model.
 template <class Model>
-inline bool start_population(const State &s, const double *params, Model &&model, int *status, long *nbad) {
+inline void start_groups(const State *gs, int ngroups, const double *const *params, Model &&model, int *status,
+                         long *nbad, char *ok) {
+  const int nch = gs[0].nch;
+  char *active = ok;   // (during the rounds: the group still re-draws)
   auto evaluate = [&] {
-    model(s.x, s.nch, s.cur, status);
-    for (int i = 0; i < s.nch; i++) {
-      if (nbad && status[i] >= 1 && status[i] <= 3) nbad[status[i]]++;
-      s.c[i] = status[i] == 0 ? chisq_of(s, s.cur + (size_t)i * s.ndata, s.x + (size_t)i * s.npars) : INFINITY;
+    model(gs[0].x, ngroups * nch, gs[0].cur, status);
+    for (int g = 0; g < ngroups; g++) {
+      if (!active[g]) continue;
+      const State &s = gs[g];
+      const int *st = status + (size_t)g * nch;
+      for (int i = 0; i < nch; i++) {
+        if (nbad && st[i] >= 1 && st[i] <= 3) nbad[(size_t)g * 4 + st[i]]++;
+        s.c[i] = st[i] == 0 ? chisq_of(s, s.cur + (size_t)i * s.ndata, s.x + (size_t)i * s.npars) : INFINITY;
+      }
     }
   };
-  for (int i = 0; i < s.nch; i++) start_point(s, 0, i, params, s.x + (size_t)i * s.npars);
+  for (int g = 0; g < ngroups; g++) {
+    active[g] = 1;
+    for (int i = 0; i < nch; i++) start_point(gs[g], 0, i, params[g], gs[g].x + (size_t)i * gs[g].npars);
+  }
   evaluate();
   for (int round = 1; round <= kStartRounds; round++) {
     bool any_bad = false;
-    for (int i = 0; i < s.nch; i++)
-      if (!std::isfinite(s.c[i])) {
-        any_bad = true;
-        start_point(s, round, i, params, s.x + (size_t)i * s.npars);
-      }
+    for (int g = 0; g < ngroups; g++) {
+      if (!active[g]) continue;
+      const State &s = gs[g];
+      bool bad = false;
+      for (int i = 0; i < nch; i++)
+        if (!std::isfinite(s.c[i])) {
+          bad = true;
+          start_point(s, round, i, params[g], s.x + (size_t)i * s.npars);
+        }
+      active[g] = bad;
+      any_bad = any_bad || bad;
+    }
     if (!any_bad) break;
     evaluate();
   }
-  for (int i = 0; i < s.nch; i++)
-    if (std::isfinite(s.c[i])) return true;
-  return false;
+  for (int g = 0; g < ngroups; g++) {
+    ok[g] = 0;
+    for (int i = 0; i < nch; i++)
+      if (std::isfinite(gs[g].c[i])) ok[g] = 1;
+  }
+}
+
+// one run: false where no chain starts on a physical model
+template <class Model>
+inline bool start_population(const State &s, const double *params, Model &&model, int *status, long *nbad) {
+  char ok = 0;
+  start_groups(&s, 1, &params, model, status, nbad, &ok);
+  return ok != 0;
 }
 
 // Diagnostics (bartrt_mcmc_draws): every draw of chain i at iteration t among nch chains, as doubles:

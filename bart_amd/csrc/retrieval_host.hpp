@@ -8,6 +8,7 @@
 #include "../../include/bartrt.h"
 #include "comm.hpp"
 #include "engine.hpp"
+#include "retrieval_check.hpp"
 #include "step.hpp"
 
 namespace bartrt {
@@ -15,12 +16,7 @@ namespace bartrt {
 // The problem with nfree counted, or the refusal every retrieval entry point makes, `who` in front.  Without an engine
 // (e null: fit_probe) the checks that need none.
 inline Objective check_retrieval(const std::string &who, const Engine *e, RetrievalProblem p) {
-  if ((p.prior || p.priorlow || p.priorup) && !(p.prior && p.priorlow && p.priorup))
-    throw std::invalid_argument(who + ": prior, priorlow and priorup come together");
-  if (const int bad = check_stepsize(p.npars, p.stepsize, &p.nfree))
-    throw std::invalid_argument(who + ": stepsize[" + std::to_string(bad - 1) + "] = " +
-                                std::to_string(p.stepsize[bad - 1]) + " shares parameter " + std::to_string(bad - 1) +
-                                " with a parameter that is out of range or itself shared");
+  p = check_problem(who, p);   // (retrieval_check.hpp: priors and stepsizes)
   if (!e) return p;
   if (p.ndata < 1 || p.ndata != e->step->nfilters)
     throw std::invalid_argument(who + ": data length must equal the number of filters");

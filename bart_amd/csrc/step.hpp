@@ -113,6 +113,21 @@ struct McmcOpts {
 // nkept = ceil(nsteps / thin); with grexit only the rows of the iterations done are written
 void mcmc_run_resident(Engine &e, const RetrievalProblem &p, int nchains, long nsteps, const double *params,
                        const McmcOpts &opts, double *chain, double *chisq, double *models, long *naccept, long *nbad);
+// Several independent retrievals of one shape in that loop (mcmc_core.hpp: GROUPS): per iteration one
+// mcmc_advance_groups launch, workgroup g advancing group g, and one step_run_dev over the ngroups nchains rows.  A
+// group is its problem, its configured point, its seed and, in a resumed call, its start [nchains][npars]; opts.seed
+// and opts.start go unread.  chain [ngroups][nchains][nkept][npars], chisq, models likewise; naccept [ngroups],
+// nbad [ngroups][4], converged_at [ngroups] (the index of the first test that found the group converged, -1: none)
+// may be null; opts.grstat is [ngr][ngroups][npars], and grexit stops at the first test that finds every group converged.
+struct McmcGroup {
+  RetrievalProblem p;
+  const double *params;
+  unsigned long long seed;
+  const double *start;
+};
+void mcmc_run_resident_groups(Engine &e, int ngroups, const McmcGroup *groups, int nchains, long nsteps,
+                              const McmcOpts &opts, double *chain, double *chisq, double *models, long *naccept,
+                              long *nbad, int *converged_at);
 // diagnostics (bartrt_mcmc_gr): gr_core.hpp's statistic of a host chain[nchains][nkept][npars], rows [r0, r1),
 // evaluated on the device by the loop's own kernels: psrf[npars], triples[nchains][npars][3], *converged; needs no engine
 void mcmc_gr_probe(const double *chain, int nchains, long nkept, int npars, const double *stepsize, long r0, long r1,

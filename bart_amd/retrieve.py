@@ -31,6 +31,12 @@ run would have made -- ``grexit`` applies again, to the new rows alone: set ``gr
 and writes the concatenated ``output.npy``, the concatenated ``savemodel`` file and an appended ``MCMC.log``.
 ``--resident`` is also the loop that serves ``walk = mrw``; the other two refuse it.
 
+``--resident --datasets FILE`` runs an ENSEMBLE (sampler.run_resident_groups; INTEGRATION.md, "Ensembles"): FILE is an
+``.npz`` with ``data`` [G, ndata] and optionally ``uncert`` [G, ndata] (default: the configuration's) and ``seed`` [G]
+(default: the configuration's seed + g); the G retrievals advance in one resident loop and are written to
+``group_000/`` ... ``group_<G-1>/`` of the output directory, each as a run of its own writes its files.  Not with
+``--resume``, ``leastsq``, ``chisqscale`` or ``walk = unif``.
+
 ``walk = unif`` makes a MODEL GRID instead of a chain (sampler.run_grid; INTEGRATION.md, "Model grids"): parameters
 drawn uniformly in [pmin, pmax], no ``data`` / ``uncert`` needed, every model kept whole.  It writes ``output.npy``
 (the parameters, [nchains, niter, npars]), ``status.npy`` ([nchains, niter]) and the models under the name of
@@ -115,6 +121,58 @@ def model_grid(w, scfg, a, out, rank, log):
     return res
 
 
+def ensemble(w, scfg, path, out, rank, log, lines):
+    """`--resident --datasets FILE`: one retrieval per row of FILE's ``data`` in one resident loop
+    (sampler.run_resident_groups), each written to ``group_<g, three digits>/`` as a run of its own writes its files.
+    Returns the list of the groups' result dictionaries."""
+    import copy
+    with np.load(path) as f:
+        data = np.asarray(f["data"], float)
+        uncert = np.asarray(f["uncert"], float) if "uncert" in f.files else None
+        seeds = np.asarray(f["seed"]) if "seed" in f.files else None
+    if data.ndim != 2 or data.shape[1] != len(scfg.data):
+        raise ValueError("--datasets: `data` is %r; it holds one row of %d values per retrieval" % (
+            data.shape, len(scfg.data)))
+    G = len(data)
+    if uncert is not None and uncert.shape != data.shape:
+        raise ValueError("--datasets: `uncert` is %r and `data` %r" % (uncert.shape, data.shape))
+    if seeds is not None and seeds.shape != (G,):
+        raise ValueError("--datasets: `seed` holds one value per retrieval")
+    cfgs = []
+    for g in range(G):
+        cfg = copy.copy(scfg)
+        cfg.data = data[g].copy()
+        cfg.uncert = uncert[g].copy() if uncert is not None else np.asarray(scfg.uncert, float).copy()
+        cfg.seed = int(seeds[g]) if seeds is not None else int(scfg.seed) + g
+        cfgs.append(cfg)
+    t0 = time.perf_counter()
+    before = dict(w.nbad)
+    results = sampler.run_resident_groups(w, cfgs, log=log)
+    dt = time.perf_counter() - t0
+    nmodel = G * scfg.nchains * results[0]["done"]
+    log("%d models of %d groups in %.2f s (%.0f models/s)" % (nmodel, G, dt, nmodel / dt))
+    log("Bad iterations due to temperature %d, abundance %d, energy %d" % tuple(w.nbad[k] - before[k] for k in (1, 2, 3)))
+    if rank != 0:
+        return results
+    for g, (cfg, res) in enumerate(zip(cfgs, results)):
+        d = os.path.join(out, "group_%03d" % g)
+        os.makedirs(d, exist_ok=True)
+        np.save(os.path.join(d, "output.npy"), res["chain"])
+        np.savez(os.path.join(d, "state.npz"), **dict(state_of(cfg), iterations=res["done"], naccept=res["accepted"],
+                                                      nbad=np.array(res["nbad"]), best_chisq=res["best_chisq"],
+                                                      bestp=res["bestp"]))
+        with open(os.path.join(d, "bestFit.txt"), "w") as f:
+            f.write("# best-fit parameters, chisq = %.6f\n" % res["best_chisq"])
+            f.write(" ".join("%.8g" % p for p in res["bestp"]) + "\n")
+        if cfg.savemodel:
+            name = os.path.join(d, os.path.basename(cfg.savemodel))
+            np.save(name if name.endswith(".npy") else name + ".npy", np.ascontiguousarray(res["models"].transpose(0, 2, 1)))
+        with open(os.path.join(d, "MCMC.log"), "w") as f:      # the call's lines and this group's
+            mine = [l for l in lines if not l.startswith("group ") or l.startswith("group %d:" % g)]
+            f.write("\n".join(mine) + "\n")
+    return results
+
+
 STATE_KEYS = ("seed", "nchains", "thinning", "walk", "npars")     # what a resumed run must share with the run before
 
 
@@ -158,6 +216,10 @@ def main(argv=None):
                          "parameters, priors, thinning and the `savemodel` array of the configuration")
     ap.add_argument("--resume", action="store_true",
                     help="with --resident: continue the run whose output.npy and state.npz lie in the output directory")
+    ap.add_argument("--datasets", default=None, metavar="FILE",
+                    help="with --resident: an .npz with data[G][ndata] (optional uncert[G][ndata], seed[G]): G "
+                         "independent retrievals in one resident loop, written to group_000/ ... (INTEGRATION.md, "
+                         "\"Ensembles\")")
     ap.add_argument("--leastsq", action="store_true",
                     help="run the multi-start least-squares fit before the chain (fit.fit), as `leastsq = True` in "
                          "the configuration does")
@@ -180,6 +242,17 @@ def main(argv=None):
         scfg.numit = a.numit
     leastsq = a.leastsq or scfg.leastsq
     unif = scfg.walk == "unif"
+    if a.datasets:
+        if not a.resident:
+            ap.error("--datasets runs an ensemble in the resident loop: add --resident")
+        if a.resume:
+            ap.error("--datasets with --resume: an ensemble is not resumed from the command line.")
+        if scfg.chisqscale:
+            ap.error("--datasets with chisqscale: the uncertainties are not rescaled per group.")
+        if leastsq:
+            ap.error("--datasets with leastsq: the fit before the chain is not run per group.")
+        if unif:
+            ap.error("--datasets with walk = unif: a model grid has no data to vary.")
     if unif:
         for on, what in ((leastsq, "leastsq"), (scfg.chisqscale, "chisqscale"), (scfg.grexit, "grexit"),
                          (a.resume, "--resume")):
@@ -226,6 +299,16 @@ def main(argv=None):
         ap.error("--resident runs the native way: not with --python-loop, and on several ranks only with --native-sharded")
     if a.resume and not a.resident:
         ap.error("--resume continues a --resident run")
+    if a.datasets:
+        try:
+            res = ensemble(w, scfg, a.datasets, out, rank, log, lines)
+        finally:
+            w.close()
+        if world > 1:
+            import torch.distributed as dist
+            dist.barrier()
+            dist.destroy_process_group()
+        return res
     before = None
     if a.resume:
         if scfg.chisqscale:

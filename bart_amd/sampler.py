@@ -448,6 +448,127 @@ def run_resident(worker, cfg: SamplerConfig, log=None, block: int = 256, first: 
                    accepted=nacc.value)
 
 
+class McmcGroup(C.Structure):
+    """``bartrt_mcmc_group`` of include/bartrt.h."""
+    _fields_ = [("size", C.c_ulong), ("params", C.c_void_p), ("pmin", C.c_void_p), ("pmax", C.c_void_p),
+                ("stepsize", C.c_void_p), ("data", C.c_void_p), ("uncert", C.c_void_p), ("prior", C.c_void_p),
+                ("priorlow", C.c_void_p), ("priorup", C.c_void_p), ("seed", C.c_ulonglong), ("start", C.c_void_p)]
+
+
+# what the groups of one call share (the other keys of a SamplerConfig are each group's own)
+GROUP_COMMON = ("nchains", "numit", "walk", "thinning", "burnin", "grtest", "grexit", "grcheck", "grthreshold")
+
+
+def run_resident_groups(worker, cfgs, log=None, first: int = 0, start=None, block: int = 256):
+    """An ensemble: ``len(cfgs)`` INDEPENDENT retrievals on one engine in one resident loop
+    (``bartrt_mcmc_run_resident_groups``; csrc/mcmc.hip: mcmc_advance_groups).  Per iteration there is one sampler
+    launch, a workgroup per retrieval, and one batched model evaluation over the chains of all of them, so the
+    launches one ten-chain retrieval leaves half empty are filled.  ``cfgs`` is a list of :class:`SamplerConfig`: each
+    carries its own params, box, stepsizes (fixed and shared patterns included), data, uncert, priors and seed; the
+    keys of ``GROUP_COMMON`` must agree (ValueError naming the first that differs), as must the parameter and data
+    counts.  At most 1024 chains in all.  Group g draws as :func:`run_resident` on ``cfgs[g]`` alone does, and where
+    the model's kernels give a row the same bits in both batch sizes its arrays are that run's bytes.
+
+    Convergence tests as in :func:`run_resident`, on every group's own rows; with ``grexit`` the call stops at the
+    first test that finds EVERY group converged.  ``first`` / ``start`` [ngroups, nchains, npars] resume all groups.
+
+    Speed as measured (MEASUREMENTS.md row 23; one MI355X, ten chains per group, snooker, against consecutive
+    :func:`run_resident` calls on the same configurations): 1.27 / 1.63 / 1.80 / 1.90 x the models/s at 2 / 4 / 6 / 8
+    groups on the headline shape (1.42e5 models/s at six), 1.86 / 2.99 / 3.33 / 3.77 x on the WASP-12b shape; one
+    group costs what :func:`run_resident` costs.
+
+    Returns a list of :func:`run_resident`'s dictionaries, one per group, each with ``nbad`` (that group's models
+    rejected with status 1, 2, 3) and ``converged_at``: the global
+    iteration count at the first test that found that group converged (None: no test did)."""
+    from . import transit_module as trm
+    cfgs = list(cfgs)
+    if not cfgs:
+        raise ValueError("run_resident_groups: at least one configuration")
+    c0, G = cfgs[0], len(cfgs)
+    for g, cfg in enumerate(cfgs):
+        for key in GROUP_COMMON:
+            if getattr(cfg, key) != getattr(c0, key):
+                raise ValueError("run_resident_groups: `%s` is %r in group %d and %r in group 0: the groups of one call "
+                                 "share it" % (key, getattr(cfg, key), g, getattr(c0, key)))
+    if c0.walk == "unif":
+        raise ValueError("run_resident_groups: walk = unif is not a chain: run_grid makes model grids")
+    need_whole_grid_or_comm(worker, "run_resident_groups")
+    nch = c0.nchains
+    total = max(1, int(np.ceil(c0.numit / nch)))
+    first = int(first)
+    nsteps = total - first
+    if nsteps < 1:
+        raise ValueError("run_resident_groups: the run before already made %d of %d iterations" % (first, total))
+    thin = max(1, int(c0.thinning))
+    nkept = -(-nsteps // thin)
+    arrays = [problem_arrays(cfg, "run_resident_groups: group %d" % g) for g, cfg in enumerate(cfgs)]
+    npars, ndata = len(arrays[0][0]), len(arrays[0][4])
+    if any(len(a[0]) != npars or len(a[4]) != ndata for a in arrays):
+        raise ValueError("run_resident_groups: every group has the same number of parameters and of data")
+    grcheck = 0
+    if c0.grtest and nch > 1:
+        if c0.grcheck:
+            block = min(block, int(c0.grcheck))
+        block = -(-block // thin) * thin
+        grcheck = int(c0.grcheck) if c0.grcheck else max(1, -(-nsteps // (10 * block))) * block
+    opts = McmcOpts(size=C.sizeof(McmcOpts), snooker=int(c0.walk == "snooker"), thin=thin, block=block,
+                    burnin=int(c0.burnin), grcheck=grcheck, grthreshold=float(c0.grthreshold),
+                    grexit=int(bool(c0.grexit)), first=first, walk=WALK_MRW if c0.walk == "mrw" else 0)
+    if start is not None:
+        start = np.ascontiguousarray(start, np.double)
+        if start.shape != (G, nch, npars):
+            raise ValueError("run_resident_groups: start holds one row per group and chain")
+    groups = (McmcGroup * G)()
+    for g, (cfg, (par, pmin, pmax, step, data, unc, pri)) in enumerate(zip(cfgs, arrays)):
+        groups[g] = McmcGroup(size=C.sizeof(McmcGroup), params=par.ctypes.data, pmin=pmin.ctypes.data,
+                              pmax=pmax.ctypes.data, stepsize=step.ctypes.data, data=data.ctypes.data,
+                              uncert=unc.ctypes.data, seed=cfg.seed)
+        if pri is not None:
+            groups[g].prior, groups[g].priorlow, groups[g].priorup = (v.ctypes.data for v in pri)
+        if start is not None:
+            groups[g].start = start[g].ctypes.data
+    if log is not None:
+        report = PROGRESS(lambda it, acc, _: log("step %d/%d  acceptance %.2f" % (first + it, total, acc / (it * nch * G))))
+        opts.progress = C.cast(report, C.c_void_p)
+    ngr = nsteps // grcheck + 1 if grcheck > 0 else 0
+    grstat, grwhen = np.zeros((max(ngr, 1), G, npars)), np.zeros(max(ngr, 1), np.int64)
+    made, done = C.c_int(0), C.c_long(0)
+    opts.grstat, opts.grwhen, opts.ngr = grstat.ctypes.data, grwhen.ctypes.data, ngr
+    opts.ngr_out, opts.done = C.addressof(made), C.addressof(done)
+    chain, chis = np.zeros((G, nch, nkept, npars)), np.zeros((G, nch, nkept))
+    models = np.zeros((G, nch, nkept, ndata))
+    nacc, nbad, conv = np.zeros(G, np.int64), np.zeros((G, 4), np.int64), np.zeros(G, np.intc)
+    ptr = lambda v: v.ctypes.data_as(C.c_void_p)
+    trm.check(trm.lib().bartrt_mcmc_run_resident_groups(
+        G, C.cast(groups, C.c_void_p), nch, npars, C.c_long(nsteps), ndata, C.cast(C.byref(opts), C.c_void_p),
+        ptr(chain), ptr(chis), ptr(models), ptr(nacc), ptr(nbad), ptr(conv)))
+    for k in (1, 2, 3):
+        worker.nbad[k] += int(nbad[:, k].sum())
+    kd = -(-done.value // thin)
+    when = grwhen[:made.value].copy()
+    out = []
+    for g, cfg in enumerate(cfgs):
+        step = arrays[g][3]
+        free = step > 0
+        psrf = grstat[:made.value, g].copy()
+        last_ok = lambda r: bool(free.any() and np.all(np.isfinite(r[free])) and np.all(r[free] < cfg.grthreshold))
+        if log is not None:
+            for k in range(made.value):
+                log("group %d: Gelman-Rubin after %d iterations: %s" % (g, when[k], " ".join("%.4f" % v for v in psrf[k][free])))
+            log("group %d: %d iterations of %d chains; best chisq %.4f  acceptance %.2f" % (
+                g, done.value, nch, float(chis[g, :, :kd].min()), nacc[g] / (done.value * nch)))
+        res = _result(np.ascontiguousarray(chain[g, :, :kd]), np.ascontiguousarray(chis[g, :, :kd]), int(nacc[g]),
+                      done.value, nch, cfg, thin, burnin=max(0, cfg.burnin - first),
+                      models=np.ascontiguousarray(models[g, :, :kd]), done=done.value, grhistory=(when, psrf),
+                      converged=made.value > 0 and last_ok(psrf[-1]), accepted=int(nacc[g]),
+                      converged_at=int(when[conv[g]]) if 0 <= conv[g] < len(when) else None,
+                      nbad=[int(v) for v in nbad[g, 1:]])
+        out.append(res)
+    if log is not None and done.value < nsteps:
+        log("grexit: every group converged; stopped after %d of %d iterations" % (first + done.value, total))
+    return out
+
+
 class GridOpts(C.Structure):
     """``bartrt_grid_opts`` of include/bartrt.h."""
     _fields_ = [("size", C.c_ulong), ("seed", C.c_ulonglong), ("chunk", C.c_long), ("first", C.c_long),

@@ -357,6 +357,43 @@ int bartrt_mcmc_run_resident(int nchains, int npars, long nsteps, const double *
                              const double *pmax, const double *stepsize, int ndata, const double *data,
                              const double *uncert, const bartrt_mcmc_opts *opts, double *chain, double *chisq,
                              double *models /* NULL */, long *naccept, long *nbad);
+/* ENSEMBLES: ngroups INDEPENDENT retrievals ("groups") of one shape -- nchains chains, npars parameters and ndata data
+ * each, on the one engine -- advanced in lockstep by one resident loop.  An iteration is one sampler launch, workgroup
+ * g advancing group g with chain i of the group on lane i, and ONE batched model evaluation over all ngroups x nchains
+ * rows: the launches a ten-chain retrieval leaves half empty are filled by its neighbours.  Nothing else is shared.
+ * Group g is bartrt_mcmc_run_resident with groups[g]'s params, pmin, pmax, stepsize (fixed and shared parameters its
+ * own), data, uncert, priors (all three or none) and seed, and the opts of this call: its draws are keyed by its seed
+ * and its own chain indices 0 .. nchains - 1, its partner chains are drawn among its own, and where the model's
+ * launches give a row the same bits in both batches, chain / chisq / models / naccept / nbad of group g are the bytes
+ * of that single call.
+ *   chain[ngroups][nchains][nkept][npars], chisq[ngroups][nchains][nkept], models (may be NULL)
+ *   [ngroups][nchains][nkept][ndata]; naccept[ngroups], nbad[ngroups][4], converged_at[ngroups] (each may be NULL).
+ * Set size = sizeof(bartrt_mcmc_group) in EVERY group (fields past `size` read as zero).  opts as above, except that
+ * opts->seed, prior, priorlow, priorup and start must be unset (BARTRT_EINVAL): they live in the groups.  Limits:
+ * ngroups >= 1, nchains >= 1 and ngroups x nchains <= 1024, 64 parameters (BARTRT_EINVAL beyond).  What the single
+ * call refuses about a problem is refused here with the group named: "mcmc_run_resident_groups: group 2: stepsize[6] =
+ * -7 ...".  walk = BARTRT_WALK_UNIF: BARTRT_EINVAL.
+ *   CONVERGENCE TESTS run for every group on its own rows, by the single call's kernels in their fixed summation order:
+ * opts->grstat is [ngr][ngroups][npars], grwhen[ngr] as above.  converged_at[g] is the index k of the first test that
+ * found group g converged (its iteration count: grwhen[k]), -1 if none did.  grexit stops the call at the first test
+ * at which EVERY group is found converged; a group that converged earlier keeps running until then, so its rows up
+ * to any iteration are still those of a run of its own.  Stopping point, discarded blocks and *done as above.
+ *   RESUME: opts->first = t0 > 0 with start[nchains][npars] in every group, or neither; the guarantee of the single
+ * call holds group by group.
+ * Sharded engines, LOCKSTEP, chain-service clients and line-by-line engines with a communicator: as for
+ * bartrt_mcmc_run_resident. */
+typedef struct bartrt_mcmc_group {
+  unsigned long size;                 /* sizeof(bartrt_mcmc_group) of the caller */
+  const double *params;               /* [npars] the configured point (not read in a resumed call) */
+  const double *pmin, *pmax, *stepsize;
+  const double *data, *uncert;        /* [ndata] */
+  const double *prior, *priorlow, *priorup;   /* [npars], all three or none */
+  unsigned long long seed;
+  const double *start;                /* resume: [nchains][npars], with opts->first > 0 */
+} bartrt_mcmc_group;
+int bartrt_mcmc_run_resident_groups(int ngroups, const bartrt_mcmc_group *groups, int nchains, int npars, long nsteps,
+                                    int ndata, const bartrt_mcmc_opts *opts, double *chain, double *chisq,
+                                    double *models /* NULL */, long *naccept, long *nbad, int *converged_at);
 /* Diagnostics: the sampler's draws of chains 0 .. nchains - 1 at iteration t, evaluated ON THE DEVICE (its log, sqrt,
  * sin and cos): out[nchains][9 + npars] = the uniforms of r1, r2, z, gamma and acceptance, log of the acceptance
  * uniform, the partners r1, r2, z (z = -1 with fewer than four chains) and the jitter normal of each parameter.
