@@ -560,6 +560,36 @@ int bartrt_get_radius(double *rad, int nlayers) {
   });
 }
 
+int bartrt_get_prep_shape(int *nmol, int *ncs) {
+  NEED_ENGINE();
+  if (nmol) *nmol = g_eng->M;
+  if (ncs) *ncs = g_eng->C;
+  return BARTRT_OK;
+}
+
+int bartrt_get_prep_records(int walker, double *coef, long long *idx, int *kstop, unsigned char *ok) {
+  NEED_ENGINE();
+  Engine *e = g_eng;
+  const Engine::PrepSeen &s = e->prep_seen;
+  if (!s.coef || s.n <= 0) return fail(BARTRT_EINVAL, "get_prep_records: no launch has left layer records to read back");
+  if (s.folded)
+    return fail(BARTRT_EINVAL, "get_prep_records: the latest launch prepared its walkers inside the RT kernel; the "
+                               "records lived in LDS and were never written out");
+  if (walker < 0 || walker >= s.n)
+    return fail(BARTRT_EINVAL, "get_prep_records: walker " + std::to_string(walker) + " is outside the latest batch of " +
+                               std::to_string(s.n));
+  return guarded([&] {
+    static_assert(sizeof(idx_t) == sizeof(long long), "idx_t is the header's long long");
+    const size_t L = (size_t)e->L, NC = (size_t)coef_stride(e->M, e->C), NI = (size_t)idx_stride(e->C);
+    HIPCHK(hipDeviceSynchronize());
+    if (coef) HIPCHK(hipMemcpy(coef, s.coef + (size_t)walker * L * NC, sizeof(double) * L * NC, hipMemcpyDeviceToHost));
+    if (idx) HIPCHK(hipMemcpy(idx, s.idx + (size_t)walker * L * NI, sizeof(idx_t) * L * NI, hipMemcpyDeviceToHost));
+    if (kstop) HIPCHK(hipMemcpy(kstop, s.kstop + walker, sizeof(int), hipMemcpyDeviceToHost));
+    if (ok) HIPCHK(hipMemcpy(ok, s.ok + walker, 1, hipMemcpyDefault));   // (device memory, or the pinned staging buffer)
+    return BARTRT_OK;
+  });
+}
+
 int bartrt_get_nangles(void) { CLIENT_OR_ENGINE(); return g_cli ? g_cli->info.A : g_eng->A; }
 
 int bartrt_get_tau(double *tau, int *last, int nwave, int nlayers) {

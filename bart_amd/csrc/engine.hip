@@ -614,6 +614,7 @@ void Engine::ensure_walkers(int n) {
   HIPCHK(hipDeviceSynchronize());
   if (last_prof == d_prof) forget_profiles();
   pf_have_prof = nullptr;  // (prefetched records, if any, are dropped with their buffers' sizes)
+  prep_seen = PrepSeen{};
   if (cap2) {
     rec[1].reserve((size_t)cap, L, M, C);
     cap2 = cap;
@@ -633,6 +634,7 @@ void Engine::ensure_walkers(int n) {
 void Engine::ensure_second_set() {
   if (cap2 >= cap_walkers) return;
   HIPCHK(hipDeviceSynchronize());
+  prep_seen = PrepSeen{};
   rec[1].reserve((size_t)cap_walkers, L, M, C);
   cap2 = cap_walkers;
 }
@@ -655,6 +657,7 @@ void Engine::ensure_pin(size_t bytes) {
   const size_t n = (bytes + sizeof(double) - 1) / sizeof(double);
   if (n <= h_pin.count()) return;
   forget_profiles();
+  prep_seen = PrepSeen{};   // (a small host-buffer call keeps its flags in h_pin)
   h_pin.reserve(n);
 }
 
@@ -938,6 +941,7 @@ void Engine::run_chunk(const RunRequest &rq) {
   // (a call that launches nothing -- no walkers -- takes no event pair: bartrt_timing_end would read unstamped events)
   const bool timed = timing && n > 0 && rt.W > 0 && (timing_seen++ % timing_stride == 0);
   const RtArgs r = rt_args(rq, pa, pf, eclipse_rt, timed);
+  bool folded = false;
   if (rq.lbl_fused) lbl_rt_eclipse(*this, rq.prof, n, r, st);
   else if (solution == 1) {
     RtLaunchInfo li;   // (the transit kernels keep no walked-layer record: the name only)
@@ -946,7 +950,6 @@ void Engine::run_chunk(const RunRequest &rq) {
   }
   else {
     RtLaunchInfo li;
-    bool folded = false;
     if (try_fold) HIPCHK(launch_rt_folded(r, pa, rt_block(), st, &li, &folded));
     if (!folded) {
       if (try_fold) HIPCHK(launch_prep(pa, st));
@@ -959,6 +962,8 @@ void Engine::run_chunk(const RunRequest &rq) {
       pf_have_stream = st; pf_have_set = pf.now;
     }
   }
+  // (records prefetched by the previous call's launch: their flags lie in that set unless this call asked for a copy)
+  prep_seen = PrepSeen{pa.coef, pa.idx, pa.kstop, use_have && !rq.ok ? rec[pf.bset].ok.get() : pa.ok, n, folded};
   if (timed) {
     if (rq.lbl_fused) HIPCHK(hipEventRecord(ev[ev_used + 1], st));
     ev_used += 2;

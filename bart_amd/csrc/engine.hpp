@@ -156,6 +156,17 @@ struct Engine : EngineStream {
   int walked_nwalkers = 0;
   size_t walked_restart_off = 0;   // the restarted-wave counts of the last record: d_walked + this, [walked_nwalkers]
   RtLaunchInfo walked_info{};
+  // Where the latest launch's preparation left its layer records (bartrt_get_prep_records: a host-side copy for
+  // tests).  folded: the RT kernel prepared its own walkers, the records lived in its LDS.  Forgotten when the
+  // buffers behind it are regrown.
+  struct PrepSeen {
+    const double *coef = nullptr;
+    const idx_t *idx = nullptr;
+    const int *kstop = nullptr;
+    const unsigned char *ok = nullptr;
+    int n = 0;
+    bool folded = false;
+  } prep_seen;
   // timing of RT launches
   bool timing = false;
   int timing_stride = 1;     // events bracket every timing_stride-th launch (a pair of event

@@ -91,6 +91,28 @@ def get_tau(walker=None):
     return tau, last
 
 
+def get_radius() -> np.ndarray:
+    """Hydrostatic radii [L] (cm, atm layer order) of the latest run's first profile."""
+    out = np.zeros(nlayers())
+    _check(trm.lib().bartrt_get_radius(_ptr(out), out.size))
+    return out
+
+
+def prep_records(walker: int):
+    """What the latest launch's preparation wrote for one walker of its batch (diagnostics; include/bartrt.h,
+    bartrt_get_prep_records): (coef[L, 4 + 2 M + 2 C], idx[L, 1 + C], kstop, ok), layers from the top.  Raises
+    when the launch prepared its walkers inside the RT kernel, and for a walker outside the batch."""
+    m, c = C.c_int(), C.c_int()
+    _check(trm.lib().bartrt_get_prep_shape(C.byref(m), C.byref(c)))
+    L = nlayers()
+    coef = np.zeros((L, 4 + 2 * m.value + 2 * c.value))
+    idx = np.zeros((L, 1 + c.value), np.int64)
+    kstop = np.zeros(1, np.int32)
+    ok = np.zeros(1, np.uint8)
+    _check(trm.lib().bartrt_get_prep_records(int(walker), _ptr(coef), _ptr(idx), _ptr(kstop), _ptr(ok)))
+    return coef, idx, int(kstop[0]), int(ok[0])
+
+
 def lbl_extinction(profile: np.ndarray) -> np.ndarray:
     """Line-by-line extinction [L, W_local] (cm-1, atm layer order) of one profile."""
     prof = np.ascontiguousarray(profile, np.double).ravel()

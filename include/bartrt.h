@@ -595,6 +595,25 @@ int bartrt_get_angles(double *deg, int n);
 int bartrt_get_intensity(double *intens, int nangles, int nwave);
 int bartrt_get_intensity_of(int walker, double *intens, int nangles, int nwave);  /* as bartrt_get_tau_of */
 
+/* Diagnostics (tests): what the preparation of the latest launch wrote for walker `walker` of its batch, copied
+ * back from the engine's device buffers -- a host-side copy after a device synchronisation, no kernel runs.  Any
+ * output may be NULL.  With M table molecules and C cross-section tables (bartrt_get_prep_shape; a file read under
+ * `cia_interp spline` counts twice, its second table holds the curvature terms), layer k counted FROM THE TOP:
+ *   coef[L][4 + 2 M + 2 C]   path length r[k-1] - r[k] (cm; 0 on the top layer), c2 / T, per molecule the weights
+ *                            rho (1 - f) and rho f of the table's planes j and j + 1, per cross-section table its two
+ *                            weights, the Rayleigh term (x wn^4), the grey-cloud extinction;
+ *   idx[L][1 + C]            byte offsets: of plane j of the layer's slab in the table ((l Nt + j) M W 8, l the layer
+ *                            in atm order), and of each cross-section table's pair plane (16 W bytes each);
+ *   kstop                    the last layer of the column (L - 1), or a cloud deck's layer with bit 30 set;
+ *   ok                       1, or 0 for a profile the engine cannot evaluate (its records are zeros, c2 / T = 1).
+ * BARTRT_EINVAL: no launch yet (or its buffers have been regrown since); a walker index outside the latest batch;
+ * the latest launch prepared its walkers inside the RT kernel (one to four walkers under the default conventions:
+ * the records lived in LDS and were never written out -- run a larger batch, or with BARTRT_FOLD=0).  After a
+ * device-buffer call the flags are read from the caller's buffer, which has to be alive still.  A batch that went
+ * out in chunks leaves its last chunk.  Contribution-function calls keep records of their own and leave these alone. */
+int bartrt_get_prep_shape(int *nmol, int *ncs);
+int bartrt_get_prep_records(int walker, double *coef, long long *idx, int *kstop, unsigned char *ok);
+
 /* Band-averaged contribution functions and transmittance of a batch of profiles: BART's
  * post-processing (code/cf.py:114-199, called at BART.py:626-644) on the optical depth
  * bartrt_get_tau_of would return for each walker with `toomuch` infinite -- the engine's
