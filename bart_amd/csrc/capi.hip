@@ -1039,6 +1039,7 @@ static McmcOpts mcmc_opts_of(const bartrt_mcmc_opts &o) {
   m.grstat = o.grstat; m.grwhen = o.grwhen; m.ngr = o.ngr; m.ngr_out = o.ngr_out;
   m.first = o.first; m.start = o.start; m.done = o.done;
   m.walk = o.walk;
+  m.esstarget = o.esstarget; m.essexit = o.essexit; m.maxlag = o.maxlag; m.essstat = o.essstat; m.esstau = o.esstau;
   return m;
 }
 
@@ -1098,6 +1099,17 @@ int bartrt_mcmc_gr(const double *chain, int nchains, long nkept, int npars, cons
   if (!chain || !stepsize || !psrf || !triples || !converged) return null_buffer("bartrt_mcmc_gr");
   return guarded([&] {
     mcmc_gr_probe(chain, nchains, nkept, npars, stepsize, r0, r1, threshold, psrf, triples, converged);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_mcmc_ess(const double *chain, int nchains, long nkept, int npars, const double *stepsize, long r0, long r1,
+                    long maxlag, double esstarget, double *tau, double *ess, int *truncated, double *acf,
+                    int *reached) {
+  if (!chain || !stepsize || !tau || !ess || !truncated || !reached) return null_buffer("bartrt_mcmc_ess");
+  return guarded([&] {
+    mcmc_ess_probe(chain, nchains, nkept, npars, stepsize, r0, r1, maxlag, esstarget, tau, ess, truncated, acf,
+                   reached);
     return BARTRT_OK;
   });
 }

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "ess_core.hpp"
 #include "gr_core.hpp"
 #include "mcmc_core.hpp"
 #include "retrieval_host.hpp"
@@ -306,6 +307,146 @@ struct GrTest {
   }
 };
 
+// ---- the effective sample size of the chain in device memory (ess_core.hpp states every sum and its order) ----------
+// The lagged sums S_k.  A workgroup owns one (chain i, free parameter, block b of ess::kLanes consecutive lags); lane l
+// carries S_k of lag k = b kLanes + l in a register and adds to it in ascending row order, kLanes rows a step.  The
+// differences x - m go through LDS: win_a holds those of the step's rows (every lane reads the same one), win_b a ring
+// of two halves with those of the rows b kLanes further on -- the half the step before loaded as its "next" and the
+// next one, loaded now -- in which lane l reads entry rr + l of row rr's partner.  A row >= r1 is never read: its
+// entry is 0.0 and no lane adds it.  The means are the merge stage's (triples[nch][npars][3]); acf[nch][npars][K + 1]
+// is written for the free parameters alone.  Grid: nch nfree ceil((K + 1) / kLanes) workgroups, the lag block fastest.
+__global__ __launch_bounds__(ess::kLanes) void mcmc_ess_lags(const double *chain, int nch, long nkept, int npars,
+                                                             const double *stepsize, const double *triples, long r0,
+                                                             long r1, long K, int nfree, double *acf) {
+  constexpr int L = ess::kLanes;
+  __shared__ double win_a[L], win_b[2 * L];
+  const int l = threadIdx.x;
+  const long nblk = (K + L) / L;
+  size_t w = blockIdx.x;
+  const long b = (long)(w % nblk);
+  w /= nblk;
+  const int f = (int)(w % nfree), i = (int)(w / nfree);
+  if (i >= nch) return;
+  int j = 0;   // the f-th free parameter
+  for (int seen = -1; j < npars; j++)
+    if (stepsize[j] > 0 && ++seen == f) break;
+  if (j >= npars) return;
+  const double m = triples[((size_t)i * npars + j) * 3 + 1];
+  const double *col = chain + (size_t)i * nkept * npars + j;
+  const long k = b * L + l;        // this lane's lag
+  const long lim = r1 - k;         // rows r < lim have a partner r + k
+  const long first = r0 + b * L;   // the row of the ring's entry 0
+  auto diff_at = [&](long row) { return row < r1 ? ess::diff(col[(size_t)row * npars], m) : 0.0; };
+  double s = 0.0;
+  win_b[l] = diff_at(first + l);
+  const long nsteps = (r1 - first + L - 1) / L;   // rows r0 ... r1 - 1 - b kLanes: those with a partner at lag b kLanes
+  for (long c = 0; c < nsteps; c++) {
+    const long base = r0 + c * L;
+    win_a[l] = diff_at(base + l);
+    win_b[(int)((c + 1) & 1) * L + l] = diff_at(first + (c + 1) * L + l);
+    __syncthreads();
+    const int h = (int)(c & 1) * L + l;
+    for (int rr = 0; rr < L; rr++) {
+      const double t = ess::lag_add(s, win_a[rr], win_b[(h + rr) & (2 * L - 1)]);
+      s = base + rr < lim ? t : s;
+    }
+    __syncthreads();
+  }
+  if (k <= K) acf[((size_t)i * npars + j) * (K + 1) + k] = s;
+}
+
+// Finisher: one workgroup.  A lane per (chain, parameter) for tau and the truncated flag, then parameter j on lane j
+// for ess and lane 0 for `reached`.  Writes the record the host reads (host-mapped, as mcmc_gr_finish's): rec_d =
+// ess[npars] then tau[nch][npars]; rec_w = reached, the four counters summed over the chains as they stand now
+// (counts null: zeros), then truncated[nch][npars].  tau and trunc: the same in device memory, for the second stage.
+constexpr int kEssFinishLanes = 256;
+static_assert(kEssFinishLanes >= kMaxPars, "one lane per parameter");
+__global__ __launch_bounds__(kEssFinishLanes) void mcmc_ess_finish(const double *acf, int nch, int npars,
+                                                                   const double *stepsize, long n, long K,
+                                                                   double target, const long *counts, double *tau,
+                                                                   int *trunc, double *rec_d, long *rec_w) {
+  __shared__ double e[kMaxPars];
+  const int l = threadIdx.x;
+  for (size_t q = l; q < (size_t)nch * npars; q += kEssFinishLanes) {
+    int tr = 0;
+    const double t = stepsize[q % npars] > 0 ? ess::tau_of(acf + q * (K + 1), K, &tr) : 0.0;
+    tau[q] = t;
+    trunc[q] = tr;
+    rec_d[npars + q] = t;
+    rec_w[5 + q] = tr;
+  }
+  __syncthreads();
+  if (l < npars) {
+    e[l] = stepsize[l] > 0 ? ess::ess_of(tau + l, (size_t)npars, nch, n) : 0.0;
+    rec_d[l] = e[l];
+  }
+  __syncthreads();
+  if (l == 0) rec_w[0] = ess::reached_of(e, trunc, stepsize, nch, npars, target);
+  if (l >= 1 && l <= 4) {
+    long sum = 0;
+    if (counts)
+      for (int i = 0; i < nch; i++) sum += counts[(size_t)i * 4 + (l - 1)];
+    rec_w[l] = sum;
+  }
+}
+
+// The launches of one ESS test on `stream` -- the Gelman-Rubin test's leaf and merge stages for the means, the lagged
+// sums, the finisher -- their scratch, and the host-mapped records: `slots` of them, each ess[npars] + tau[nch][npars]
+// doubles and 5 + nch npars words.
+struct EssTest {
+  int nch, npars, nfree;
+  long maxlag;   // as ess::maxlag_of gives it
+  DevBuf<double> leafs, triples, acf, tau;
+  DevBuf<int> trunc;
+  PinBuf<double> rec_d;
+  PinBuf<long> rec_w;
+  double *rec_d_dev = nullptr;
+  long *rec_w_dev = nullptr;
+
+  size_t doubles() const { return (size_t)npars + (size_t)nch * npars; }
+  size_t words() const { return 5 + (size_t)nch * npars; }
+  // stepsize: the host's copy (the launches read the device's)
+  EssTest(int nch_, int npars_, const double *stepsize, long maxrows, long maxlag_, int slots)
+      : nch(nch_), npars(npars_), nfree(0), maxlag(ess::maxlag_of(maxlag_)) {
+    for (int j = 0; j < npars; j++) nfree += stepsize[j] > 0;
+    leafs.reserve((size_t)nch * gr::tiles(0, maxrows) * npars * 3);
+    triples.reserve((size_t)nch * npars * 3);
+    acf.reserve((size_t)nch * npars * (ess::lags(maxlag, maxrows) + 1));
+    tau.reserve((size_t)nch * npars);
+    trunc.reserve((size_t)nch * npars);
+    rec_d.reserve(doubles() * slots);
+    rec_w.reserve(words() * slots);
+    void *p = nullptr;
+    HIPCHK(hipHostGetDevicePointer(&p, rec_d.get(), 0));
+    rec_d_dev = static_cast<double *>(p);
+    HIPCHK(hipHostGetDevicePointer(&p, rec_w.get(), 0));
+    rec_w_dev = static_cast<long *>(p);
+  }
+  const double *stat(int slot) const { return rec_d.get() + doubles() * slot; }
+  const long *word(int slot) const { return rec_w.get() + words() * slot; }
+  // rows [r0, r1) of the device chain[nch][nkept][npars]; ess::testable(r0, r1) and r1 - r0 <= maxrows hold
+  void enqueue(const double *chain, long nkept, const double *stepsize, long r0, long r1, double target,
+               const long *counts, int slot, hipStream_t st) {
+    const long nt = gr::tiles(r0, r1), n = r1 - r0, K = ess::lags(maxlag, n);
+    const size_t lanes = (size_t)nch * nt * npars, pairs = (size_t)nch * npars;
+    hipLaunchKernelGGL(mcmc_gr_leaf, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, chain, nch, nkept, npars,
+                       stepsize, r0, r1, leafs.get());
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(mcmc_gr_merge, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, leafs.get(), nch, nt,
+                       npars, stepsize, triples.get());
+    HIPCHK(hipGetLastError());
+    if (nfree > 0) {
+      const size_t groups = (size_t)nch * nfree * ((K + ess::kLanes) / ess::kLanes);
+      hipLaunchKernelGGL(mcmc_ess_lags, dim3((unsigned)groups), dim3(ess::kLanes), 0, st, chain, nch, nkept, npars,
+                         stepsize, triples.get(), r0, r1, K, nfree, acf.get());
+      HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(mcmc_ess_finish, dim3(1), dim3(kEssFinishLanes), 0, st, acf.get(), nch, npars, stepsize, n, K,
+                       target, counts, tau.get(), trunc.get(), rec_d_dev + doubles() * slot, rec_w_dev + words() * slot);
+    HIPCHK(hipGetLastError());
+  }
+};
+
 struct Events {
   hipEvent_t ev[2] = {nullptr, nullptr};
   Events() {
@@ -353,6 +494,38 @@ void mcmc_gr_probe(const double *chain, int nch, long nkept, int npars, const do
   *converged = (int)test.words(0)[0];
 }
 
+void mcmc_ess_probe(const double *chain, int nch, long nkept, int npars, const double *stepsize, long r0, long r1,
+                    long maxlag, double target, double *tau, double *ess_out, int *truncated, double *acf,
+                    int *reached) {
+  if (nch < 1 || nch > (1 << 20) || npars < 1 || npars > kMaxPars || nkept < 1)
+    throw std::invalid_argument("bartrt_mcmc_ess: 1 <= nchains <= 2^20, 1 <= npars <= 64 and nkept >= 1");
+  if (r0 < 0 || r1 < r0 || r1 > nkept || !(target >= 0))
+    throw std::invalid_argument("bartrt_mcmc_ess: 0 <= r0 <= r1 <= nkept and esstarget >= 0");
+  if (maxlag < 0 || maxlag > ess::kMaxLag)
+    throw std::invalid_argument("bartrt_mcmc_ess: maxlag = " + std::to_string(maxlag) + " is not within 0 (the default, " +
+                                std::to_string(ess::kDefaultLag) + ") ... " + std::to_string(ess::kMaxLag));
+  const size_t pairs = (size_t)nch * npars;
+  const long K = ess::lags(ess::maxlag_of(maxlag), r1 - r0);
+  std::fill(ess_out, ess_out + npars, 0.0);
+  std::fill(tau, tau + pairs, 0.0);
+  std::fill(truncated, truncated + pairs, 0);
+  if (acf && K >= 0) std::fill(acf, acf + pairs * (K + 1), 0.0);
+  *reached = 0;
+  if (!ess::testable(r0, r1)) return;   // no test: zeros
+  DevBuf<double> d_chain, d_step;
+  d_chain.upload(chain, (size_t)nch * nkept * npars);
+  d_step.upload(stepsize, npars);
+  EssTest test(nch, npars, stepsize, r1 - r0, maxlag, 1);
+  HIPCHK(hipMemset(test.acf, 0, sizeof(double) * pairs * (K + 1)));   // (the lags kernel writes the free parameters' alone)
+  test.enqueue(d_chain, nkept, d_step, r0, r1, target, nullptr, 0, nullptr);
+  HIPCHK(hipDeviceSynchronize());
+  std::copy(test.stat(0), test.stat(0) + npars, ess_out);
+  std::copy(test.stat(0) + npars, test.stat(0) + npars + pairs, tau);
+  for (size_t q = 0; q < pairs; q++) truncated[q] = (int)test.word(0)[5 + q];
+  if (acf) HIPCHK(hipMemcpy(acf, test.acf, sizeof(double) * pairs * (K + 1), hipMemcpyDeviceToHost));
+  *reached = (int)test.word(0)[0];
+}
+
 namespace {
 
 // The resident loop over G groups of nch chains each (mcmc_core.hpp: GROUPS); mcmc_run_resident is its G = 1 under its
@@ -383,6 +556,17 @@ void resident_loop(Engine &e, const std::string &who, int G, const McmcGroup *gr
     throw std::invalid_argument(who + ": grcheck = " + std::to_string(opts.grcheck) +
                                 " must be a multiple of block = " + std::to_string(B) + ", and block of thin = " +
                                 std::to_string(opts.thin) + ": every test falls on a block end that is a kept row");
+  const bool ess_on = opts.esstarget > 0;
+  if (!(opts.esstarget >= 0) || opts.maxlag < 0)
+    throw std::invalid_argument(who + ": esstarget and maxlag must be >= 0");
+  if (opts.maxlag > ess::kMaxLag)
+    throw std::invalid_argument(who + ": maxlag = " + std::to_string(opts.maxlag) + " is more than " +
+                                std::to_string(ess::kMaxLag) + " lags");
+  if (ess_on && opts.grcheck == 0)
+    throw std::invalid_argument(who + ": esstarget > 0 with grcheck = 0: the effective-sample-size tests run where "
+                                      "the convergence tests run, every grcheck iterations");
+  if (!ess_on && (opts.essexit || opts.essstat || opts.esstau))
+    throw std::invalid_argument(who + ": essexit, essstat and esstau come with esstarget > 0");
   std::vector<Objective> objective;
   if (by_value) objective.push_back(check_retrieval(who, &e, groups[0].p));
   else {
@@ -491,13 +675,19 @@ void resident_loop(Engine &e, const std::string &who, int G, const McmcGroup *gr
   auto test_rows = [&](long T) {   // the end of the row range of the test after T iterations, or 0: no test there
     if (opts.grcheck == 0 || (T % opts.grcheck != 0 && T != nsteps)) return 0L;
     const long r1 = mcmc::kept_rows(T, opts.thin);
-    return gr::testable(nch, r0, r1) ? r1 : 0L;
+    return gr::testable(nch, r0, r1) || (ess_on && ess::testable(r0, r1)) ? r1 : 0L;
   };
   std::unique_ptr<GrTest> tests;
   if (opts.grcheck > 0 && gr::testable(nch, r0, nkept)) tests.reset(new GrTest(nch, npars, nkept - r0, 2 * G));
+  // Effective-sample-size tests (ess_core.hpp; the single call alone): at the same places, behind the same block, on
+  // the same rows; one chain is enough for them, so with them a test is made wherever four rows lie past the burn-in
+  // and the Gelman-Rubin record of a one-chain test is zeros.
+  std::unique_ptr<EssTest> ess_tests;
+  if (ess_on && ess::testable(r0, nkept))
+    ess_tests.reset(new EssTest(nch, npars, groups[0].p.stepsize, nkept - r0, opts.maxlag, 2));
   bool tested[2] = {false, false};
   int ntests = 0;
-  long stop = -1;   // grexit: the iterations the result holds
+  long stop = -1;   // grexit / essexit: the iterations the result holds
   std::vector<long> stop_counts(4 * (size_t)G, 0);   // and the groups' counters there
   if (converged_at) std::fill(converged_at, converged_at + G, -1);
   auto finished = [&](long b) {   // block b is done: wait for it, report, read its test; true: stop here
@@ -511,19 +701,31 @@ void resident_loop(Engine &e, const std::string &who, int G, const McmcGroup *gr
     if (!tested[b % 2]) return false;
     const int k = ntests++;
     bool all = true;
+    const bool gr_made = tests && gr::testable(nch, r0, mcmc::kept_rows(T, opts.thin));
     for (int g = 0; g < G; g++) {
       const int slot = (int)(b % 2) * G + g;
-      if (k < opts.ngr && opts.grstat)
-        std::copy(tests->psrf(slot), tests->psrf(slot) + np, opts.grstat + ((size_t)k * G + g) * np);
-      const bool conv = tests->words(slot)[0] != 0;
+      if (k < opts.ngr && opts.grstat) {
+        double *to = opts.grstat + ((size_t)k * G + g) * np;
+        if (gr_made) std::copy(tests->psrf(slot), tests->psrf(slot) + np, to);
+        else std::fill(to, to + np, 0.0);
+      }
+      const bool conv = gr_made && tests->words(slot)[0] != 0;
       if (conv && converged_at && converged_at[g] < 0) converged_at[g] = k;
       all = all && conv;
     }
     if (k < opts.ngr && opts.grwhen) opts.grwhen[k] = first + T;
-    if (!opts.grexit || !all) return false;
+    bool reached = false;
+    if (ess_tests) {
+      const int slot = (int)(b % 2);
+      const double *rec = ess_tests->stat(slot);
+      if (k < opts.ngr && opts.essstat) std::copy(rec, rec + np, opts.essstat + (size_t)k * np);
+      if (k < opts.ngr && opts.esstau) std::copy(rec + np, rec + np + n * np, opts.esstau + (size_t)k * n * np);
+      reached = ess_tests->word(slot)[0] != 0;
+    }
+    if (!(opts.grexit || opts.essexit) || (opts.grexit && !all) || (opts.essexit && !reached)) return false;
     stop = T;
     for (int g = 0; g < G; g++) {
-      const long *w = tests->words((int)(b % 2) * G + g);
+      const long *w = ess_tests ? ess_tests->word((int)(b % 2)) : tests->words((int)(b % 2) * G + g);
       std::copy(w + 1, w + 5, stop_counts.begin() + 4 * (size_t)g);
     }
     return true;
@@ -537,10 +739,13 @@ void resident_loop(Engine &e, const std::string &who, int G, const McmcGroup *gr
       launch(t, t == last ? static_cast<long *>(snap_dev) + (size_t)(b % 2) * N : nullptr);
     const long r1 = test_rows(last);
     tested[b % 2] = r1 > 0;
-    if (r1 > 0)
+    if (r1 > 0 && gr::testable(nch, r0, r1))
       for (int g = 0; g < G; g++)
         tests->enqueue(ds[g].chain, nkept, consts[g]->d.stepsize, r0, r1, opts.grthreshold, ds[g].counts,
                        (int)(b % 2) * G + g, e.stream);
+    if (r1 > 0 && ess_on)
+      ess_tests->enqueue(ds[0].chain, nkept, consts[0]->d.stepsize, r0, r1, opts.esstarget, ds[0].counts, (int)(b % 2),
+                         e.stream);
     HIPCHK(hipEventRecord(events.ev[b % 2], e.stream));
   }
   for (long b = std::max(0L, enqueued - 2); stop < 0 && b < enqueued; b++) finished(b);
@@ -595,6 +800,9 @@ void mcmc_run_resident_groups(Engine &e, int ngroups, const McmcGroup *groups, i
   for (int g = 1; g < ngroups; g++)
     if (groups[g].p.npars != groups[0].p.npars || groups[g].p.ndata != groups[0].p.ndata)
       throw std::invalid_argument(who + ": every group has the same npars and ndata");
+  if (opts.esstarget != 0 || opts.essexit || opts.maxlag != 0 || opts.essstat || opts.esstau)
+    throw std::invalid_argument(who + ": esstarget, essexit, maxlag, essstat and esstau are not served here: the "
+                                      "effective-sample-size tests are the single call's (bartrt_mcmc_run_resident)");
   resident_loop(e, who, ngroups, groups, nch, nsteps, opts, false, chain, chisq, models, naccept, nbad, converged_at);
 }
 

@@ -108,6 +108,12 @@ struct McmcOpts {
   const double *start = nullptr;   // [nchains][npars]
   long *done = nullptr;
   int walk = 0;   // 0: demc / snooker as `snooker` says; mcmc::kWalkMrw: Metropolis random walk
+  // effective-sample-size tests where the convergence tests run (ess_core.hpp); the single call alone takes them
+  double esstarget = 0.0;   // 0: no ESS work at all
+  int essexit = 0;
+  long maxlag = 0;
+  double *essstat = nullptr;   // [ngr][npars]
+  double *esstau = nullptr;    // [ngr][nchains][npars]
 };
 // chain[nchains][nkept][npars], chisq[nchains][nkept], models[nchains][nkept][ndata] (may be null),
 // nkept = ceil(nsteps / thin); with grexit only the rows of the iterations done are written
@@ -132,6 +138,11 @@ void mcmc_run_resident_groups(Engine &e, int ngroups, const McmcGroup *groups, i
 // evaluated on the device by the loop's own kernels: psrf[npars], triples[nchains][npars][3], *converged; needs no engine
 void mcmc_gr_probe(const double *chain, int nchains, long nkept, int npars, const double *stepsize, long r0, long r1,
                    double threshold, double *psrf, double *triples, int *converged);
+// diagnostics (bartrt_mcmc_ess): ess_core.hpp's statistic of a host chain, rows [r0, r1), evaluated on the device by
+// the loop's own kernels: tau[nchains][npars], ess[npars], truncated[nchains][npars], acf (may be null)
+// [nchains][npars][K + 1], *reached; needs no engine
+void mcmc_ess_probe(const double *chain, int nchains, long nkept, int npars, const double *stepsize, long r0, long r1,
+                    long maxlag, double target, double *tau, double *ess, int *truncated, double *acf, int *reached);
 // diagnostics (bartrt_mcmc_draws): the core's draws of chains 0 .. nchains - 1 at iteration t, evaluated on the
 // device: out[nchains][9 + npars] (mcmc_core.hpp, draws_row); needs no engine
 void mcmc_draws_probe(unsigned long long seed, unsigned long long t, int nchains, int npars, double *out);

@@ -31,6 +31,12 @@ run would have made -- ``grexit`` applies again, to the new rows alone: set ``gr
 and writes the concatenated ``output.npy``, the concatenated ``savemodel`` file and an appended ``MCMC.log``.
 ``--resident`` is also the loop that serves ``walk = mrw``; the other two refuse it.
 
+``--resident --ess-target N`` computes, at every such test and on the GPU as well, the integrated autocorrelation time
+of every chain and the effective sample size (ESS) of every free parameter (csrc/ess_core.hpp); ``MCMC.log`` gains,
+next to each Gelman-Rubin line and at the end, the line of ESS per free parameter and the smallest one.  ``--ess-exit``
+stops the run at the first test at which every free parameter has N effective samples; with ``grexit = True`` at the
+first test where both hold.
+
 ``--resident --datasets FILE`` runs an ENSEMBLE (sampler.run_resident_groups; INTEGRATION.md, "Ensembles"): FILE is an
 ``.npz`` with ``data`` [G, ndata] and optionally ``uncert`` [G, ndata] (default: the configuration's) and ``seed`` [G]
 (default: the configuration's seed + g); the G retrievals advance in one resident loop and are written to
@@ -216,6 +222,12 @@ def main(argv=None):
                          "parameters, priors, thinning and the `savemodel` array of the configuration")
     ap.add_argument("--resume", action="store_true",
                     help="with --resident: continue the run whose output.npy and state.npz lie in the output directory")
+    ap.add_argument("--ess-target", type=float, default=0.0, metavar="N",
+                    help="with --resident: compute the effective sample size of every free parameter on the GPU "
+                         "wherever a Gelman-Rubin test runs, and write it to MCMC.log")
+    ap.add_argument("--ess-exit", action="store_true",
+                    help="with --ess-target N: stop at the first test at which every free parameter has N effective "
+                         "samples (with grexit = True: at the first test where both hold)")
     ap.add_argument("--datasets", default=None, metavar="FILE",
                     help="with --resident: an .npz with data[G][ndata] (optional uncert[G][ndata], seed[G]): G "
                          "independent retrievals in one resident loop, written to group_000/ ... (INTEGRATION.md, "
@@ -265,6 +277,13 @@ def main(argv=None):
                      "--native-sharded")
     elif a.grid_bands or a.grid_f32:
         ap.error("--grid-bands and --grid-f32 go with walk = unif")
+    if a.ess_exit and not a.ess_target > 0:
+        ap.error("--ess-exit stops at a target: name it with --ess-target N")
+    if a.ess_target < 0:
+        ap.error("--ess-target is a number of effective samples: > 0")
+    if a.ess_target > 0 and (not a.resident or a.datasets or unif):
+        ap.error("--ess-target is served by the resident loop of one retrieval: add --resident (not with --datasets "
+                 "or walk = unif)")
     if scfg.walk == "mrw" and not a.resident:
         ap.error("walk = mrw is served by the resident loop: add --resident")
     if scfg.chisqscale and not leastsq:
@@ -326,10 +345,11 @@ def main(argv=None):
             ap.error("leastsq / chisqscale run the native way: not with --python-loop, and on several ranks only with "
                      "--native-sharded")
         fitted = least_squares(w, scfg, a.fit_starts, log)
+    ess = dict(esstarget=a.ess_target, essexit=a.ess_exit)
     if a.resident and before is not None:
-        res = sampler.run_resident(w, scfg, log=log, first=int(before[1]["iterations"]), start=before[0][:, -1])
+        res = sampler.run_resident(w, scfg, log=log, first=int(before[1]["iterations"]), start=before[0][:, -1], **ess)
     elif a.resident:
-        res = sampler.run_resident(w, scfg, log=log)
+        res = sampler.run_resident(w, scfg, log=log, **ess)
     else:
         res = sampler.run_native(w, scfg, log=log) if native else sampler.run(w.step, scfg, log=log)
     dt = time.perf_counter() - t0

@@ -114,6 +114,30 @@ def gelman_rubin_dev(chain: np.ndarray, stepsize, r0: int = 0, r1: int | None = 
     return psrf, triples, bool(conv.value)
 
 
+def ess(chain: np.ndarray, stepsize, r0: int = 0, r1: int | None = None, maxlag: int = 0, target: float = 0.0):
+    """The resident loop's effective-sample-size test once on the device (``bartrt_mcmc_ess``; csrc/ess_core.hpp
+    states the lagged sums, their order and Geyer's initial positive sequence): chain [nchains, nkept, npars], rows
+    [r0, r1) of every chain, at most ``maxlag`` lags (0: 1024) -> (tau [nchains, npars] the integrated autocorrelation
+    times, ess [npars] = sum over the chains of n / tau, truncated [nchains, npars] (the sequence ran out at the last
+    lag), acf [nchains, npars, K + 1] the lagged sums S_k with K = min(maxlag, n - 1), reached: every free ess finite
+    and >= ``target`` and nothing truncated).  Zeros where ``stepsize <= 0``.  One chain is enough.  Needs no engine."""
+    from . import transit_module as trm
+    chain = np.ascontiguousarray(chain, np.double)
+    step = np.ascontiguousarray(stepsize, np.double)
+    nch, nkept, npars = chain.shape
+    if step.shape != (npars,):
+        raise ValueError("ess: stepsize has one value per parameter")
+    r1 = nkept if r1 is None else int(r1)
+    K = max(min(int(maxlag) if maxlag else 1024, r1 - int(r0) - 1), 0)
+    tau, stat, trunc = np.zeros((nch, npars)), np.zeros(npars), np.zeros((nch, npars), np.int32)
+    acf, reached = np.zeros((nch, npars, K + 1)), C.c_int(0)
+    ptr = lambda v: v.ctypes.data_as(C.c_void_p)
+    trm.check(trm.lib().bartrt_mcmc_ess(ptr(chain), nch, C.c_long(nkept), npars, ptr(step), C.c_long(int(r0)),
+                                        C.c_long(r1), C.c_long(int(maxlag)), float(target), ptr(tau), ptr(stat),
+                                        ptr(trunc), ptr(acf), C.cast(C.byref(reached), C.c_void_p)))
+    return tau, stat, trunc, acf, bool(reached.value)
+
+
 def _grexit_ignored(cfg, log, who):
     if cfg.grexit and log is not None:
         log("%s: grexit is honoured by run_resident alone; this loop runs all of numit" % who)
@@ -330,6 +354,13 @@ class McmcOpts(C.Structure):
                 ("walk", C.c_int)]
 
 
+class McmcOptsEss(McmcOpts):
+    """``bartrt_mcmc_opts`` with the fields appended after ``walk`` (the effective-sample-size tests).  The struct
+    carries its size: a caller that fills ``McmcOpts`` alone, with its size, leaves them zero."""
+    _fields_ = [("esstarget", C.c_double), ("essexit", C.c_int), ("maxlag", C.c_long), ("essstat", C.c_void_p),
+                ("esstau", C.c_void_p)]
+
+
 PROGRESS = C.CFUNCTYPE(None, C.c_long, C.c_long, C.c_void_p)
 WALK_MRW = 2    # bartrt_mcmc_opts.walk (include/bartrt.h: BARTRT_WALK_MRW)
 
@@ -344,7 +375,8 @@ def draws(seed: int, t: int, nchains: int, npars: int) -> np.ndarray:
     return out
 
 
-def run_resident(worker, cfg: SamplerConfig, log=None, block: int = 256, first: int = 0, start=None):
+def run_resident(worker, cfg: SamplerConfig, log=None, block: int = 256, first: int = 0, start=None,
+                 esstarget: float = 0.0, essexit: bool = False, maxlag: int = 0):
     """The sampler resident on the GPU through ``bartrt_mcmc_run_resident`` (csrc/mcmc.hip, csrc/mcmc_core.hpp):
     population, chi-squares and counters stay in device memory and an iteration is one small sampler launch plus the
     model's launches, enqueued without a host wait, ``block`` iterations at a time.  Its draws come from a
@@ -365,6 +397,13 @@ def run_resident(worker, cfg: SamplerConfig, log=None, block: int = 256, first: 
     total ceil(numit / nchains) with the draws of those iterations, so that the rows of both calls together are the
     bytes of one uninterrupted run.  The tests of a resumed call see that call's rows alone.
 
+    Effective sample size.  ``esstarget`` > 0: at every such test the integrated autocorrelation time of every chain
+    and free parameter and the effective sample size per free parameter are computed on the device as well
+    (csrc/ess_core.hpp; at most ``maxlag`` lags, 0: 1024), and with ``essexit`` the run stops at the first test at
+    which every free parameter has ``esstarget`` effective samples and no chain's sequence ran out at ``maxlag``
+    (together with ``cfg.grexit``: at the first test where both hold).  One chain is enough for these tests, so they
+    are made with ``walk = mrw`` and one chain, and with ``cfg.grtest`` off.
+
     Speed: SLOWER than :func:`run_native` as measured (MEASUREMENTS.md row 17; one MI355X, ten chains, snooker):
     7 745 against 9 045 iterations/s on the headline shape, 10 948 against 15 528 on the WASP-12b shape, 11 163
     against 14 896 on the demo shape -- the one-lane-per-chain sampler launch costs more than the host round trip it
@@ -376,7 +415,8 @@ def run_resident(worker, cfg: SamplerConfig, log=None, block: int = 256, first: 
     nkept = ceil(done / thinning)) plus ``models`` [nchains, nkept, ndata]: the band fluxes of each chain's current
     state at the kept iterations; ``done``: the iterations this call made; ``grhistory``: (when [ntests] global
     iteration counts, psrf [ntests, npars]); ``converged``: whether the last test made found convergence; ``accepted``: the proposals accepted in those
-    iterations."""
+    iterations; with ``esstarget``: ``essstat`` [ntests, npars] and ``esstau`` [ntests, nchains, npars] (None
+    without)."""
     from . import transit_module as trm
     if cfg.walk == "unif":
         raise ValueError("run_resident: walk = unif is not a chain: run_grid makes model grids")
@@ -393,14 +433,19 @@ def run_resident(worker, cfg: SamplerConfig, log=None, block: int = 256, first: 
     npars = len(par)
     ptr = lambda v: v.ctypes.data_as(C.c_void_p)
     grcheck = 0
-    if cfg.grtest and nch > 1:
+    esstarget = float(esstarget)
+    if esstarget < 0 or (essexit and not esstarget > 0):
+        raise ValueError("run_resident: esstarget is the effective samples asked of every free parameter: > 0 with "
+                         "essexit, 0 for no ESS tests")
+    if (cfg.grtest and nch > 1) or esstarget > 0:
         if cfg.grcheck:                      # a spacing of the caller's: no block is longer than it
             block = min(block, int(cfg.grcheck))
         block = -(-block // thin) * thin
         grcheck = int(cfg.grcheck) if cfg.grcheck else max(1, -(-nsteps // (10 * block))) * block
-    opts = McmcOpts(size=C.sizeof(McmcOpts), snooker=int(cfg.walk == "snooker"), seed=cfg.seed, thin=thin, block=block,
-                    burnin=int(cfg.burnin), grcheck=grcheck, grthreshold=float(cfg.grthreshold),
-                    grexit=int(bool(cfg.grexit)), first=first, walk=WALK_MRW if cfg.walk == "mrw" else 0)
+    opts = McmcOptsEss(size=C.sizeof(McmcOptsEss), snooker=int(cfg.walk == "snooker"), seed=cfg.seed, thin=thin,
+                       block=block, burnin=int(cfg.burnin), grcheck=grcheck, grthreshold=float(cfg.grthreshold),
+                       grexit=int(bool(cfg.grexit)), first=first, walk=WALK_MRW if cfg.walk == "mrw" else 0,
+                       esstarget=esstarget, essexit=int(bool(essexit)), maxlag=int(maxlag) if esstarget > 0 else 0)
     if pri is not None:
         opts.prior, opts.priorlow, opts.priorup = (v.ctypes.data for v in pri)
     if start is not None:
@@ -416,6 +461,9 @@ def run_resident(worker, cfg: SamplerConfig, log=None, block: int = 256, first: 
     made, done = C.c_int(0), C.c_long(0)
     opts.grstat, opts.grwhen, opts.ngr = grstat.ctypes.data, grwhen.ctypes.data, ngr
     opts.ngr_out, opts.done = C.addressof(made), C.addressof(done)
+    essstat, esstau = np.zeros((max(ngr, 1), npars)), np.zeros((max(ngr, 1), nch, npars))
+    if esstarget > 0:
+        opts.essstat, opts.esstau = essstat.ctypes.data, esstau.ctypes.data
     chain = np.zeros((nch, nkept, npars))
     chis = np.zeros((nch, nkept))
     models = np.zeros((nch, nkept, len(data)))
@@ -434,18 +482,31 @@ def run_resident(worker, cfg: SamplerConfig, log=None, block: int = 256, first: 
     free = step > 0
     last_ok = lambda r: bool(free.any() and np.all(np.isfinite(r[free])) and np.all(r[free] < cfg.grthreshold))
     converged = made.value > 0 and last_ok(psrf[-1])
+    if esstarget > 0:
+        essstat, esstau = essstat[:made.value].copy(), esstau[:made.value].copy()
+    else:
+        essstat = esstau = None
+    ess_line = lambda k: "Effective sample size after %d iterations: %s  (smallest: %.1f)" % (
+        when[k], " ".join("%.1f" % v for v in essstat[k][free]), essstat[k][free].min() if free.any() else 0.0)
     if log is not None:
         for k in range(made.value):
-            log("Gelman-Rubin after %d iterations: %s" % (when[k], " ".join("%.4f" % g for g in psrf[k][free])))
-            if last_ok(psrf[k]):
-                log("All parameters have converged to within %.3g%% of unity." % (100.0 * (cfg.grthreshold - 1.0)))
+            if nch > 1:                      # (one chain: the test was an ESS test alone)
+                log("Gelman-Rubin after %d iterations: %s" % (when[k], " ".join("%.4f" % g for g in psrf[k][free])))
+                if last_ok(psrf[k]):
+                    log("All parameters have converged to within %.3g%% of unity." % (100.0 * (cfg.grthreshold - 1.0)))
+            if essstat is not None:
+                log(ess_line(k))
         if done.value < nsteps:
-            log("grexit: stopped after %d of %d iterations" % (first + done.value, total))
+            log("%s: stopped after %d of %d iterations" % (
+                " and ".join(w for w, on in (("grexit", cfg.grexit), ("essexit", essexit)) if on),
+                first + done.value, total))
         log("%d iterations of %d chains; best chisq %.4f  acceptance %.2f" % (
             done.value, nch, float(chis.min()), nacc.value / (done.value * nch)))
+        if essstat is not None and made.value > 0:
+            log("At the end: " + ess_line(made.value - 1))
     return _result(chain, chis, nacc.value, done.value, nch, cfg, thin, burnin=max(0, cfg.burnin - first),
                    models=models, done=done.value, grhistory=(when, psrf), converged=converged,
-                   accepted=nacc.value)
+                   accepted=nacc.value, essstat=essstat, esstau=esstau)
 
 
 class McmcGroup(C.Structure):

@@ -83,6 +83,8 @@ def lib():
             L.bartrt_mcmc_run_resident.argtypes = [i, i, C.c_long, p, p, p, p, i, p, p, p, p, p, p, p, p]
             L.bartrt_mcmc_draws.argtypes = [C.c_ulonglong, C.c_ulonglong, i, i, p]
             L.bartrt_mcmc_gr.argtypes = [p, i, C.c_long, i, p, C.c_long, C.c_long, d, p, p, p]
+        if hasattr(L, "bartrt_mcmc_ess"):
+            L.bartrt_mcmc_ess.argtypes = [p, i, C.c_long, i, p, C.c_long, C.c_long, C.c_long, d, p, p, p, p, p]
         if hasattr(L, "bartrt_mcmc_run_resident_groups"):
             L.bartrt_mcmc_run_resident_groups.argtypes = [i, p, i, i, C.c_long, i, p, p, p, p, p, p, p]
         if hasattr(L, "bartrt_grid_run"):

@@ -329,7 +329,23 @@ int bartrt_mcmc_run(int nchains, int npars, long nsteps, const double *params, c
  * no partner chain is drawn, no rule of the move reads the iteration, and one chain is enough.  Box, shared
  * parameters, priors, thinning, models, the convergence tests and resume are as above.  walk = BARTRT_WALK_UNIF (3;
  * MC3's `walk = unif`) is not a chain: BARTRT_EINVAL here, bartrt_grid_run serves it.  Any other value:
- * BARTRT_EINVAL. */
+ * BARTRT_EINVAL.
+ *
+ * EFFECTIVE SAMPLE SIZE.  esstarget > 0: at every place where a convergence test runs -- every grcheck iterations and
+ * after the last one, on the rows of global iterations >= burnin, enqueued behind the block that ends there -- the
+ * integrated autocorrelation time tau of every chain and free parameter and the effective sample size ess_j = sum
+ * over the chains of n / tau_ij are computed ON THE DEVICE as well (bart_amd/csrc/ess_core.hpp states the lagged sums,
+ * their fixed order and Geyer's initial positive sequence; maxlag lags at most, 0 reads as 1024, more than 4096 is
+ * BARTRT_EINVAL).  esstarget > 0 with grcheck == 0 is BARTRT_EINVAL.  One chain is enough for these tests: with them a
+ * test is made wherever four rows lie past the burn-in, and where there is one chain grstat[k] is zeros.  Test k is
+ * recorded in essstat[k][npars] (0 for parameters that are not free) and esstau[k][nchains][npars] while k < ngr.
+ * The target is REACHED when there is a free parameter, every free ess_j is finite and >= esstarget, and no chain's
+ * sequence of a free parameter ran out at maxlag before it turned non-positive.  The call stops at the first test at
+ * which every requested exit holds: grexit -- converged; essexit -- reached; both set -- both at the same test.
+ * *done, the shape of the arrays, the discarded blocks and the independence from timing are as for grexit; a resumed
+ * call's tests see its own rows alone; sharded engines in lockstep take the same decision, since the test reads the
+ * chain alone.  esstarget == 0: no ESS work at all, and essexit, essstat and esstau must be unset.
+ * bartrt_mcmc_run_resident_groups does not serve these fields: any of them set there is BARTRT_EINVAL naming them. */
 enum { BARTRT_WALK_MRW = 2, BARTRT_WALK_UNIF = 3 };
 typedef struct bartrt_mcmc_opts {
   unsigned long size;                 /* sizeof(bartrt_mcmc_opts) of the caller */
@@ -352,6 +368,11 @@ typedef struct bartrt_mcmc_opts {
   const double *start;                /* resume: [nchains][npars] */
   long *done;                         /* iterations of this call the result holds, may be NULL */
   int walk;                           /* 0: as `snooker` says; 2: mrw (BARTRT_WALK_MRW) */
+  double esstarget;                   /* effective samples per free parameter; 0: no ESS work at all */
+  int essexit;                        /* stop at the first test that reaches esstarget */
+  long maxlag;                        /* lags of the autocorrelation; 0 reads as 1024, at most 4096 */
+  double *essstat;                    /* [ngr][npars], may be NULL */
+  double *esstau;                     /* [ngr][nchains][npars], may be NULL */
 } bartrt_mcmc_opts;
 int bartrt_mcmc_run_resident(int nchains, int npars, long nsteps, const double *params, const double *pmin,
                              const double *pmax, const double *stepsize, int ndata, const double *data,
@@ -369,7 +390,9 @@ int bartrt_mcmc_run_resident(int nchains, int npars, long nsteps, const double *
  *   chain[ngroups][nchains][nkept][npars], chisq[ngroups][nchains][nkept], models (may be NULL)
  *   [ngroups][nchains][nkept][ndata]; naccept[ngroups], nbad[ngroups][4], converged_at[ngroups] (each may be NULL).
  * Set size = sizeof(bartrt_mcmc_group) in EVERY group (fields past `size` read as zero).  opts as above, except that
- * opts->seed, prior, priorlow, priorup and start must be unset (BARTRT_EINVAL): they live in the groups.  Limits:
+ * opts->seed, prior, priorlow, priorup and start must be unset (BARTRT_EINVAL): they live in the groups, and that
+ * esstarget, essexit, maxlag, essstat and esstau must be unset (BARTRT_EINVAL naming them): the effective-sample-size
+ * tests are the single call's.  Limits:
  * ngroups >= 1, nchains >= 1 and ngroups x nchains <= 1024, 64 parameters (BARTRT_EINVAL beyond).  What the single
  * call refuses about a problem is refused here with the group named: "mcmc_run_resident_groups: group 2: stepsize[6] =
  * -7 ...".  walk = BARTRT_WALK_UNIF: BARTRT_EINVAL.
@@ -407,6 +430,16 @@ int bartrt_mcmc_draws(unsigned long long seed, unsigned long long t, int nchains
  * most 64 parameters.  Needs no engine. */
 int bartrt_mcmc_gr(const double *chain, int nchains, long nkept, int npars, const double *stepsize, long r0, long r1,
                    double threshold, double *psrf, double *triples, int *converged);
+/* Diagnostics: the resident loop's effective-sample-size test once ON THE DEVICE, by its own kernels, on a host
+ * chain[nchains][nkept][npars], rows [r0, r1) of every chain, n = r1 - r0, K = min(maxlag, n - 1) (maxlag 0 reads as
+ * 1024; more than 4096: BARTRT_EINVAL): tau[nchains][npars] the integrated autocorrelation times, ess[npars],
+ * truncated[nchains][npars] (1: the sequence ran out at K), acf (may be NULL) [nchains][npars][K + 1] the lagged sums
+ * S_k = sum_r (x_r - mean)(x_{r+k} - mean), *reached as bartrt_mcmc_run_resident decides it.  Zeros for parameters
+ * that are not free (stepsize[j] <= 0).  Fewer than four rows: no test, every output zero.  One chain is enough.  The
+ * bits are those of a host build of bart_amd/csrc/ess_core.hpp.  At most 64 parameters.  Needs no engine. */
+int bartrt_mcmc_ess(const double *chain, int nchains, long nkept, int npars, const double *stepsize, long r0, long r1,
+                    long maxlag, double esstarget, double *tau, double *ess, int *truncated,
+                    double *acf /* NULL */, int *reached);
 /* MODEL GRIDS (MC3's `walk = unif`, the reference's way to the training sets of surrogate models,
  * code/makecfg.py:177-190): nsteps iterations of nrows parameter vectors drawn uniformly in [pmin, pmax], each
  * evaluated by the batched model and handed to the caller WITH ITS WHOLE MODEL ROW.  No data, no chi-square, no
