@@ -225,9 +225,33 @@ def _sharding(shard, group):
     return (dist.get_rank(group), ngpu)
 
 
-def _run_samples(cfg, samples, filters, kind, chunk, shard=None, device=None, group=None):
+def _device_envelopes(samples, win, kind, chunk):
+    """The band curves of the samples kept in HBM as one [n, nfilters L] matrix, and their envelopes from order
+    statistics selected there (engine.percentiles_dev) under the mask status == 0.  -> (band, status, envelopes): the
+    host copies of the curves and flags, and the dict of median / lo1 / hi1 / lo2 / hi2 [nfilters, L]."""
+    import torch
+    from . import engine
+    nf, L, n = engine.cf_setup(win), engine.nlayers(), len(samples)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    band = torch.empty((n, nf * L), dtype=torch.float64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    call = engine.contribution_from_params_dev if kind == "contribution" else engine.transmittance_from_params_dev
+    for off in range(0, n, chunk):
+        p = torch.from_numpy(np.ascontiguousarray(samples[off:off + chunk])).to(dev)
+        b, st = call(p)
+        band[off:off + len(p)] = b.reshape(len(p), nf * L)
+        status[off:off + len(p)] = st
+    ok = (status == 0).to(torch.uint8)
+    levels = {"median": 50.0, **PERCENTILES}
+    vals, _, _ = engine.percentiles_dev(band, list(levels.values()), ok)
+    env = {k: vals[i].reshape(nf, L) for i, k in enumerate(levels)}
+    return band.cpu().numpy().reshape(n, nf, L), status.cpu().numpy(), env
+
+
+def _run_samples(cfg, samples, filters, kind, chunk, shard=None, device=None, group=None, envelopes="host"):
     """Worker, step and CF set up from the [MCMC] configuration as BARTfunc.Worker does; the samples in chunks.
-    -> (band [nsamples, nfilters, L], status [nsamples], kind).  ``shard`` (rank, count) with count > 1: the engine
+    -> (band [nsamples, nfilters, L], status [nsamples], kind); with ``envelopes`` = "device" (band, status, the
+    envelopes' dict, kind: _device_envelopes).  ``shard`` (rank, count) with count > 1: the engine
     holds its wavenumber block, the library's communicator is attached over ``group`` (engine.comm_init) and every
     rank, making the same calls, gets the same rows."""
     from . import BARTfunc, engine
@@ -241,6 +265,8 @@ def _run_samples(cfg, samples, filters, kind, chunk, shard=None, device=None, gr
         if shard is not None and shard[1] > 1:
             engine.comm_init(group)
         win = filter_windows(w.specwn, list(filters if filters is not None else wcfg.filters))
+        if envelopes == "device":
+            return _device_envelopes(samples, win, kind, chunk) + (kind,)
         bands, stats = [], []
         for off in range(0, len(samples), chunk):
             p = samples[off:off + chunk]
@@ -256,7 +282,7 @@ def _run_samples(cfg, samples, filters, kind, chunk, shard=None, device=None, gr
 
 
 def posterior(output_npy, cfg, filters, burnin, thinning=1, kind=None, chunk=4096, layout=None, shard=None,
-              device=None, group=None):
+              device=None, group=None, envelopes="host"):
     """The band-averaged contribution functions or transmittance of every sample of an MCMC posterior, and their
     envelopes: what bestFit.callTransit (code/bestFit.py:429-525) draws beside the T(p) envelopes, for the whole
     posterior instead of the best fit.  ``output_npy``: the output.npy of MC3 or of bart_amd.retrieve (a path or the
@@ -271,12 +297,26 @@ def posterior(output_npy, cfg, filters, burnin, thinning=1, kind=None, chunk=409
     bestFit.py:461-465; NaN when no sample was accepted).  No plots.
     ``shard`` = (rank, count), ``device``, ``group``: the sharding BARTfunc.Worker and engine.init take (or
     BARTRT_GPUS = G over a torch process group of G ranks) -- each rank's engine holds one wavenumber block, every
-    rank calls posterior with the same arguments and returns the same curves and envelopes."""
+    rank calls posterior with the same arguments and returns the same curves and envelopes.
+    ``envelopes``: 'host' (default) takes them with np.percentile on the host copy of the curves; 'device' keeps the
+    curves in HBM as one [n, nfilters L] matrix and interpolates the envelopes from exact order statistics selected
+    there (engine.percentiles_dev; csrc/quant_core.hpp) -- the same keys, ``band`` and ``status`` the same bits, the
+    envelopes np.percentile's values (the same rule and expression).  'device' is not served on sharded engines
+    (NotImplementedError)."""
+    if envelopes not in ("host", "device"):
+        raise ValueError("posterior: envelopes is 'host' or 'device'")
     params, stepsize = _mcmc_vectors(cfg)
     data = np.load(output_npy) if isinstance(output_npy, (str, bytes, os.PathLike)) else output_npy
     samples = posterior_samples(data, params, stepsize, burnin, thinning, layout)
     shard = _sharding(shard, group)
     extra = {} if shard is None and device is None else {"shard": shard, "device": device, "group": group}
+    if envelopes == "device":
+        if shard is not None and shard[1] > 1:
+            raise NotImplementedError("posterior: envelopes='device' is not served on sharded engines; "
+                                      "envelopes='host' is")
+        band, status, env, kind = _run_samples(cfg, samples, filters, kind, max(1, int(chunk)), envelopes="device",
+                                               **extra)
+        return {"samples": samples, "band": band, "status": status, "kind": kind, **env}
     band, status, kind = _run_samples(cfg, samples, filters, kind, max(1, int(chunk)), **extra)
     out = {"samples": samples, "band": band, "status": status, "kind": kind}
     good = band[status == 0]

@@ -8,6 +8,7 @@
 #include "contrib.hpp"
 #include "engine.hpp"
 #include "lbl.hpp"
+#include "quant.hpp"
 #include "share.hpp"
 #include "step.hpp"
 #include "rt_launch.hpp"
@@ -921,6 +922,123 @@ int bartrt_cf_params(const double *params, int nwalkers, int npars, int kind, do
 int bartrt_cf_params_dev(const double *d_params, int nwalkers, int npars, int kind, double *d_band, double *d_full,
                          int *d_status, void *stream) {
   return cf_call("cf_params_dev", cf_params(d_params, nwalkers, npars, kind, d_band, d_full, d_status, false, stream));
+}
+
+// ---- order statistics and posterior envelopes (quant.hip) ----------------
+// the arguments both forms of the selection refuse, each named
+static int colselect_check(const char *who, const void *x, long nrows, int ncols, long ld, int nranks,
+                           const long *ranks, const void *out) {
+  const std::string pre = std::string(who) + ": ";
+  if (!x || !ranks || !out) return fail(BARTRT_EINVAL, pre + "null buffer");
+  if (nranks < 1 || nranks > quant::kMaxRanks)
+    return fail(BARTRT_EINVAL, pre + "nranks = " + std::to_string(nranks) + " is outside 1.." + std::to_string(quant::kMaxRanks));
+  if (nrows < 1 || nrows > kQuantMaxRows)
+    return fail(BARTRT_EINVAL, pre + "nrows = " + std::to_string(nrows) + " is outside 1.." + std::to_string(kQuantMaxRows));
+  if (ncols < 0 || ncols > kQuantMaxCols)
+    return fail(BARTRT_EINVAL, pre + "ncols = " + std::to_string(ncols) + " is outside 0.." + std::to_string(kQuantMaxCols));
+  if (ld < ncols) return fail(BARTRT_EINVAL, pre + "ld = " + std::to_string(ld) + " is below ncols = " + std::to_string(ncols));
+  for (int r = 0; r < nranks; r++)
+    if (ranks[r] < 0)
+      return fail(BARTRT_EINVAL, pre + "ranks[" + std::to_string(r) + "] = " + std::to_string(ranks[r]) + " is negative");
+  return BARTRT_OK;
+}
+
+int bartrt_colselect_dev(const double *d_x, long nrows, int ncols, long ld, const unsigned char *d_ok, int nranks,
+                         const long *ranks, double *d_out, void *stream) {
+  NEED_ENGINE();
+  if (int rc = colselect_check("colselect_dev", d_x, nrows, ncols, ld, nranks, ranks, d_out)) return rc;
+  return guarded([&] {
+    colselect_dev(*g_eng, d_x, nrows, ncols, ld, d_ok, nranks, ranks, d_out, stream_of(stream));
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_colselect(const double *x, long nrows, int ncols, long ld, const unsigned char *ok, int nranks,
+                     const long *ranks, double *out) {
+  NEED_ENGINE();
+  if (int rc = colselect_check("colselect", x, nrows, ncols, ld, nranks, ranks, out)) return rc;
+  long count = nrows;
+  if (ok) {
+    count = 0;
+    for (long r = 0; r < nrows; r++) count += ok[r] != 0;
+  }
+  if (count == 0) return fail(BARTRT_EINVAL, "colselect: ok leaves no row");
+  for (int r = 0; r < nranks; r++)
+    if (ranks[r] >= count)
+      return fail(BARTRT_EINVAL, "colselect: ranks[" + std::to_string(r) + "] = " + std::to_string(ranks[r]) +
+                                     " is not below the " + std::to_string(count) + " rows that count");
+  if (ncols == 0) return BARTRT_OK;
+  return guarded([&] {
+    colselect_host(*g_eng, x, nrows, ncols, ld, ok, nranks, ranks, out);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_colselect_slab(long *rows) {
+  if (!rows) return fail(BARTRT_EINVAL, "colselect_slab: null buffer");
+  *rows = g_eng ? colselect_slab(*g_eng) : kQuantSlabRows;
+  return BARTRT_OK;
+}
+
+int bartrt_colselect_set_slab(long rows) {
+  NEED_ENGINE();
+  return guarded([&] {
+    colselect_set_slab(*g_eng, rows);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_posterior_tp(const double *params, long nsamples, int npars, int nq, const double *q, double *env,
+                        int *status, long *ngood) {
+  NEED_ENGINE();
+  Engine *e = g_eng;
+  if (!e->step) return fail(BARTRT_EINVAL, "posterior_tp: call bartrt_step_setup first");
+  if (!params || !q || !env || !status || !ngood) return fail(BARTRT_EINVAL, "posterior_tp: null buffer");
+  if (nsamples < 1 || nsamples > kQuantMaxRows)
+    return fail(BARTRT_EINVAL, "posterior_tp: nsamples = " + std::to_string(nsamples) + " is outside 1.." + std::to_string(kQuantMaxRows));
+  if (nq < 1 || nq > quant::kMaxPercents)
+    return fail(BARTRT_EINVAL, "posterior_tp: nq = " + std::to_string(nq) + " is outside 1.." + std::to_string(quant::kMaxPercents));
+  for (int i = 0; i < nq; i++)
+    if (!(q[i] >= 0.0 && q[i] <= 100.0))
+      return fail(BARTRT_EINVAL, "posterior_tp: q[" + std::to_string(i) + "] = " + std::to_string(q[i]) + " is outside 0..100");
+  if (npars != step_npars(*e))
+    return fail(BARTRT_EINVAL, "posterior_tp: npars must be nPT + (radius, cloud top, scattering parameters declared with "
+                               "step_set_extras) + nmolfit");
+  return guarded([&] {
+    posterior_tp(*e, params, nsamples, npars, nq, q, env, status, ngood);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_posterior_set_chunk(long rows) {
+  NEED_ENGINE();
+  return guarded([&] {
+    posterior_set_chunk(*g_eng, rows);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_posterior_tp_order(int nq, int nlayers, long *ranks, double *order) {
+  NEED_ENGINE();
+  if (!ranks || !order) return fail(BARTRT_EINVAL, "posterior_tp_order: null buffer");
+  if (!posterior_tp_order(*g_eng, nq, nlayers, ranks, order))
+    return fail(BARTRT_EINVAL, "posterior_tp_order: no envelope of that shape (no bartrt_posterior_tp yet, no accepted "
+                               "sample, or another nq / nlayers)");
+  return BARTRT_OK;
+}
+
+int bartrt_percentile_rule(long n, double q, long *lo, long *hi, double *w) {
+  if (!lo || !hi || !w) return fail(BARTRT_EINVAL, "percentile_rule: null buffer");
+  if (n < 1) return fail(BARTRT_EINVAL, "percentile_rule: n = " + std::to_string(n) + " is below 1");
+  if (!(q >= 0.0 && q <= 100.0)) return fail(BARTRT_EINVAL, "percentile_rule: q = " + std::to_string(q) + " is outside 0..100");
+  quant::percentile_rule(n, q, lo, hi, w);
+  return BARTRT_OK;
+}
+
+int bartrt_percentile_lerp(const double *a, const double *b, double w, double *out, long n) {
+  if (!a || !b || !out) return fail(BARTRT_EINVAL, "percentile_lerp: null buffer");
+  for (long i = 0; i < n; i++) out[i] = quant::interpolate(a[i], b[i], w);
+  return BARTRT_OK;
 }
 
 // ---- per-step converters (step.hip) ------------------------------------

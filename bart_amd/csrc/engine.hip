@@ -5,6 +5,7 @@
 #include "lds.hpp"
 #include "prep.hpp"
 #include "contrib.hpp"
+#include "quant.hpp"
 #include "share.hpp"
 #include "step.hpp"
 #include "svc.hpp"
@@ -31,6 +32,7 @@ Engine::~Engine() {
   delete step;
   delete lbl;
   cf_release(*this);
+  quant_release(*this);
   if (kappa_share) { kappa_share->release(); kappa_share = nullptr; }
 }
 

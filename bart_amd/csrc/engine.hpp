@@ -29,6 +29,7 @@ struct StepArgs;  // converters around the engine (step.hip)
 struct Lbl;       // line-by-line extinction (lbl.hip)
 struct Comm;      // the ranks' communicator (comm.hpp)
 struct CfState;   // contribution-function tables and workspaces (contrib.hip)
+struct QuantState;  // scratch of the order statistics and the posterior envelope (quant.hip)
 
 // The stream and the timing events, as a base of Engine: a base outlives the members, so every buffer the engine
 // owns (DevBuf / PinBuf members, freed by their own destructors) goes before the events, and the stream goes last.
@@ -231,6 +232,8 @@ struct Engine : EngineStream {
   // destroyed by capi.hip (bartrt_comm_free, bartrt_free_memory, a re-bartrt_init) before the engine goes.
   Comm *comm = nullptr;
   unsigned long long ncollectives = 0;  // collectives this engine has issued (kept across bartrt_comm_free)
+
+  QuantState *quant = nullptr;  // owned, null until a selection call (quant_release)
 };
 
 }  // namespace bartrt

@@ -772,3 +772,131 @@ def contribution_from_params_dev(d_params, full=False, stream=None):
 def transmittance_from_params_dev(d_params, full=False, stream=None):
     """Device form of transmittance_from_params, as contribution_from_params_dev."""
     return _cf_params_dev(d_params, CF_TRANSMIT, full, stream)
+
+
+# ---- exact order statistics and posterior envelopes (include/bartrt.h, bartrt_colselect) ----------------
+def colselect_slab() -> int:
+    """The rows of a column one workgroup of the selection owns (tests place their shapes around it)."""
+    rows = C.c_long()
+    _check(trm.lib().bartrt_colselect_slab(C.byref(rows)))
+    return rows.value
+
+
+def colselect_set_slab(rows: int) -> None:
+    """Another slab size (0: the default).  For tests: results do not depend on it."""
+    _check(trm.lib().bartrt_colselect_set_slab(int(rows)))
+
+
+def _row_stride(shape, strides, itemsize):
+    """ld of a two-dimensional array whose rows are contiguous (a padded view is taken as it lies)."""
+    if len(shape) != 2 or (shape[1] > 1 and strides[1] != itemsize) or strides[0] % itemsize or strides[0] < 0:
+        return None
+    ld = strides[0] // itemsize
+    return ld if (ld >= shape[1] or shape[0] == 1) else None
+
+
+def colselect(x, ranks, ok=None, stream=None):
+    """Order statistics of the columns of x [nrows, ncols]: -> [nranks, ncols], row r the values
+    np.sort(x[ok], axis=0)[ranks[r]] has, bit for bit.  ``x``: a float64 numpy array (host form: a rank at or above
+    the rows that count raises) or a float64 CUDA tensor (device form, asynchronous on torch's current stream: such a
+    rank gives NaN).  Rows may be padded (a view x[:, :ncols] of a wider array is read in place).  ``ok`` [nrows]:
+    rows with 0 do not exist.  At most 16 ranks, any order, duplicates allowed."""
+    r = np.ascontiguousarray(ranks, np.int64).ravel()
+    if isinstance(x, np.ndarray):
+        if x.dtype != np.double or x.ndim != 2:
+            x = np.ascontiguousarray(x, np.double)
+            x = x.reshape(-1, x.shape[-1]) if x.ndim != 2 else x
+        ld = _row_stride(x.shape, x.strides, 8)
+        if ld is None:
+            x = np.ascontiguousarray(x)
+            ld = x.shape[1]
+        ld = max(ld, x.shape[1])
+        m = None if ok is None else np.ascontiguousarray(np.asarray(ok) != 0, np.uint8)
+        if m is not None and m.shape != (x.shape[0],):
+            raise ValueError("colselect: ok must have one entry per row")
+        out = np.zeros((r.size, x.shape[1]))
+        _check(trm.lib().bartrt_colselect(C.c_void_p(x.ctypes.data), x.shape[0], x.shape[1], ld,
+                                          _ptr(m) if m is not None else None, r.size, _ptr(r), _ptr(out)))
+        return out
+    import torch
+    assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2
+    ld = _row_stride(tuple(x.shape), tuple(s * 8 for s in x.stride()), 8)
+    if ld is None:
+        x = x.contiguous()
+        ld = x.shape[1]
+    ld = max(ld, x.shape[1])
+    if ok is not None:
+        assert ok.is_cuda and ok.dtype == torch.uint8 and ok.is_contiguous() and ok.shape == (x.shape[0],)
+    out = torch.empty((r.size, x.shape[1]), dtype=torch.float64, device=x.device)
+    _check(trm.lib().bartrt_colselect_dev(C.c_void_p(x.data_ptr()), x.shape[0], x.shape[1], ld,
+                                          C.c_void_p(ok.data_ptr()) if ok is not None else None, r.size, _ptr(r),
+                                          C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
+    return out
+
+
+def percentile_rule(n: int, q: float):
+    """np.percentile's default linear rule for n sorted values: -> (lo, hi, w), the two neighbouring ranks and the
+    weight (csrc/quant_core.hpp)."""
+    lo, hi, w = C.c_long(), C.c_long(), C.c_double()
+    _check(trm.lib().bartrt_percentile_rule(int(n), float(q), C.byref(lo), C.byref(hi), C.byref(w)))
+    return lo.value, hi.value, w.value
+
+
+def percentile_lerp(a, b, w: float) -> np.ndarray:
+    """The value between the order statistics a (rank lo) and b (rank hi) at weight w, elementwise."""
+    a, b = np.ascontiguousarray(a, np.double), np.ascontiguousarray(b, np.double)
+    out = np.empty_like(a)
+    _check(trm.lib().bartrt_percentile_lerp(_ptr(a), _ptr(b), float(w), _ptr(out), a.size))
+    return out
+
+
+def percentiles_dev(d_x, q, d_ok=None, count=None):
+    """Percentiles q (at most 8) of every column of the CUDA tensor d_x [nrows, ncols] over the rows d_ok (uint8
+    tensor) lets count: two order statistics per percent selected on the device (colselect), interpolated by
+    percentile_lerp.  ``count``: the rows that count, when the caller knows it (else read from d_ok).
+    -> (values [nq, ncols], order [2 nq, ncols], ranks [2 nq]) numpy arrays; NaN values when no row counts."""
+    q = [float(v) for v in np.atleast_1d(q)]
+    ncols = d_x.shape[1]
+    if count is None:
+        count = d_x.shape[0] if d_ok is None else int(d_ok.count_nonzero().item())
+    if count == 0:
+        return np.full((len(q), ncols), np.nan), np.full((2 * len(q), ncols), np.nan), np.zeros(2 * len(q), np.int64)
+    rules = [percentile_rule(count, v) for v in q]
+    ranks = np.array([k for lo, hi, _ in rules for k in (lo, hi)], np.int64)
+    order = colselect(d_x, ranks, d_ok).cpu().numpy()
+    vals = np.stack([percentile_lerp(order[2 * i], order[2 * i + 1], rules[i][2]) for i in range(len(q))])
+    return vals, order, ranks
+
+
+def posterior_set_chunk(rows: int) -> None:
+    """Rows per chunk of posterior_tp (0: the default).  The envelope does not depend on it."""
+    _check(trm.lib().bartrt_posterior_set_chunk(int(rows)))
+
+
+def posterior_tp(params, q, chunk=None, want_order=False):
+    """The percentile envelope of the temperature profiles of parameter vectors [nsamples, npars] as step_batch takes
+    them (after step_setup; include/bartrt.h, bartrt_posterior_tp): -> (env [nq, L] in atm layer order, status
+    [nsamples], ngood); with ``want_order`` also (ranks [2 nq], order [2 nq, L]), the order statistics behind the
+    envelope (None, None when no sample was accepted).  At most 8 percents.  ``chunk``: rows per conversion launch."""
+    p = np.ascontiguousarray(params, np.double)
+    p = p.reshape(-1, p.shape[-1])
+    qs = np.ascontiguousarray(np.atleast_1d(q), np.double)
+    L = nlayers()
+    env = np.zeros((qs.size, L))
+    status = np.zeros(p.shape[0], np.int32)
+    ngood = C.c_long()
+    if chunk is not None:
+        posterior_set_chunk(chunk)
+    try:
+        _check(trm.lib().bartrt_posterior_tp(_ptr(p), p.shape[0], p.shape[1], qs.size, _ptr(qs), _ptr(env),
+                                             _ptr(status), C.byref(ngood)))
+    finally:
+        if chunk is not None:
+            posterior_set_chunk(0)
+    if not want_order:
+        return env, status, ngood.value
+    if ngood.value == 0:
+        return env, status, 0, None, None
+    ranks, order = np.zeros(2 * qs.size, np.int64), np.zeros((2 * qs.size, L))
+    _check(trm.lib().bartrt_posterior_tp_order(qs.size, L, _ptr(ranks), _ptr(order)))
+    return env, status, ngood.value, ranks, order

@@ -239,6 +239,10 @@ def main(argv=None):
     ap.add_argument("--grid-bands", action="store_true",
                     help="with walk = unif: keep the band fluxes of every model instead of its whole spectrum")
     ap.add_argument("--grid-f32", action="store_true", help="with walk = unif: write the models as float")
+    ap.add_argument("--tp-envelopes", action="store_true",
+                    help="after the run (after --resume: on the whole chain) write tp_envelopes.npz beside output.npy: "
+                         "the median and the 1- and 2-sigma percentiles of T(p) over the rows past the burn-in "
+                         "(bart_amd.posterior; not with walk = unif or --datasets)")
     a = ap.parse_args(argv)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -277,6 +281,8 @@ def main(argv=None):
                      "--native-sharded")
     elif a.grid_bands or a.grid_f32:
         ap.error("--grid-bands and --grid-f32 go with walk = unif")
+    if a.tp_envelopes and (unif or a.datasets):
+        ap.error("--tp-envelopes is the envelope of one retrieval's chain: not with walk = unif or --datasets")
     if a.ess_exit and not a.ess_target > 0:
         ap.error("--ess-exit stops at a target: name it with --ess-target N")
     if a.ess_target < 0:
@@ -393,6 +399,17 @@ def main(argv=None):
             np.save(name, models)
         with open(os.path.join(out, "MCMC.log"), "a" if before is not None else "w") as f:
             f.write("\n".join(lines) + "\n")
+    if a.tp_envelopes:
+        # the whole chain's rows past the burn-in (after --resume: both calls'), on the engine the run used; the T(p)
+        # model needs no spectrum, so every rank computes the same curves and rank 0 writes them
+        from . import cf, posterior
+        thin = max(1, int(scfg.thinning)) if a.resident else 1
+        rows = min(int(scfg.burnin) // thin, res["chain"].shape[1] - 1)
+        samples = cf.posterior_samples(res["chain"], scfg.params, scfg.stepsize, rows, layout="retrieve")
+        env = dict(posterior.envelopes_of_samples(samples), burnin=rows)
+        if rank == 0:
+            posterior.save(os.path.join(out, "tp_envelopes.npz"), env)
+        res["tp_envelopes"] = env
     if fitted is not None:
         res["fit"] = fitted
     w.close()

@@ -145,6 +145,15 @@ def lib():
         L.bartrt_cf_setup_block.argtypes = [i, p, p, p]
         L.bartrt_cf_partials_dev.argtypes = [p, i, i, p, p, p, p, p]
         L.bartrt_cf_combine_dev.argtypes = [p, i, i, p, p, p]
+        L.bartrt_colselect_dev.argtypes = [p, C.c_long, i, C.c_long, p, i, p, p, p]
+        L.bartrt_colselect.argtypes = [p, C.c_long, i, C.c_long, p, i, p, p]
+        L.bartrt_colselect_slab.argtypes = [C.POINTER(C.c_long)]
+        L.bartrt_colselect_set_slab.argtypes = [C.c_long]
+        L.bartrt_posterior_tp.argtypes = [p, C.c_long, i, i, p, p, p, C.POINTER(C.c_long)]
+        L.bartrt_posterior_set_chunk.argtypes = [C.c_long]
+        L.bartrt_posterior_tp_order.argtypes = [i, i, p, p]
+        L.bartrt_percentile_rule.argtypes = [C.c_long, d, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(d)]
+        L.bartrt_percentile_lerp.argtypes = [p, p, d, p, C.c_long]
         L.bartrt_algorithmic_bytes.argtypes = [i]
         L.bartrt_algorithmic_bytes.restype = d
         _lib = L

@@ -767,6 +767,56 @@ int bartrt_cf_partials_dev(const double *d_prof, int nwalkers, int kind, const d
 int bartrt_cf_combine_dev(const double *d_slots, int nranks, int nwalkers, const unsigned char *d_ok,
                           double *d_band, void *stream);
 
+/* ---- exact order statistics, posterior envelopes (csrc/quant.hip, csrc/quant_core.hpp) ----
+ * bartrt_colselect_dev: order statistics of the columns of a row-major matrix in device memory.
+ *   d_x[nrows][ld]   doubles, of which the first ncols <= ld columns of every row are read
+ *   d_ok[nrows]      or NULL: rows with 0 do not exist for the selection
+ *   ranks[nranks]    HOST array, 1 <= nranks <= 16, zero-based ranks among the rows that count; any order,
+ *                    duplicates allowed
+ *   d_out[nranks][ncols]  out[r][c] is the value np.sort(x[ok, c])[ranks[r]] has, bit for bit: the values are
+ *                    selected (a radix select on order-preserving 64-bit keys), not computed.  NaNs of
+ *                    either sign sort behind +inf and come back with a clear sign bit; -0 sorts before +0.
+ * Asynchronous on `stream` (NULL: the engine's own).  The counts are integers added by atomics: the result
+ * depends on no launch shape.  It needs an initialised engine for the stream and the scratch buffers, and
+ * nothing else from it (any geometry, sharded or not, line-by-line or not).
+ *   BARTRT_EINVAL    nranks outside 1..16, a negative rank, ld < ncols, nrows < 1 (or above 2^31 - 1),
+ *                    ncols < 0 or above 65535 * 64, a NULL buffer; the message names the argument.
+ *   rank too large   the _dev form cannot look at the mask: for a rank at or above the number of rows that count
+ *                    it writes NaN into that rank's row of d_out and reports nothing (as
+ *                    bartrt_cf_batch_over_dev flags a walker instead of failing).  The host form
+ *                    bartrt_colselect (host buffers, the engine's stream, waits) counts the rows first and
+ *                    refuses such a rank, and a mask without a row, with BARTRT_EINVAL.
+ * bartrt_colselect_slab: *rows = what one workgroup owns of a column (the default, or what
+ * bartrt_colselect_set_slab set; 0 restores the default).  For tests: results do not depend on it.
+ *
+ * bartrt_posterior_tp: the percentile envelope of the temperature profiles of a posterior (reference
+ * code/bestFit.py:429-466), after bartrt_step_setup.
+ *   params[nsamples][npars]  HOST, rows as bartrt_step_batch takes them; they go through the kernels of
+ *                    bartrt_step_profiles_dev in chunks (bartrt_posterior_set_chunk rows, 0: the default;
+ *                    the result does not depend on it) and their temperature rows stay on the device
+ *   q[nq]            1 <= nq <= 8 percents in [0, 100]
+ *   env[nq][L]       HOST: percentile q[i] of every layer (atm order) over the accepted samples (status 0),
+ *                    by np.percentile's default linear rule from the two neighbouring order statistics
+ *   status[nsamples] 0, 1 (temperature), 2 (abundance) as bartrt_cf_params reports it; bartrt_step_set_carry
+ *                    has no effect here either
+ *   *ngood           the accepted samples.  None accepted: env is NaN, *ngood = 0, and the call succeeds.
+ * bartrt_posterior_tp_order: the order statistics behind the latest envelope, ranks[2 nq] (lo, hi of each
+ * percent) and order[2 nq][L]; BARTRT_EINVAL when there is none of that shape.
+ * bartrt_percentile_rule / bartrt_percentile_lerp need no engine: the rule's two ranks and weight for n values
+ * and percent q, and out[i] = the value between a[i] (rank lo) and b[i] (rank hi) at weight w. */
+int bartrt_colselect_dev(const double *d_x, long nrows, int ncols, long ld, const unsigned char *d_ok,
+                         int nranks, const long *ranks, double *d_out, void *stream);
+int bartrt_colselect(const double *x, long nrows, int ncols, long ld, const unsigned char *ok,
+                     int nranks, const long *ranks, double *out);
+int bartrt_colselect_slab(long *rows);
+int bartrt_colselect_set_slab(long rows);
+int bartrt_posterior_tp(const double *params, long nsamples, int npars, int nq, const double *q,
+                        double *env, int *status, long *ngood);
+int bartrt_posterior_set_chunk(long rows);
+int bartrt_posterior_tp_order(int nq, int nlayers, long *ranks, double *order);
+int bartrt_percentile_rule(long n, double q, long *lo, long *hi, double *w);
+int bartrt_percentile_lerp(const double *a, const double *b, double w, double *out, long n);
+
 /* Line-by-line engines only (cfg has `linedb`, no `opacityfile`): the Voigt
  * extinction of one profile, ext[nlayers][nwave_local] in cm-1, atm layer order. */
 int bartrt_get_lbl_extinction(const double *prof, int nprof, double *ext,
