@@ -676,6 +676,18 @@ int bartrt_expint_e2(const double *x, double *out, long n) {
   });
 }
 
+int bartrt_rt_math(int which, const double *x, double *out, long n) {
+  if (n < 0 || (n > 0 && (!x || !out))) return fail(BARTRT_EINVAL, "bartrt_rt_math: bad arguments");
+  return guarded([&] {
+    if (which == BARTRT_RT_MATH_EXP_RT_FMA3) {
+      lbl_exp_rt_fma3_probe(x, out, n);
+    } else if (!step_rt_math_probe(which, x, out, n)) {
+      return fail(BARTRT_EINVAL, "bartrt_rt_math: unknown function selector");
+    }
+    return BARTRT_OK;
+  });
+}
+
 int bartrt_timing_begin(void) { return bartrt_timing_begin_sampled(1); }
 
 int bartrt_timing_begin_sampled(int stride) {

@@ -271,6 +271,23 @@ void lbl_voigt_probe(const double *x, const double *y, double *k, long n) {
   HIPCHK(hipMemcpy(k, d + 2 * n, sizeof(double) * n, hipMemcpyDeviceToHost));
 }
 
+// Diagnostics (bartrt_rt_math): exp_rt_fma3 on n values.
+__global__ void exp_rt_fma3_probe(const double *x, double *out, long n) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = exp_rt_fma3(x[i]);
+}
+
+void lbl_exp_rt_fma3_probe(const double *x, double *out, long n) {
+  if (n <= 0) return;
+  DevBuf<double> d;
+  d.reserve(2 * (size_t)n);
+  HIPCHK(hipMemcpy(d, x, sizeof(double) * n, hipMemcpyHostToDevice));
+  exp_rt_fma3_probe<<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(d, d + n, n);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(out, d + n, sizeof(double) * n, hipMemcpyDeviceToHost));
+}
+
 struct StateArgs {
   int L, S, nstate, table_mode, iH2, iHe, Nt, layer0;
   const double *prof;    // extinction mode: [nw][(S+1)][L]

@@ -104,5 +104,7 @@ void lbl_write_opacity(Engine &e, const std::string &path, const std::vector<dou
 
 // Diagnostics: Re w(x + i y) as the accumulation kernels evaluate it (host arrays).
 void lbl_voigt_probe(const double *x, const double *y, double *k, long n);
+// Diagnostics (bartrt_rt_math, BARTRT_RT_MATH_EXP_RT_FMA3): the accumulation kernels' own copy of exp_rt (host arrays).
+void lbl_exp_rt_fma3_probe(const double *x, double *out, long n);
 
 }  // namespace bartrt

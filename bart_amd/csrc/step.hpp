@@ -82,6 +82,9 @@ void step_run_host(Engine &e, const double *params, int n, int npars, double *ba
                    int *status);
 // diagnostics (bartrt_expint_e2): the T(p) kernels' exponential integral E_2 on n host values; needs no engine
 void step_expint_e2_probe(const double *x, double *out, long n);
+// diagnostics (bartrt_rt_math): the function a BARTRT_RT_MATH_* selector names, of those kernels.hpp defines, on n host
+// values; needs no engine.  false: not one of them (nothing is launched)
+bool step_rt_math_probe(int which, const double *x, double *out, long n);
 // A retrieval problem as a caller states it: retrieval.hpp's Objective on host memory, nothing checked and nfree not
 // counted yet.  The entry points below do that (retrieval_host.hpp: check_retrieval; std::invalid_argument).
 using RetrievalProblem = Objective;

@@ -152,6 +152,24 @@ def expint_e2(x: np.ndarray) -> np.ndarray:
     return out.reshape(x.shape)
 
 
+# the selectors of bartrt_rt_math (include/bartrt.h, BARTRT_RT_MATH_*)
+RT_MATH = {"exp_rt": 0, "exp_rt_n4": 1, "exp_rt_fma3": 2, "exp_core": 3, "rcp_core": 4, "rcp_n1": 5, "rcp_raw": 6,
+           "planck_inv": 7}
+
+
+def rt_math(name: str, x: np.ndarray) -> np.ndarray:
+    """One of the RT kernels' elementary functions (a key of RT_MATH) as the device evaluates it (diagnostics; no
+    engine needed).  The arguments are not checked: the exponentials take -708 .. 700 (exp_core: 709), the
+    reciprocals normal positive numbers."""
+    if name not in RT_MATH:
+        raise ValueError("rt_math: %r is not one of %s" % (name, ", ".join(RT_MATH)))
+    x = np.asarray(x, np.double)
+    xs = np.ascontiguousarray(x).ravel()
+    out = np.empty_like(xs)
+    _check(trm.lib().bartrt_rt_math(RT_MATH[name], _ptr(xs), _ptr(out), xs.size))
+    return out.reshape(x.shape)
+
+
 # ---- device-resident (torch tensors own the memory) ----------------------
 def _stream_ptr(stream=None):
     """The HIP stream the library is to enqueue on: torch's current stream.  torch's DEFAULT stream

@@ -114,6 +114,7 @@ def lib():
         L.bartrt_lbl_owners.argtypes = [p, i, p, i, i]
         L.bartrt_voigt.argtypes = [p, p, p, C.c_long]
         L.bartrt_expint_e2.argtypes = [p, p, C.c_long]
+        L.bartrt_rt_math.argtypes = [i, p, p, C.c_long]
         L.bartrt_timing_end.argtypes = [C.POINTER(d), C.POINTER(i)]
         L.bartrt_timing_begin_sampled.argtypes = [i]
         L.bartrt_set_integ.argtypes = [i]

@@ -837,6 +837,21 @@ int bartrt_voigt(const double *x, const double *y, double *k, long n);
  * model's kernels evaluate it (csrc/step.hip, expint_e2) on n host values:
  * x >= 0; 1.0 at 0, 0.0 beyond 709.78 and at +inf, NaN for NaN. */
 int bartrt_expint_e2(const double *x, double *out, long n);
+/* Diagnostics, no engine needed: one of the RT kernels' elementary functions (csrc/kernels.hpp; exp_rt_fma3:
+ * csrc/lbl.hip), evaluated by the device exactly as the kernels call it, on n host values.  The exponentials take
+ * -708 <= x <= 700 (exp_core: 709), the reciprocals normal positive numbers; nothing is checked, as in the kernels.
+ * BARTRT_EINVAL for a selector that is not in this list. */
+enum {
+  BARTRT_RT_MATH_EXP_RT = 0,      /* exp_rt(x) */
+  BARTRT_RT_MATH_EXP_RT_N4 = 1,   /* exp_rt_n<4> on four consecutive values per lane, every slot written */
+  BARTRT_RT_MATH_EXP_RT_FMA3 = 2, /* the line-by-line kernels' copy of exp_rt */
+  BARTRT_RT_MATH_EXP_CORE = 3,    /* exp_core(x) */
+  BARTRT_RT_MATH_RCP_CORE = 4,    /* rcp_core(x): hardware estimate + two Newton steps */
+  BARTRT_RT_MATH_RCP_N1 = 5,      /* rcp_n1(x): hardware estimate + one Newton step */
+  BARTRT_RT_MATH_RCP_RAW = 6,     /* the hardware estimate alone */
+  BARTRT_RT_MATH_PLANCK_INV = 7   /* rcp_n1(exp_rt(fmin(x, 700.0)) - 1.0): the Planck term without its numerator */
+};
+int bartrt_rt_math(int which, const double *x, double *out, long n);
 
 /* HIP-event timing of the RT kernel launches (bench.py's roofline leg).
  * begin resets; end returns accumulated device ms and launch count. */
