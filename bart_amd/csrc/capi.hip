@@ -591,6 +591,35 @@ int bartrt_get_prep_records(int walker, double *coef, long long *idx, int *kstop
   });
 }
 
+int bartrt_get_chord_table(int walker, double *rtop, double *ds, double *raw) {
+  NEED_ENGINE();
+  Engine *e = g_eng;
+  const Engine::PrepSeen &s = e->prep_seen;
+  if (e->solution != 1) return fail(BARTRT_EINVAL, "get_chord_table: transit geometry only");
+  if (!rtop || !ds) return fail(BARTRT_EINVAL, "get_chord_table: rtop and ds must not be null");
+  // (the radii and the table live in the engine's own workspaces, regrown -- and prep_seen forgotten -- with the records)
+  if (!s.coef || s.n <= 0 || !e->d_rtop.get() || !e->d_ds.get())
+    return fail(BARTRT_EINVAL, "get_chord_table: no launch has left a chord table to read back");
+  if (walker < 0 || walker >= s.n)
+    return fail(BARTRT_EINVAL, "get_chord_table: walker " + std::to_string(walker) + " is outside the latest batch of " +
+                               std::to_string(s.n));
+  return guarded([&] {
+    const int L = e->L;
+    const size_t nraw = chord_table_size(L);
+    std::vector<double> block(nraw);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(rtop, e->d_rtop.get() + (size_t)walker * L, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(block.data(), e->d_ds.get() + (size_t)walker * nraw, sizeof(double) * nraw, hipMemcpyDeviceToHost));
+    // dense [k][j] (chord k, layer j; both from the top) from the row-tile order the kernels read; a row tile ends
+    // with its diagonal tile (chord_table_fill), the steps behind it are never written
+    for (int k = 0; k < L; k++)
+      for (int j = 0; j < L; j++)
+        ds[(size_t)k * L + j] = j < 16 * ((k >> 4) + 1) ? block[chord_table_index(L, k, j)] : 0.0;
+    if (raw) std::memcpy(raw, block.data(), sizeof(double) * nraw);
+    return BARTRT_OK;
+  });
+}
+
 int bartrt_get_nangles(void) { CLIENT_OR_ENGINE(); return g_cli ? g_cli->info.A : g_eng->A; }
 
 int bartrt_get_tau(double *tau, int *last, int nwave, int nlayers) {

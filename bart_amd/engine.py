@@ -113,6 +113,19 @@ def prep_records(walker: int):
     return coef, idx, int(kstop[0]), int(ok[0])
 
 
+def chord_table(walker: int):
+    """The transit geometry's radii and chord table as the latest launch's preparation wrote them for one walker of
+    its batch (diagnostics; include/bartrt.h, bartrt_get_chord_table): (rtop[L], ds[L, L], raw[nkt, 4 nkt, 64]) --
+    the radii top to bottom, ds[k, j] = s_{j-1} - s_j of chord k in layer j (zero for j = 0 and j > k), and the table
+    as it lies in memory (row tile, step, lane; nkt = ceil(L / 16)).  Raises on an eclipse engine and for a walker
+    outside the batch."""
+    L = nlayers()
+    nkt = (L + 15) // 16
+    rtop, ds, raw = np.zeros(L), np.zeros((L, L)), np.zeros((nkt, 4 * nkt, 64))
+    _check(trm.lib().bartrt_get_chord_table(int(walker), _ptr(rtop), _ptr(ds), _ptr(raw)))
+    return rtop, ds, raw
+
+
 def lbl_extinction(profile: np.ndarray) -> np.ndarray:
     """Line-by-line extinction [L, W_local] (cm-1, atm layer order) of one profile."""
     prof = np.ascontiguousarray(profile, np.double).ravel()

@@ -110,6 +110,7 @@ def lib():
         if hasattr(L, "bartrt_get_prep_records"):
             L.bartrt_get_prep_shape.argtypes = [C.POINTER(i), C.POINTER(i)]
             L.bartrt_get_prep_records.argtypes = [i, p, p, p, p]
+        L.bartrt_get_chord_table.argtypes = [i, p, p, p]
         L.bartrt_get_lbl_extinction.argtypes = [p, i, p, i, i]
         L.bartrt_lbl_owners.argtypes = [p, i, p, i, i]
         L.bartrt_voigt.argtypes = [p, p, p, C.c_long]

@@ -647,6 +647,22 @@ int bartrt_get_intensity_of(int walker, double *intens, int nangles, int nwave);
 int bartrt_get_prep_shape(int *nmol, int *ncs);
 int bartrt_get_prep_records(int walker, double *coef, long long *idx, int *kstop, unsigned char *ok);
 
+/* Diagnostics (tests), transit geometry: the radii and the chord table the preparation of the latest launch wrote for
+ * walker `walker` of its batch -- a host-side copy after a device synchronisation, no kernel runs.  With L layers,
+ * layers and chords counted FROM THE TOP:
+ *   rtop[L]        the hydrostatic radii, top to bottom (cm);
+ *   ds[L][L]       ds[k][j] = s_{j-1} - s_j, s_j = sqrt(r_j^2 - r_k^2): the length inside layer j (between r_{j-1} and
+ *                  r_j) of half the chord with impact parameter r_k; 0 for j = 0 and for j > k.  Brought out of the
+ *                  order the kernels read into dense rows on the host;
+ *   raw            NULL, or 256 ceil(L / 16)^2 doubles: the table as it lies in memory, [row tile kt][step s][lane],
+ *                  lane l of step s holding ds[16 kt + l % 16][4 s + l / 16].  Row tile kt is written
+ *                  and read up to step 4 kt + 3 (its diagonal tile): there the entries with k >= L, j > k or j = 0
+ *                  are 0; the steps behind it are never written nor read (ds reports them as 0).
+ * BARTRT_EINVAL: an eclipse engine; rtop or ds NULL; no launch yet (or its buffers have been regrown since); a walker
+ * index outside the latest batch.  A batch that went out in chunks leaves its last chunk; bartrt_get_tau_of runs its
+ * walker again as a batch of one. */
+int bartrt_get_chord_table(int walker, double *rtop, double *ds, double *raw);
+
 /* Band-averaged contribution functions and transmittance of a batch of profiles: BART's
  * post-processing (code/cf.py:114-199, called at BART.py:626-644) on the optical depth
  * bartrt_get_tau_of would return for each walker with `toomuch` infinite -- the engine's
