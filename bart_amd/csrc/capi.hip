@@ -825,6 +825,45 @@ const char *bartrt_kernel_choice(int nmol, long columns) {
   return kernel_variant_name(slant_simpson_choice(nmol, columns < 0 ? 0 : columns).variant);
 }
 
+int bartrt_slant_thresholds(double toomuch, const double *invmu, int n, double *thr, double *thrb) {
+  if (!invmu || n < 1 || n > kMaxAngles) return fail(BARTRT_EINVAL, "slant_thresholds: 1 .. 16 rays");
+  RtArgs r{};
+  r.A = n;
+  r.toomuch = toomuch;
+  for (int a = 0; a < n; a++) r.invmu[a] = invmu[a];
+  slant_thresholds(r);
+  for (int a = 0; a < n; a++) {
+    if (thr) thr[a] = r.thr[a];
+    if (thrb) thrb[a] = r.thrb[a];
+  }
+  return BARTRT_OK;
+}
+
+int bartrt_get_ray_args(int n, double *invmu, double *wgt, double *wq, double *thr, double *thrb, int *order, int *sq) {
+  NEED_ENGINE();
+  Engine *e = g_eng;
+  if (e->solution != 0) return fail(BARTRT_EINVAL, "get_ray_args: eclipse geometry only");
+  if (n != e->A) return fail(BARTRT_EINVAL, "get_ray_args: bad length");
+  RtArgs r = e->rt;
+  r.toomuch = e->toomuch;
+  slant_thresholds(r);
+  for (int a = 0; a < n; a++) {
+    if (invmu) invmu[a] = r.invmu[a];
+    if (wgt) wgt[a] = r.wgt[a];
+    if (wq) wq[a] = r.wq[a];
+    if (thr) thr[a] = r.thr[a];
+    if (thrb) thrb[a] = r.thrb[a];
+  }
+  // the specialised kernels' order: the same call their launcher makes, on a copy whose drank carries the slots' origin
+  RtArgs b = r;
+  for (int a = 0; a < n; a++) b.drank[a] = a;
+  const bool is_sq = order_angles_for_square(b);
+  for (int a = 0; a < n; a++)
+    if (order) order[a] = b.drank[a];
+  if (sq) *sq = is_sq ? 1 : 0;
+  return BARTRT_OK;
+}
+
 int bartrt_kernel_inventory(char *buf, int buflen) {
   std::string s;
   if (!kernel_inventory(s)) return fail(BARTRT_ENOTSUP, "kernel_inventory: a unit lists " + s + " and the ahead-of-time lookup does not reach it");

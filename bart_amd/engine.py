@@ -167,7 +167,7 @@ def expint_e2(x: np.ndarray) -> np.ndarray:
 
 # the selectors of bartrt_rt_math (include/bartrt.h, BARTRT_RT_MATH_*)
 RT_MATH = {"exp_rt": 0, "exp_rt_n4": 1, "exp_rt_fma3": 2, "exp_core": 3, "rcp_core": 4, "rcp_n1": 5, "rcp_raw": 6,
-           "planck_inv": 7}
+           "planck_inv": 7, "alive_flags": 8}
 
 
 def rt_math(name: str, x: np.ndarray) -> np.ndarray:
@@ -181,6 +181,38 @@ def rt_math(name: str, x: np.ndarray) -> np.ndarray:
     out = np.empty_like(xs)
     _check(trm.lib().bartrt_rt_math(RT_MATH[name], _ptr(xs), _ptr(out), xs.size))
     return out.reshape(x.shape)
+
+
+def alive_flags(tm: np.ndarray, thr: np.ndarray) -> np.ndarray:
+    """The ray flag of rule 1's `cut slant` kernel (csrc/rt_eclipse_s1s.hpp alive_flags) for pairs of a running
+    optical depth and a ray's threshold, as the device evaluates it: 1.0 where the ray is alive (diagnostics; no
+    engine needed; include/bartrt.h, BARTRT_RT_MATH_ALIVE_FLAGS)."""
+    tm, thr = np.broadcast_arrays(np.asarray(tm, np.double), np.asarray(thr, np.double))
+    pairs = np.ascontiguousarray(np.stack([tm.ravel(), thr.ravel()], axis=1))
+    return rt_math("alive_flags", pairs).ravel()[:tm.size].reshape(tm.shape)
+
+
+def slant_thresholds(toomuch: float, invmu: np.ndarray):
+    """(thr, thrb) of `cut slant` for the rays' 1 / cos(theta), as the host forms them for a launch (no GPU, no engine;
+    include/bartrt.h, bartrt_slant_thresholds)."""
+    im = np.ascontiguousarray(invmu, np.double).ravel()
+    thr, thrb = np.zeros(im.size), np.zeros(im.size)
+    _check(trm.lib().bartrt_slant_thresholds(float(toomuch), _ptr(im), im.size, _ptr(thr), _ptr(thrb)))
+    return thr, thrb
+
+
+def ray_args() -> dict:
+    """The ray quadrature of the initialised eclipse engine as its launches carry it (diagnostics; include/bartrt.h,
+    bartrt_get_ray_args): invmu, wgt, wq, thr, thrb in the order of the raygrid, `order` (the ray in each slot of the
+    specialised kernels' order) and `sq` (that order is the square-root one: the last slot's transmittance is the
+    square of the first's)."""
+    n = trm.lib().bartrt_get_nangles()
+    out = {k: np.zeros(n) for k in ("invmu", "wgt", "wq", "thr", "thrb")}
+    order, sq = np.zeros(n, np.int32), C.c_int()
+    _check(trm.lib().bartrt_get_ray_args(n, *[_ptr(out[k]) for k in ("invmu", "wgt", "wq", "thr", "thrb")], _ptr(order),
+                                         C.byref(sq)))
+    out["order"], out["sq"] = order, bool(sq.value)
+    return out
 
 
 # ---- device-resident (torch tensors own the memory) ----------------------

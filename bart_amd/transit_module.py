@@ -116,6 +116,8 @@ def lib():
         L.bartrt_voigt.argtypes = [p, p, p, C.c_long]
         L.bartrt_expint_e2.argtypes = [p, p, C.c_long]
         L.bartrt_rt_math.argtypes = [i, p, p, C.c_long]
+        L.bartrt_slant_thresholds.argtypes = [d, p, i, p, p]
+        L.bartrt_get_ray_args.argtypes = [i, p, p, p, p, p, p, C.POINTER(i)]
         L.bartrt_timing_end.argtypes = [C.POINTER(d), C.POINTER(i)]
         L.bartrt_timing_begin_sampled.argtypes = [i]
         L.bartrt_set_integ.argtypes = [i]

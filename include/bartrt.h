@@ -595,6 +595,19 @@ const char *bartrt_build_id(void);
  * step of the layer-parallel walk), "adj8" / "adj16" (rows on adjacent lanes).  Needs no GPU and
  * no engine; the returned string is static. */
 const char *bartrt_kernel_choice(int nmol, long columns);
+/* The per-ray thresholds of `cut slant` as the host forms them for every launch (csrc/kernels.hpp, slant_thresholds):
+ * for n <= 16 rays with invmu[a] = 1 / cos(theta_a), thr[a] = the largest double t with fl(t * invmu[a]) <= toomuch
+ * (so that tau > thr[a] <=> tau * invmu[a] > toomuch, to the bit) and thrb[a] = 2^600 * the next double above thr[a]
+ * (+inf where that overflows: the scaled form the single-wave kernel's ray flags add to).  Either output may be NULL.
+ * Needs no GPU and no engine. */
+int bartrt_slant_thresholds(double toomuch, const double *invmu, int n, double *thr, double *thrb);
+/* Diagnostics (tests): the ray quadrature of the initialised eclipse engine as its launches carry it, n =
+ * bartrt_get_nangles() entries each, in the order of the `raygrid`: invmu = 1 / cos(theta), wgt = pi (sin^2 hi -
+ * sin^2 lo), wq = wgt * invmu, and thr / thrb of bartrt_slant_thresholds for the engine's present `toomuch`.
+ * order[s] = the ray in slot s of the specialised kernels' order; *sq = 1 when that order is the square-root one
+ * (slot n - 1 holds a ray of exactly twice slot 0's 1 / cos: its transmittance is taken as the square of slot 0's),
+ * else 0 and order is the identity.  Any output may be NULL.  Host side only: no kernel runs. */
+int bartrt_get_ray_args(int n, double *invmu, double *wgt, double *wq, double *thr, double *thrb, int *order, int *sq);
 /* The eclipse kernels the library holds ahead of time, one line each: the kernel's template-id in
  * namespace bartrt with every argument spelled out (the text the run-time compiler is given for a
  * shape that is NOT here), a tab, 1 / 0 -- whether a run-time build of it gets the max-ILP
@@ -865,7 +878,13 @@ enum {
   BARTRT_RT_MATH_RCP_CORE = 4,    /* rcp_core(x): hardware estimate + two Newton steps */
   BARTRT_RT_MATH_RCP_N1 = 5,      /* rcp_n1(x): hardware estimate + one Newton step */
   BARTRT_RT_MATH_RCP_RAW = 6,     /* the hardware estimate alone */
-  BARTRT_RT_MATH_PLANCK_INV = 7   /* rcp_n1(exp_rt(fmin(x, 700.0)) - 1.0): the Planck term without its numerator */
+  BARTRT_RT_MATH_PLANCK_INV = 7,  /* rcp_n1(exp_rt(fmin(x, 700.0)) - 1.0): the Planck term without its numerator */
+  /* alive_flags (csrc/rt_eclipse_s1s.hpp), the ray flags of rule 1's `cut slant` kernel: x holds n / 2 pairs (tm, thr)
+   * -- a running optical depth and a ray's threshold, 0 < thr < 1.7e308 --, and out[i], i < n / 2, is the flag of pair
+   * i (1.0: tm <= thr, the ray is alive; 0.0: it is not); the rest of out is left alone.  The threshold's scaled form
+   * is made by the host exactly as for a launch (bartrt_slant_thresholds).  BARTRT_EINVAL for an odd n or a threshold
+   * outside that range. */
+  BARTRT_RT_MATH_ALIVE_FLAGS = 8
 };
 int bartrt_rt_math(int which, const double *x, double *out, long n);
 
