@@ -332,6 +332,11 @@ def main(comm, argv=None, group=None, worker_factory=None, shard_backend="nccl")
     if ngpu > 1 and shard_pg is not None:
         import torch.distributed as dist
         if shard_pg is dist.group.WORLD:
+            # gloo (the CPU test of this path) only: rank 0 holds the rendezvous store, and when it tears down while a
+            # slower rank is still inside its last collective, rank 0's own exit ends in std::terminate
+            # (tests/test_distributed_cpu.py, intermittently).  The RCCL path is as it was.
+            if shard_backend != "nccl":
+                dist.barrier(group=shard_pg)
             dist.destroy_process_group()      # this function created it
     if verb and nbad is not None:
         print("Bad iterations of {} due to:".format("chain 0" if nworkers == 1 else "all chains"))

@@ -995,6 +995,41 @@ int bartrt_cf_combine_dev(const double *d_slots, int nranks, int nwalkers, const
   });
 }
 
+// (diagnostics, host code only: the shapes and the latest launch are filled in first, so a call with every buffer
+// null is the shape query; the copies need a chunk and a walker inside it)
+int bartrt_cf_get_records(int walker, bartrt_cf_records *r) {
+  NEED_ENGINE();
+  Engine *e = g_eng;
+  if (!r) return fail(BARTRT_EINVAL, "cf_get_records: null argument");
+  if (cf_nfilters(*e) == 0) return fail(BARTRT_EINVAL, "cf_get_records: call bartrt_cf_setup first");
+  const CfSeen s = cf_seen(*e);
+  r->nlayers = e->L; r->nmol = e->M; r->ncs = e->C; r->transit = e->solution == 1; r->nwalkers = s.n; r->nfilters = s.nf; r->ntiles = s.ntiles;
+  r->nent = s.nent; r->kernel = s.form; r->lds_bytes = (long long)s.lds; r->kstop = 0; r->ok = 0;
+  if (!r->coef && !r->idx && !r->rdlp && !r->rtop && !r->ds && !r->tile_ptr && !r->wt && !r->f_ptr && !r->f_ent && !r->trapz &&
+      walker < 0)
+    return BARTRT_OK;
+  // (cf_get_records refuses a missing chunk and a walker outside it: std::invalid_argument, BARTRT_EINVAL)
+  if (e->solution != 1 && (r->rtop || r->ds)) return fail(BARTRT_EINVAL, "cf_get_records: rtop and ds are the transit geometry's");
+  return guarded([&] {
+    static_assert(sizeof(idx_t) == sizeof(long long), "idx_t is the header's long long");
+    const int L = e->L;
+    std::vector<double> block(r->ds ? chord_table_size(L) : 0);
+    unsigned char ok = 0;
+    CfReadback o;
+    o.coef = r->coef; o.idx = r->idx; o.kstop = &r->kstop; o.ok = &ok; o.rdlp = r->rdlp; o.rtop = r->rtop;
+    o.ds = r->ds ? block.data() : nullptr;
+    o.tile_ptr = r->tile_ptr; o.f_ptr = r->f_ptr; o.f_ent = r->f_ent; o.wt = r->wt; o.trapz = r->trapz;
+    cf_get_records(*e, walker, o);
+    r->ok = ok;
+    // dense [k][j] from the row-tile order the kernels read, as bartrt_get_chord_table reports it
+    if (r->ds)
+      for (int k = 0; k < L; k++)
+        for (int j = 0; j < L; j++)
+          r->ds[(size_t)k * L + j] = j < 16 * ((k >> 4) + 1) ? block[chord_table_index(L, k, j)] : 0.0;
+    return BARTRT_OK;
+  });
+}
+
 int bartrt_cf_params(const double *params, int nwalkers, int npars, int kind, double *band, double *full, int *status) {
   return cf_call("cf_params", cf_params(params, nwalkers, npars, kind, band, full, status, true, nullptr));
 }

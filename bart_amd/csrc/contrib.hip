@@ -11,6 +11,11 @@
 //                     LDS (the generic rt_eclipse's tiling, kernels.hip): per layer the table extinction (Rayleigh,
 //                     grey cloud, molecules, CIA), TauColumn<INTEG>, then the layer's value.
 //  cf_transit<STAGE>  the same for the transit geometry: the chord sum of the generic rt_transit (transit_geom.hip).
+//  Dynamic LDS        with NC = 4 + 2 M + 2 C doubles and NI = 1 + C offsets per layer and the reduction block of
+//                     16 x 65 doubles (8320 bytes): cf_eclipse 8 L (NC + NI) + 8320 (+ 24 (L + kSimpsonPad) under rule 1);
+//                     cf_transit<true> 8 L (NC + NI + 64) + 8320, cf_transit<false> 512 L + 8320.  Above 64 kB the launch
+//                     raises the kernel's limit first; cf_transit is staged while that fits in 160 kB, unstaged while
+//                     512 L + 8320 does (L <= 303), and refused beyond (run_sums, launch_cf).
 //  Band reduction     every 16 layers the wave's values go to an LDS block [16 layers][64 lanes]; for each filter
 //                     that overlaps the tile, lane (j, q) sums layer j over the 16 wavenumbers of quarter q with the
 //                     filter's weights h_i resp_i (h = 1/2 at the window's ends), two cross-lane butterflies add the
@@ -278,6 +283,11 @@ struct CfWork {
   DevBuf<int> d_status;
   DevBuf<char> d_stage;               // staging of the host-buffer call
   hipStream_t last_stream = nullptr;  // the workspaces' latest user
+  // the latest chunk as bartrt_cf_get_records reports it: its walkers (0: none since the latest setup, or its launch
+  // was refused), where its flags lie, the kernel form and the dynamic LDS of its launch
+  int seen_n = 0, seen_form = kCfFormEclipse;
+  size_t seen_lds = 0;
+  const unsigned char *seen_ok = nullptr;
 };
 struct CfState : CfWork {   // ... and the filter tables
   int nf = 0, ntiles = 0, nent = 0;
@@ -363,8 +373,9 @@ void launch_cf(K kernel, size_t lds, int nblocks, hipStream_t st, const CfArgs &
 
 // one chunk up to this engine's band sums d_sums [m][nf][L] (cf_block_sums, not divided)
 void run_sums(Engine &e, const CfChunk &c, double *d_sums) {
-  const CfState &g = *e.cf;
+  CfState &g = *e.cf;
   const int m = c.m;
+  g.seen_n = 0;
   hipStream_t st = c.st;
   // the layer records under the engine's settings, as run_transit_batch builds them, into this module's buffers
   // (no radii output, only the caller's own per-walker overrides: the engine's own state is left as it was)
@@ -395,11 +406,15 @@ void run_sums(Engine &e, const CfChunk &c, double *d_sums) {
   const size_t L = e.L, NC = coef_stride(e.M, e.C), NI = idx_stride(e.C), blk = (size_t)kCfRows * kCfPitch;
   if (e.solution == 1) {
     const size_t with = sizeof(double) * (L * NC + L * NI + L * 64 + blk), without = sizeof(double) * (L * 64 + blk);
+    g.seen_form = with <= 160 * 1024 ? kCfFormStaged : kCfFormUnstaged;
+    g.seen_lds = with <= 160 * 1024 ? with : without;
     if (with <= 160 * 1024) launch_cf(cf_transit<true>, with, nblocks, st, a);
     else launch_cf(cf_transit<false>, without, nblocks, st, a);
   } else {
     const size_t base = sizeof(double) * (L * NC + L * NI + blk);
     const size_t simp = base + sizeof(double) * simpson_lds_doubles(e.L);
+    g.seen_form = kCfFormEclipse;
+    g.seen_lds = e.integ == kIntegSimpson ? simp : base;
     switch (e.integ) {
       case kIntegTransmittance: launch_cf(cf_eclipse<kIntegTransmittance>, base, nblocks, st, a); break;
       case kIntegSimpson: launch_cf(cf_eclipse<kIntegSimpson>, simp, nblocks, st, a); break;
@@ -411,6 +426,8 @@ void run_sums(Engine &e, const CfChunk &c, double *d_sums) {
   hipLaunchKernelGGL(cf_block_sums, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, g.d_part, m, g.nf, g.nent,
                      e.L, g.d_f_ptr, g.d_f_ent, d_sums);
   HIPCHK(hipGetLastError());
+  g.seen_n = m;
+  g.seen_ok = c.ok;
 }
 
 void combine(const Engine &e, const double *d_slots, int nranks, size_t slot, int m, const unsigned char *okp,
@@ -486,7 +503,7 @@ void cf_setup(Engine &e, int nf, const int *idx0, const int *npts, const double 
     tile_ptr[t + 1] = (int)ent_f.size();
   }
   const int nent = (int)ent_f.size();
-  // a window of n samples meets at most n / 64 + 2 tiles, wherever the tiles start
+  // a window of n samples meets at most (n - 1) / 64 + 2 <= n / 64 + 2 tiles, wherever the tiles start
   long bound = 0;
   for (int f = 0; f < nf; f++) bound += npts[f] / 64 + 2;
   std::vector<int> f_ptr(nf + 1, 0), f_ent;
@@ -511,10 +528,47 @@ void cf_setup(Engine &e, int nf, const int *idx0, const int *npts, const double 
   // an earlier setup's workspaces stay unless the entry or filter count changes (they size the partials and the
   // sums); its tables go with `old`
   if (old && old->nent == nent && old->nf == nf) static_cast<CfWork &>(*g) = std::move(*old);
+  g->seen_n = 0;   // (no chunk has run under these tables)
   e.cf = g.release();
 }
 
 int cf_nfilters(const Engine &e) { return e.cf ? e.cf->nf : 0; }
+
+CfSeen cf_seen(const Engine &e) {
+  CfSeen s;
+  if (const CfState *g = e.cf) {
+    s.n = g->seen_n; s.nf = g->nf; s.ntiles = g->ntiles; s.nent = g->nent;
+    s.form = g->seen_form; s.lds = g->seen_lds;
+  }
+  return s;
+}
+
+void cf_get_records(Engine &e, int walker, const CfReadback &o) {
+  CfState &g = *e.cf;
+  if (g.seen_n <= 0) throw std::invalid_argument("cf_get_records: no contribution-function call has run since the latest setup");
+  if (walker < 0 || walker >= g.seen_n)
+    throw std::invalid_argument("cf_get_records: walker " + std::to_string(walker) + " is outside the latest chunk of " +
+                                std::to_string(g.seen_n));
+  const size_t L = (size_t)e.L, NC = (size_t)coef_stride(e.M, e.C), NI = (size_t)idx_stride(e.C), w = (size_t)walker;
+  HIPCHK(hipStreamSynchronize(g.last_stream));
+  auto get = [](void *dst, const void *src, size_t bytes) {
+    if (dst && bytes) HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyDefault));
+  };
+  get(o.coef, g.rec.coef.get() + w * L * NC, sizeof(double) * L * NC);
+  get(o.idx, g.rec.idx.get() + w * L * NI, sizeof(idx_t) * L * NI);
+  get(o.kstop, g.rec.kstop.get() + w, sizeof(int));
+  get(o.ok, g.seen_ok + w, 1);   // (the module's own buffer, its staging, or the caller's device buffer: alive still)
+  get(o.rdlp, g.d_rdlp.get(), sizeof(double) * L);
+  if (e.solution == 1) {
+    get(o.rtop, g.d_rtop.get() + w * L, sizeof(double) * L);
+    get(o.ds, g.d_ds.get() + w * chord_table_size(e.L), sizeof(double) * chord_table_size(e.L));
+  }
+  get(o.tile_ptr, g.d_tile_ptr.get(), sizeof(int) * ((size_t)g.ntiles + 1));
+  get(o.f_ptr, g.d_f_ptr.get(), sizeof(int) * ((size_t)g.nf + 1));
+  get(o.f_ent, g.d_f_ent.get(), sizeof(int) * (size_t)g.nent);
+  get(o.wt, g.d_wt.get(), sizeof(double) * (size_t)g.nent * 64);
+  get(o.trapz, g.d_trapz.get(), sizeof(double) * (size_t)g.nf);
+}
 
 void cf_combine_dev(Engine &e, const double *d_slots, int nranks, int n, const unsigned char *d_ok, double *d_band,
                     hipStream_t st) {

@@ -52,6 +52,28 @@ void cf_run(Engine &e, const CfRequest &rq);
 // order into d_band [n][nfilters][L]; NaN rows where d_ok (optional) is 0.  No atomics: the bits depend on nranks only.
 void cf_combine_dev(Engine &e, const double *d_slots, int nranks, int n, const unsigned char *d_ok, double *d_band,
                     hipStream_t st);
+// Diagnostics (bartrt_cf_get_records): what the CF kernel of the latest chunk read for one of its walkers, and the
+// filter tables of the latest setup, copied to the host after a synchronisation of the module's last stream.  Host code
+// only: no kernel runs.  Every buffer may be null.  Throws std::invalid_argument without a chunk (no call since the
+// latest setup, or the latest call was refused) and for a walker outside it.
+struct CfSeen {
+  int n = 0, nf = 0, ntiles = 0, nent = 0;   // walkers of the latest chunk; the tables' shapes
+  int form = 0;                              // kCfFormEclipse / kCfFormStaged / kCfFormUnstaged
+  size_t lds = 0;                            // dynamic LDS bytes of the latest launch
+};
+enum { kCfFormEclipse = 0, kCfFormStaged = 1, kCfFormUnstaged = 2 };
+struct CfReadback {
+  double *coef = nullptr;   // [L][coef_stride]
+  idx_t *idx = nullptr;     // [L][idx_stride]
+  int *kstop = nullptr;
+  unsigned char *ok = nullptr;
+  double *rdlp = nullptr;   // [L]
+  double *rtop = nullptr, *ds = nullptr;   // transit: [L], [chord_table_size(L)] as it lies in memory
+  int *tile_ptr = nullptr, *f_ptr = nullptr, *f_ent = nullptr;   // [ntiles + 1], [nf + 1], [nent]
+  double *wt = nullptr, *trapz = nullptr;                        // [nent][64], [nf]
+};
+CfSeen cf_seen(const Engine &e);   // (zeros without a setup)
+void cf_get_records(Engine &e, int walker, const CfReadback &out);
 // frees the engine's filter tables and workspaces (~Engine, an earlier setup's)
 void cf_release(Engine &e);
 

@@ -690,6 +690,50 @@ def cf_combine_dev(d_slots, nranks, d_ok=None, stream=None):
     return band
 
 
+CF_KERNELS = ("cf_eclipse", "cf_transit<staged>", "cf_transit<unstaged>")
+
+
+class _CfRecords(C.Structure):
+    """include/bartrt.h, bartrt_cf_records."""
+    _fields_ = ([(k, C.c_int) for k in ("nlayers", "nmol", "ncs", "transit", "nwalkers", "nfilters", "ntiles", "nent", "kernel",
+                                        "kstop", "ok")] + [("lds_bytes", C.c_longlong)] +
+                [(k, C.c_void_p) for k in ("coef", "idx", "rdlp", "rtop", "ds", "tile_ptr", "wt", "f_ptr", "f_ent", "trapz")])
+
+
+def cf_launch():
+    """The shapes of the latest cf_setup and the CF kernel of the latest launch, a refused one included (diagnostics;
+    include/bartrt.h, bartrt_cf_get_records with no buffers): dict(nwalkers, nfilters, ntiles, nent, kernel, lds_bytes,
+    nmol, ncs, transit) -- kernel one of CF_KERNELS, nmol / ncs the engine's M and C, transit True on a transit
+    engine; nwalkers = 0 when no chunk has run since the setup."""
+    r = _CfRecords()
+    _check(trm.lib().bartrt_cf_get_records(-1, C.byref(r)))
+    return {"nwalkers": r.nwalkers, "nfilters": r.nfilters, "ntiles": r.ntiles, "nent": r.nent,
+            "kernel": CF_KERNELS[r.kernel], "lds_bytes": int(r.lds_bytes), "nmol": r.nmol, "ncs": r.ncs, "transit": bool(r.transit)}
+
+
+def cf_records(walker: int):
+    """What the CF kernel of the latest contribution / transmittance call read for one walker of its last chunk, and
+    the filter tables of the latest cf_setup (diagnostics; include/bartrt.h, bartrt_cf_get_records): a dict of
+    coef[L, 4 + 2 M + 2 C], idx[L, 1 + C], kstop, ok, rdlp[L] (layers from the top), on a transit engine rtop[L] and
+    ds[L, L] as chord_table gives them, tile_ptr[ntiles + 1], wt[nent, 64], f_ptr[nf + 1], f_ent[nent], trapz[nf],
+    and cf_launch()'s entries.  Raises without a setup, without a call since it, and for a walker outside the chunk."""
+    out = cf_launch()
+    L = nlayers()
+    a = {"coef": np.zeros((L, 4 + 2 * out["nmol"] + 2 * out["ncs"])), "idx": np.zeros((L, 1 + out["ncs"]), np.int64),
+         "rdlp": np.zeros(L), "tile_ptr": np.zeros(out["ntiles"] + 1, np.int32), "wt": np.zeros((out["nent"], 64)),
+         "f_ptr": np.zeros(out["nfilters"] + 1, np.int32), "f_ent": np.zeros(out["nent"], np.int32),
+         "trapz": np.zeros(out["nfilters"])}
+    if out["transit"]:
+        a["rtop"], a["ds"] = np.zeros(L), np.zeros((L, L))
+    r = _CfRecords()
+    for k, v in a.items():
+        setattr(r, k, v.ctypes.data)
+    _check(trm.lib().bartrt_cf_get_records(int(walker), C.byref(r)))
+    out.update(a)
+    out.update(kstop=r.kstop, ok=r.ok, nwalkers=r.nwalkers)
+    return out
+
+
 def _cf_over(over, n):
     """over [nwalkers, 3] = (radius km, log10 cloud-top bar, Rayleigh value) per walker, NaN = the engine-wide
     setting (include/bartrt.h, bartrt_cf_batch_over) -> contiguous float64 [n, 3]."""

@@ -149,6 +149,8 @@ def lib():
         L.bartrt_cf_setup_block.argtypes = [i, p, p, p]
         L.bartrt_cf_partials_dev.argtypes = [p, i, i, p, p, p, p, p]
         L.bartrt_cf_combine_dev.argtypes = [p, i, i, p, p, p]
+        if hasattr(L, "bartrt_cf_get_records"):
+            L.bartrt_cf_get_records.argtypes = [i, p]
         L.bartrt_colselect_dev.argtypes = [p, C.c_long, i, C.c_long, p, i, p, p, p]
         L.bartrt_colselect.argtypes = [p, C.c_long, i, C.c_long, p, i, p, p]
         L.bartrt_colselect_slab.argtypes = [C.POINTER(C.c_long)]

@@ -796,6 +796,40 @@ int bartrt_cf_partials_dev(const double *d_prof, int nwalkers, int kind, const d
 int bartrt_cf_combine_dev(const double *d_slots, int nranks, int nwalkers, const unsigned char *d_ok,
                           double *d_band, void *stream);
 
+/* Diagnostics (tests): what the contribution-function kernel of the latest call's LAST chunk read for walker `walker`
+ * of that chunk, and the filter tables of the latest setup -- the module prepares its walkers into workspaces of its
+ * own, which bartrt_get_prep_records and bartrt_get_chord_table do not see.  A host-side copy after a synchronisation
+ * of the module's latest stream; no kernel runs.  The call fills the scalar fields first, so a call with walker < 0
+ * and every buffer NULL is the shape query (BARTRT_OK once a setup exists); then each buffer that is not NULL:
+ *   coef, idx, kstop, ok   as bartrt_get_prep_records.  After a device-buffer call that passed d_ok the flag is read
+ *                          from THAT buffer, as bartrt_get_prep_records reads it: the caller keeps it allocated until
+ *                          the read-back (the module does not copy flags it was not asked to keep);
+ *   rdlp[L]                1 / (ln p_k - ln p_{k-1}), k from the top; [0] is 0 and unused;
+ *   rtop[L], ds[L][L]      transit engines only, as bartrt_get_chord_table (BARTRT_EINVAL on an eclipse engine);
+ *   tile_ptr[ntiles + 1]   the entries of tile t (64 samples of the engine's block) are tile_ptr[t] .. tile_ptr[t+1]-1,
+ *                          one per filter with a sample on the tile, filters ascending;
+ *   wt[nent][64]           an entry's weights h_i resp_i on its tile's lanes, 0 outside the window;
+ *   f_ptr[nfilters + 1], f_ent[nent]   filter f's entries in tile order: f_ent[f_ptr[f] .. f_ptr[f+1]-1];
+ *   trapz[nfilters]        the divisor of each filter's band value;
+ *   nwalkers               of the latest chunk (0: none since the latest setup, or its launch was refused);
+ *   kernel, lds_bytes      the CF kernel of the latest launch (also of a refused one) and its dynamic LDS.
+ * BARTRT_EINVAL: no bartrt_cf_setup; no call since it; a walker outside the latest chunk. */
+#define BARTRT_CF_KERNEL_ECLIPSE          0
+#define BARTRT_CF_KERNEL_TRANSIT_STAGED   1   /* the layer records staged in LDS */
+#define BARTRT_CF_KERNEL_TRANSIT_UNSTAGED 2   /* read where they lie: deep columns */
+typedef struct bartrt_cf_records {
+  int nlayers, nmol, ncs, transit, nwalkers, nfilters, ntiles, nent, kernel, kstop, ok;   /* transit: 1 on a transit engine */
+  long long lds_bytes;
+  double *coef;
+  long long *idx;
+  double *rdlp, *rtop, *ds;
+  int *tile_ptr;
+  double *wt;
+  int *f_ptr, *f_ent;
+  double *trapz;
+} bartrt_cf_records;
+int bartrt_cf_get_records(int walker, bartrt_cf_records *r);
+
 /* ---- exact order statistics, posterior envelopes (csrc/quant.hip, csrc/quant_core.hpp) ----
  * bartrt_colselect_dev: order statistics of the columns of a row-major matrix in device memory.
  *   d_x[nrows][ld]   doubles, of which the first ncols <= ld columns of every row are read

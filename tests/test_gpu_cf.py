@@ -2,7 +2,8 @@
 bart_amd.engine.contribution / transmittance; bart_amd.cf) against the CPU oracle's optical depth of the
 same case written with `toomuch 1e100`, passed through the tests' restatement of code/cf.py
 (tests/cf_restate.py) and the band weights of bart_amd.cf.filter_windows.  Every comparison is relative
-to the row's largest |value| (per walker and filter; per walker and wavenumber for the full output)."""
+to the row's largest |value| (per walker and filter; per walker and wavenumber for the full output): TOL is 1e-9 of
+that maximum.  The kernels are held tightly -- to an exact column under a derived bound -- in tests/test_gpu_cf_exact.py."""
 import os
 import subprocess
 import sys
