@@ -689,6 +689,21 @@ int bartrt_lbl_owners(const double *prof, int nprof, unsigned char *owners, int 
   });
 }
 
+int bartrt_lbl_get_states(int *nstate, int *niso, int *ngroup, double *state, double *smax) {
+  NEED_ENGINE();
+  Engine *e = g_eng;
+  if (!e->lbl) return fail(BARTRT_EINVAL, "lbl_get_states: the engine was not set up with a line list");
+  if (!nstate || !niso || !ngroup) return fail(BARTRT_EINVAL, "lbl_get_states: null argument");
+  return guarded([&] {
+    *nstate = (int)lbl_last_nstate(*e);
+    *niso = e->lbl->dev.niso;
+    *ngroup = e->lbl->dev.ngroup;
+    // (lbl_get_states refuses an engine without a call and smax after bartrt_lbl_owners: std::invalid_argument, BARTRT_EINVAL)
+    if (state || smax) lbl_get_states(*e, state, smax);
+    return BARTRT_OK;
+  });
+}
+
 int bartrt_voigt(const double *x, const double *y, double *k, long n) {
   if (n < 0 || (n > 0 && (!x || !y || !k))) return fail(BARTRT_EINVAL, "bartrt_voigt: bad arguments");
   return guarded([&] {

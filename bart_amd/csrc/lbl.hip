@@ -18,6 +18,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <stdexcept>
 
 #include "engine.hpp"
 #include "imw_tab.hpp"
@@ -218,7 +219,10 @@ __device__ __forceinline__ double voigt_k(double x, double y, const double *tab,
   if (r2 >= 64.0) {
     // asymptotic series  w = i/(sqrt(pi) z) * s(1/z^2): eleven terms from |z| = 8 (<= 2.6e-12 there; the
     // Laplace continued fraction with eight levels that stood here gave 1.7e-12 at eight reciprocals), six
-    // from |z| = 17 (<= 3e-13)
+    // from |z| = 17 (<= 3.8e-12: near the real axis the first omitted term of Re w is (2k + 1) (2k - 1)!! / (2 x^2)^k
+    // of the leading one, 13 * 10395 / 64 / 17^12 = 3.6e-12 at k = 6, and the tail adds 3 %; measured 3.7e-12 at
+    // x = 17, y -> 0 against mpmath.  The 3e-13 that stood here is the term without its factor 13: the error
+    // on the imaginary axis)
     const double inv = rcp_n1(r2), inv2 = inv * inv;
     const double tr = (x2 - y2) * inv2, ti = (-2.0 * x) * y * inv2;  // t = 1/z^2
     double sr, si;
@@ -1395,6 +1399,7 @@ static void run_states(Engine &e, StateArgs &sa, AccArgs &aa, hipStream_t st) {
   sa.press = e.d_press; sa.mass = e.d_mass; sa.diam = e.d_diam;
   sa.state = b->d_state;
   sa.dvmax = b->d_dvmax;
+  b->last_nstate = sa.nstate; b->last_smax = true;
   HIPCHK(hipMemsetAsync(b->d_dvmax, 0, sizeof(int), st));
   hipLaunchKernelGGL(lbl_states, dim3(sa.nstate), dim3(64), 0, st, sa, d);
   HIPCHK(hipGetLastError());
@@ -1489,6 +1494,7 @@ void lbl_owners(Engine &e, const double *d_prof, int nwalkers, unsigned char *ow
   sa.state = b->d_state;
   sa.dvmax = b->d_dvmax;
   hipStream_t st = e.stream;
+  b->last_nstate = nstate; b->last_smax = false;
   HIPCHK(hipMemsetAsync(b->d_dvmax, 0, sizeof(int), st));
   hipLaunchKernelGGL(lbl_states, dim3(sa.nstate), dim3(64), 0, st, sa, d);
   HIPCHK(hipGetLastError());
@@ -1510,6 +1516,19 @@ void lbl_owners(Engine &e, const double *d_prof, int nwalkers, unsigned char *ow
   HIPCHK(hipMemcpy(own, d_own, (size_t)n, hipMemcpyDeviceToHost));
 }
 
+long lbl_last_nstate(const Engine &e) { return e.lbl ? e.lbl->last_nstate : 0; }
+
+void lbl_get_states(Engine &e, double *state, double *smax) {
+  Lbl *b = e.lbl;
+  if (b->last_nstate <= 0) throw std::invalid_argument("lbl_get_states: no line-by-line call has run on this engine");
+  if (smax && !b->last_smax)
+    throw std::invalid_argument("lbl_get_states: the latest call (lbl_owners) did not compute the largest line strengths");
+  HIPCHK(hipDeviceSynchronize());   // (the latest call may have run on a stream of the caller's)
+  const size_t n = (size_t)b->last_nstate;
+  if (state) HIPCHK(hipMemcpy(state, b->d_state, sizeof(double) * n * (2 + 3 * b->dev.niso), hipMemcpyDeviceToHost));
+  if (smax) HIPCHK(hipMemcpy(smax, b->d_smax, sizeof(double) * n * b->dev.ngroup, hipMemcpyDeviceToHost));
+}
+
 void lbl_rt_eclipse(Engine &e, const double *d_prof, int nwalkers, const RtArgs &r, hipStream_t st) {
   Lbl *b = e.lbl;
   const LblDev &d = b->dev;
@@ -1520,6 +1539,7 @@ void lbl_rt_eclipse(Engine &e, const double *d_prof, int nwalkers, const RtArgs 
   sa.L = e.L; sa.S = e.S; sa.iH2 = e.iH2; sa.iHe = e.iHe;
   sa.press = e.d_press; sa.mass = e.d_mass; sa.diam = e.d_diam;
   sa.state = b->d_state;
+  b->last_nstate = nstate; b->last_smax = true;
   hipLaunchKernelGGL(lbl_states, dim3(sa.nstate), dim3(64), 0, st, sa, d);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemsetAsync(b->d_smax, 0, sizeof(double) * (size_t)nstate * d.ngroup, st));

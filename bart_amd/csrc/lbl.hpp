@@ -71,6 +71,9 @@ struct Lbl {
   DevBuf<double> d_ext;          // [nstate][W] (extinction mode)
   DevBuf<int> d_dvmax;           // largest oversampling factor among the states of a call
   long cap_state = 0;
+  // the latest call that ran lbl_states (bartrt_lbl_get_states): its states, and whether lbl_smax ran on them too
+  long last_nstate = 0;
+  bool last_smax = false;
   // width-grid mode (LblDev::voigt_grid): the grids, and per call the profile tables
   DevBuf<double> d_dgrid, d_lgrid;
   DevBuf<int> d_ginfo;           // [nstate][niso][3]: Lorentz index, first Doppler index, Doppler indices used
@@ -91,6 +94,12 @@ void lbl_extinction(Engine &e, const double *d_prof, int nwalkers, hipStream_t s
 // 0 lbl_accumulate, 1 lbl_accumulate_pairs, 2 / 3 lbl_accumulate_fine (oversampled / mid reach), 4 lbl_accumulate_grid,
 // 255 none; bit 7: more than one.  Synchronises the engine's stream.
 void lbl_owners(Engine &e, const double *d_prof, int nwalkers, unsigned char *own);
+// Diagnostics (bartrt_lbl_get_states): what lbl_states / lbl_smax wrote for the latest call, copied to the host --
+// state[nstate][2 + 3 niso] (T, dv, then Doppler factor, Lorentz half-width, SIGCTE * scale per isotope) and
+// smax[nstate][ngroup]; either may be null.  Throws std::invalid_argument when no call has run, or when smax is
+// asked for after a call that did not compute it (lbl_owners).  Synchronises the engine's stream.
+long lbl_last_nstate(const Engine &e);
+void lbl_get_states(Engine &e, double *state, double *smax);
 // Fused lazy form for eclipse spectra: per wavenumber tile the layers are
 // visited from the top, each layer's line extinction is summed when it is
 // reached, and the tile stops once every sample passed `toomuch` -- the deep,

@@ -147,6 +147,24 @@ def lbl_owners(profile: np.ndarray) -> np.ndarray:
     return own
 
 
+def lbl_states(profile: np.ndarray | None = None) -> dict:
+    """The state vectors the accumulation kernels read (diagnostics; include/bartrt.h, bartrt_lbl_get_states): what
+    lbl_states and lbl_smax wrote for `lbl_extinction(profile)`, which is run first -- or, with no profile, for the
+    latest line-by-line call as it stands (a batch, the opacity-grid generator's last slab).  A dict of T[nstate],
+    dv[nstate] (int), dop[nstate, niso], lor[nstate, niso], scale[nstate, niso] (SIGCTE * scale) and
+    smax[nstate, ngroup]."""
+    if profile is not None:
+        lbl_extinction(profile)
+    ns, ni, ng = C.c_int(), C.c_int(), C.c_int()
+    _check(trm.lib().bartrt_lbl_get_states(C.byref(ns), C.byref(ni), C.byref(ng), None, None))
+    state = np.zeros((ns.value, 2 + 3 * ni.value))
+    smax = np.zeros((ns.value, ng.value))
+    _check(trm.lib().bartrt_lbl_get_states(C.byref(ns), C.byref(ni), C.byref(ng), _ptr(state), _ptr(smax)))
+    per = state[:, 2:].reshape(ns.value, ni.value, 3)
+    return dict(T=state[:, 0].copy(), dv=state[:, 1].astype(int), dop=per[:, :, 0].copy(), lor=per[:, :, 1].copy(),
+                scale=per[:, :, 2].copy(), smax=smax)
+
+
 def voigt(x: np.ndarray, y: np.ndarray) -> np.ndarray:
     """Re w(x + i y) as the line-by-line kernels evaluate it (diagnostics; no engine needed)."""
     x, y = np.broadcast_arrays(np.asarray(x, np.double), np.asarray(y, np.double))

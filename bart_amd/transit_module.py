@@ -113,6 +113,7 @@ def lib():
         L.bartrt_get_chord_table.argtypes = [i, p, p, p]
         L.bartrt_get_lbl_extinction.argtypes = [p, i, p, i, i]
         L.bartrt_lbl_owners.argtypes = [p, i, p, i, i]
+        L.bartrt_lbl_get_states.argtypes = [C.POINTER(i), C.POINTER(i), C.POINTER(i), p, p]
         L.bartrt_voigt.argtypes = [p, p, p, C.c_long]
         L.bartrt_expint_e2.argtypes = [p, p, C.c_long]
         L.bartrt_rt_math.argtypes = [i, p, p, C.c_long]

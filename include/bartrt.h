@@ -892,6 +892,17 @@ int bartrt_get_lbl_extinction(const double *prof, int nprof, double *ext,
  * 3 the same (BARTRT_MID_REACH), 4 the width-grid kernel, 255 none; bit 7 set: more than one. */
 int bartrt_lbl_owners(const double *prof, int nprof, unsigned char *owners, int nlayers, int ntile);
 
+/* Diagnostics, line-by-line engines only, host only: the state vectors the accumulation kernels read, as lbl_states
+ * and lbl_smax wrote them for the latest line-by-line call (bartrt_get_lbl_extinction: nstate = nlayers, atm layer
+ * order; a batch: walker-major; the opacity-grid generator: the last slab, [layer][temperature]).  Always sets
+ * *nstate (0: no call yet), *niso (isotopes over all databases, database order) and *ngroup (databases).  With
+ * buffers (either may be null): state[nstate][2 + 3 niso] = T, the oversampling divisor dv, then per isotope the
+ * Doppler half-width per unit wavenumber, the Lorentz half-width (cm-1) and pi e^2 / (m_e c^2) * scale (scale:
+ * n_i / Z_i(T), or ratio_i / (Z_i(T) m_mol) per gram in the generator); smax[nstate][ngroup] = the largest line
+ * strength per (state, database).  BARTRT_EINVAL with buffers before any call, and for smax after
+ * bartrt_lbl_owners (which computes no strengths).  No kernel runs. */
+int bartrt_lbl_get_states(int *nstate, int *niso, int *ngroup, double *state, double *smax);
+
 /* Diagnostics, no engine needed: the line-by-line kernels' Voigt function
  * K(x, y) = Re w(x + i y) (x >= 0: distance from the line centre in Doppler widths
  * / sqrt(ln 2); y > 0: Lorentz / Doppler width ratio) on n host (x, y) pairs. */

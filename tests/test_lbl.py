@@ -75,7 +75,7 @@ def test_voigt_function_against_wofz():
     rel = np.abs(k / ref - 1)
     # |z| >= 100: three terms of the asymptotic series (1.4e-11 at |z| = 100)
     assert rel[r2 >= 1e4].max() < 2e-11
-    # 8 <= |z| < 100: the series (eleven terms from 8: 3e-12, six from 17: 3e-13), or for y <= 0.13 and
+    # 8 <= |z| < 100: the series (eleven terms from 8: 3e-12, six from 17: 3.8e-12 near the real axis), or for y <= 0.13 and
     # |z| < 17 the expansion about the real axis (cancellation: 5e-12); the omitted exp(-z^2) is < 2e-28
     assert rel[(r2 >= 64) & (r2 < 1e4)].max() < 1e-11
     # |z| < 8: the expansion about the real axis (truncation 3e-12) or, y > 0.13, Weideman N = 36 (3e-13) --
