@@ -7,6 +7,7 @@
 #include "comm.hpp"
 #include "contrib.hpp"
 #include "engine.hpp"
+#include "hist.hpp"
 #include "lbl.hpp"
 #include "quant.hpp"
 #include "share.hpp"
@@ -1169,6 +1170,120 @@ int bartrt_percentile_lerp(const double *a, const double *b, double w, double *o
   if (!a || !b || !out) return fail(BARTRT_EINVAL, "percentile_lerp: null buffer");
   for (long i = 0; i < n; i++) out[i] = quant::interpolate(a[i], b[i], w);
   return BARTRT_OK;
+}
+
+// ---- posterior marginals (hist.hip, hist_core.hpp): no engine ------------
+// the selection both calls take, each refusal named
+static int marginals_check_sel(const std::string &pre, const void *x, long nrows, long ld, int nsel, const int *cols) {
+  if (!x || !cols) return fail(BARTRT_EINVAL, pre + "null buffer (x, cols)");
+  if (nsel < 1 || nsel > hist::kMaxSel)
+    return fail(BARTRT_EINVAL, pre + "nsel = " + std::to_string(nsel) + " is outside 1.." + std::to_string(hist::kMaxSel));
+  if (nrows < 1 || nrows > kHistMaxRows)
+    return fail(BARTRT_EINVAL, pre + "nrows = " + std::to_string(nrows) + " is outside 1.." + std::to_string(kHistMaxRows));
+  if (ld < 1) return fail(BARTRT_EINVAL, pre + "ld = " + std::to_string(ld) + " is below 1");
+  for (int s = 0; s < nsel; s++)
+    if (cols[s] < 0 || cols[s] >= ld)
+      return fail(BARTRT_EINVAL, pre + "cols[" + std::to_string(s) + "] = " + std::to_string(cols[s]) +
+                                     " is outside 0..ld - 1 (ld = " + std::to_string(ld) + ")");
+  return BARTRT_OK;
+}
+
+static int marginals_check(const char *who, const void *x, long nrows, long ld, int nsel, const int *cols, int nbins,
+                           const double *edges, const void *h1, const void *out, const void *h2) {
+  const std::string pre = std::string(who) + ": ";
+  if (!edges || !h1 || !out) return fail(BARTRT_EINVAL, pre + "null buffer (edges, h1, out)");
+  if (int rc = marginals_check_sel(pre, x, nrows, ld, nsel, cols)) return rc;
+  if (nbins < 1 || nbins > hist::kMaxBins)
+    return fail(BARTRT_EINVAL, pre + "nbins = " + std::to_string(nbins) + " is outside 1.." + std::to_string(hist::kMaxBins));
+  if (h2 && nbins > hist::kMaxPairBins)
+    return fail(BARTRT_EINVAL, pre + "nbins = " + std::to_string(nbins) + " is above " + std::to_string(hist::kMaxPairBins) +
+                                   ", the most with pairs (h2 not NULL)");
+  for (int s = 0; s < nsel; s++) {
+    const int bad = hist::bad_edge(edges + (size_t)s * (nbins + 1), nbins);
+    if (bad >= 0)
+      return fail(BARTRT_EINVAL, pre + "edges[" + std::to_string(s) + "][" + std::to_string(bad) +
+                                     "] is not finite or not above the edge before it");
+  }
+  return BARTRT_OK;
+}
+
+int bartrt_marginals_dev(const double *d_x, long nrows, long ld, const unsigned char *d_ok, int nsel, const int *cols,
+                         int nbins, const double *edges, unsigned long long *d_h1, unsigned long long *d_out,
+                         unsigned long long *d_h2, void *stream) {
+  if (int rc = marginals_check("marginals_dev", d_x, nrows, ld, nsel, cols, nbins, edges, d_h1, d_out, d_h2)) return rc;
+  return guarded([&] {
+    marginals_dev(d_x, nrows, ld, d_ok, nsel, cols, nbins, edges, d_h1, d_out, d_h2, (hipStream_t)stream);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_marginals(const double *x, long nrows, long ld, const unsigned char *ok, int nsel, const int *cols, int nbins,
+                     const double *edges, unsigned long long *h1, unsigned long long *out, unsigned long long *h2) {
+  if (int rc = marginals_check("marginals", x, nrows, ld, nsel, cols, nbins, edges, h1, out, h2)) return rc;
+  return guarded([&] {
+    marginals_host(x, nrows, ld, ok, nsel, cols, nbins, edges, h1, out, h2);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_marginals_range_dev(const double *d_x, long nrows, long ld, const unsigned char *d_ok, int nsel, const int *cols,
+                               double *d_lohi, unsigned long long *d_nfinite, void *stream) {
+  if (!d_lohi || !d_nfinite) return fail(BARTRT_EINVAL, "marginals_range_dev: null buffer (lohi, nfinite)");
+  if (int rc = marginals_check_sel("marginals_range_dev: ", d_x, nrows, ld, nsel, cols)) return rc;
+  return guarded([&] {
+    marginals_range_dev(d_x, nrows, ld, d_ok, nsel, cols, d_lohi, d_nfinite, (hipStream_t)stream);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_marginals_range(const double *x, long nrows, long ld, const unsigned char *ok, int nsel, const int *cols,
+                           double *lohi, unsigned long long *nfinite) {
+  if (!lohi || !nfinite) return fail(BARTRT_EINVAL, "marginals_range: null buffer (lohi, nfinite)");
+  if (int rc = marginals_check_sel("marginals_range: ", x, nrows, ld, nsel, cols)) return rc;
+  return guarded([&] {
+    marginals_range_host(x, nrows, ld, ok, nsel, cols, lohi, nfinite);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_marginals_slab(long *rows) {
+  if (!rows) return fail(BARTRT_EINVAL, "marginals_slab: null buffer");
+  *rows = marginals_slab();
+  return BARTRT_OK;
+}
+
+int bartrt_marginals_set_slab(long rows) {
+  return guarded([&] {
+    marginals_set_slab(rows);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_marginals_chunk(long *rows) {
+  if (!rows) return fail(BARTRT_EINVAL, "marginals_chunk: null buffer");
+  *rows = marginals_chunk();
+  return BARTRT_OK;
+}
+
+int bartrt_marginals_set_chunk(long rows) {
+  return guarded([&] {
+    marginals_set_chunk(rows);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_hpd(const unsigned long long *counts, int nbins, double p, unsigned char *mask, unsigned long long *threshold,
+               unsigned long long *included, int *nruns) {
+  if (!counts || !mask || !threshold || !included || !nruns) return fail(BARTRT_EINVAL, "hpd: null buffer");
+  if (nbins < 1) return fail(BARTRT_EINVAL, "hpd: nbins = " + std::to_string(nbins) + " is below 1");
+  if (!(p > 0.0 && p <= 1.0)) return fail(BARTRT_EINVAL, "hpd: p = " + std::to_string(p) + " is outside (0, 1]");
+  return guarded([&] {
+    uint64_t thr = 0, inc = 0;
+    hist::hpd(reinterpret_cast<const uint64_t *>(counts), nbins, p, mask, &thr, &inc, nruns);
+    *threshold = thr;
+    *included = inc;
+    return BARTRT_OK;
+  });
 }
 
 // ---- per-step converters (step.hip) ------------------------------------

@@ -1025,3 +1025,115 @@ def posterior_tp(params, q, chunk=None, want_order=False):
     ranks, order = np.zeros(2 * qs.size, np.int64), np.zeros((2 * qs.size, L))
     _check(trm.lib().bartrt_posterior_tp_order(qs.size, L, _ptr(ranks), _ptr(order)))
     return env, status, ngood.value, ranks, order
+
+
+# ---- posterior marginals: histograms, ranges, HPD regions (include/bartrt.h, bartrt_marginals) ------------------
+def marginals_slab() -> int:
+    """The rows one workgroup of the histogram kernels owns (tests place their shapes around it)."""
+    rows = C.c_long()
+    _check(trm.lib().bartrt_marginals_slab(C.byref(rows)))
+    return rows.value
+
+
+def marginals_set_slab(rows: int) -> None:
+    """Another slab size (0: the default).  For tests: no count depends on it."""
+    _check(trm.lib().bartrt_marginals_set_slab(int(rows)))
+
+
+def marginals_set_chunk(rows: int) -> None:
+    """Rows per upload of the host forms (0: the default, 64 MiB).  For tests: no count depends on it."""
+    _check(trm.lib().bartrt_marginals_set_chunk(int(rows)))
+
+
+def _marginals_matrix(x, ok, who):
+    """(x, nrows, ld, x pointer, ok, ok pointer, is_host): x [nrows, ncols] float64, numpy or CUDA tensor, rows
+    contiguous (a padded view is read in place); ok [nrows] or None."""
+    if isinstance(x, np.ndarray):
+        if x.dtype != np.double or x.ndim != 2:
+            x = np.ascontiguousarray(x, np.double)
+            x = x.reshape(-1, x.shape[-1]) if x.ndim != 2 else x
+        ld = _row_stride(x.shape, x.strides, 8)
+        if ld is None:
+            x = np.ascontiguousarray(x)
+            ld = x.shape[1]
+        m = None if ok is None else np.ascontiguousarray(np.asarray(ok) != 0, np.uint8)
+        if m is not None and m.shape != (x.shape[0],):
+            raise ValueError(who + ": ok must have one entry per row")
+        return x, x.shape[0], max(ld, x.shape[1]), C.c_void_p(x.ctypes.data), m, (_ptr(m) if m is not None else None), True
+    import torch
+    assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2
+    ld = _row_stride(tuple(x.shape), tuple(s * 8 for s in x.stride()), 8)
+    if ld is None:
+        x = x.contiguous()
+        ld = x.shape[1]
+    if ok is not None:
+        assert ok.is_cuda and ok.dtype == torch.uint8 and ok.is_contiguous() and ok.shape == (x.shape[0],)
+    return (x, x.shape[0], max(ld, x.shape[1]), C.c_void_p(x.data_ptr()), ok,
+            (C.c_void_p(ok.data_ptr()) if ok is not None else None), False)
+
+
+def _marginals_cols(x, cols, who):
+    c = np.ascontiguousarray(cols, np.int32).ravel()
+    if c.size and (c.min() < 0 or c.max() >= x.shape[1]):
+        raise ValueError("%s: cols must lie in 0..%d" % (who, x.shape[1] - 1))
+    return c
+
+
+def marginals_range(x, cols, ok=None, stream=None):
+    """The smallest and largest finite value of the columns ``cols`` of x [nrows, ncols] among the rows ``ok`` lets
+    count, and their number: -> (lohi [nsel, 2], nfinite [nsel]).  np.nanmin / np.nanmax over the finite values, bit
+    for bit; NaN, NaN, 0 for a column without one.  ``x``: a float64 numpy array (host form, uploaded in chunks) or a
+    float64 CUDA tensor (device form, asynchronous on torch's current stream; the results are CUDA tensors, nfinite
+    as int64).  Needs no engine."""
+    x, nrows, ld, xp, ok, okp, host = _marginals_matrix(x, ok, "marginals_range")
+    c = _marginals_cols(x, cols, "marginals_range")
+    if host:
+        lohi, nfin = np.zeros((c.size, 2)), np.zeros(c.size, np.uint64)
+        _check(trm.lib().bartrt_marginals_range(xp, nrows, ld, okp, c.size, _ptr(c), _ptr(lohi), _ptr(nfin)))
+        return lohi, nfin
+    import torch
+    lohi = torch.zeros((c.size, 2), dtype=torch.float64, device=x.device)
+    nfin = torch.zeros(c.size, dtype=torch.int64, device=x.device)
+    _check(trm.lib().bartrt_marginals_range_dev(xp, nrows, ld, okp, c.size, _ptr(c), C.c_void_p(lohi.data_ptr()),
+                                                C.c_void_p(nfin.data_ptr()), _stream_ptr(stream)))
+    return lohi, nfin
+
+
+def marginals(x, cols, edges, pairs=True, ok=None, stream=None):
+    """1-D and pairwise histograms of the columns ``cols`` of x [nrows, ncols] (include/bartrt.h, bartrt_marginals):
+    -> (h1 [nsel, nbins], outside [nsel, 3], h2 [npairs, nbins, nbins] or None without ``pairs``).  ``edges`` [nsel,
+    nbins + 1] (host): finite, strictly increasing, uniform or not; h1[s] is np.histogram(x[ok, cols[s]],
+    bins=edges[s])[0], outside[s] the values below / above the edges and the NaNs, h2[p] np.histogram2d of the pair
+    (a, b) of selection indices, a < b, a-major, with bins=[edges[a], edges[b]] -- equal integers.  At most 64 columns,
+    1024 bins, 128 bins with pairs.  ``x``: a float64 numpy array (host form: uploaded in chunks, uint64 results) or
+    a float64 CUDA tensor (device form, asynchronous on torch's current stream, int64 CUDA tensors).  Needs no engine."""
+    x, nrows, ld, xp, ok, okp, host = _marginals_matrix(x, ok, "marginals")
+    c = _marginals_cols(x, cols, "marginals")
+    e = np.ascontiguousarray(edges, np.double)
+    if e.ndim != 2 or e.shape[0] != c.size or e.shape[1] < 2:
+        raise ValueError("marginals: edges must be [nsel, nbins + 1]")
+    nbins, npairs = e.shape[1] - 1, c.size * (c.size - 1) // 2
+    lib = trm.lib()
+    if host:
+        h1, out = np.zeros((c.size, nbins), np.uint64), np.zeros((c.size, 3), np.uint64)
+        h2 = np.zeros((npairs, nbins, nbins), np.uint64) if pairs else None
+        _check(lib.bartrt_marginals(xp, nrows, ld, okp, c.size, _ptr(c), nbins, _ptr(e), _ptr(h1), _ptr(out),
+                                    _ptr(h2) if pairs else None))
+        return h1, out, h2
+    import torch
+    new = lambda *shape: torch.zeros(shape, dtype=torch.int64, device=x.device)
+    h1, out, h2 = new(c.size, nbins), new(c.size, 3), (new(npairs, nbins, nbins) if pairs else None)
+    _check(lib.bartrt_marginals_dev(xp, nrows, ld, okp, c.size, _ptr(c), nbins, _ptr(e), C.c_void_p(h1.data_ptr()),
+                                    C.c_void_p(out.data_ptr()), C.c_void_p(h2.data_ptr()) if pairs else None,
+                                    _stream_ptr(stream)))
+    return h1, out, h2
+
+
+def hpd(counts, p: float):
+    """The highest-density region of a histogram at fraction 0 < p <= 1 (include/bartrt.h, bartrt_hpd; the rule is
+    csrc/hist_core.hpp's): -> (mask [nbins] bool, threshold, included, nruns).  On the host; needs no device."""
+    c = np.ascontiguousarray(counts, np.uint64).ravel()
+    mask = np.zeros(c.size, np.uint8)
+    thr, inc, runs = C.c_ulonglong(), C.c_ulonglong(), C.c_int()
+    _check(trm.lib().bartrt_hpd(_ptr(c), c.size, float(p), _ptr(mask), C.byref(thr), C.byref(inc), C.byref(runs)))
+    return mask.astype(bool), thr.value, inc.value, runs.value

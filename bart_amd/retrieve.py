@@ -243,6 +243,13 @@ def main(argv=None):
                     help="after the run (after --resume: on the whole chain) write tp_envelopes.npz beside output.npy: "
                          "the median and the 1- and 2-sigma percentiles of T(p) over the rows past the burn-in "
                          "(bart_amd.posterior; not with walk = unif or --datasets)")
+    ap.add_argument("--marginals", default=None, metavar="FILE.npz",
+                    help="after the run (after --resume: on the whole chain) write the free parameters' 1-D and "
+                         "pairwise histograms and their highest-density regions over the rows past the burn-in to "
+                         "FILE.npz (a relative name: beside output.npy; bart_amd.posterior.marginals; not with walk = "
+                         "unif or --datasets)")
+    ap.add_argument("--marginals-bins", type=int, default=20, metavar="N",
+                    help="with --marginals: bins per parameter (default 20, MC3's own)")
     a = ap.parse_args(argv)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -283,6 +290,10 @@ def main(argv=None):
         ap.error("--grid-bands and --grid-f32 go with walk = unif")
     if a.tp_envelopes and (unif or a.datasets):
         ap.error("--tp-envelopes is the envelope of one retrieval's chain: not with walk = unif or --datasets")
+    if a.marginals and (unif or a.datasets):
+        ap.error("--marginals is the histograms of one retrieval's chain: not with walk = unif or --datasets")
+    if a.marginals and not 1 <= a.marginals_bins <= 1024:
+        ap.error("--marginals-bins is a number of bins: 1 .. 1024")
     if a.ess_exit and not a.ess_target > 0:
         ap.error("--ess-exit stops at a target: name it with --ess-target N")
     if a.ess_target < 0:
@@ -410,6 +421,17 @@ def main(argv=None):
         if rank == 0:
             posterior.save(os.path.join(out, "tp_envelopes.npz"), env)
         res["tp_envelopes"] = env
+    if a.marginals:
+        # the same rows; counted on this rank's GPU (no engine call: every rank gets the same integers, rank 0 writes)
+        from . import cf, posterior
+        thin = max(1, int(scfg.thinning)) if a.resident else 1
+        rows = min(int(scfg.burnin) // thin, res["chain"].shape[1] - 1)
+        samples = cf.posterior_samples(res["chain"], scfg.params, scfg.stepsize, rows, layout="retrieve")
+        free = np.nonzero(np.asarray(scfg.stepsize) > 0)[0]
+        marg = dict(posterior.marginals_of_samples(samples, free, a.marginals_bins), burnin=rows)
+        if rank == 0:
+            posterior.save(os.path.join(out, a.marginals), marg)
+        res["marginals"] = marg
     if fitted is not None:
         res["fit"] = fitted
     w.close()

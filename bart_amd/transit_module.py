@@ -161,6 +161,16 @@ def lib():
         L.bartrt_posterior_tp_order.argtypes = [i, i, p, p]
         L.bartrt_percentile_rule.argtypes = [C.c_long, d, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(d)]
         L.bartrt_percentile_lerp.argtypes = [p, p, d, p, C.c_long]
+        if hasattr(L, "bartrt_marginals"):
+            L.bartrt_marginals_dev.argtypes = [p, C.c_long, C.c_long, p, i, p, i, p, p, p, p, p]
+            L.bartrt_marginals.argtypes = [p, C.c_long, C.c_long, p, i, p, i, p, p, p, p]
+            L.bartrt_marginals_range_dev.argtypes = [p, C.c_long, C.c_long, p, i, p, p, p, p]
+            L.bartrt_marginals_range.argtypes = [p, C.c_long, C.c_long, p, i, p, p, p]
+            L.bartrt_marginals_slab.argtypes = [C.POINTER(C.c_long)]
+            L.bartrt_marginals_set_slab.argtypes = [C.c_long]
+            L.bartrt_marginals_chunk.argtypes = [C.POINTER(C.c_long)]
+            L.bartrt_marginals_set_chunk.argtypes = [C.c_long]
+            L.bartrt_hpd.argtypes = [p, i, d, p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(i)]
         L.bartrt_algorithmic_bytes.argtypes = [i]
         L.bartrt_algorithmic_bytes.restype = d
         _lib = L

@@ -880,6 +880,68 @@ int bartrt_posterior_tp_order(int nq, int nlayers, long *ranks, double *order);
 int bartrt_percentile_rule(long n, double q, long *lo, long *hi, double *w);
 int bartrt_percentile_lerp(const double *a, const double *b, double w, double *out, long n);
 
+/* ---- posterior marginals: 1-D and pairwise histograms, their range, HPD regions (csrc/hist.hip,
+ * csrc/hist_core.hpp) ----
+ * The numbers behind MC3's `histogram` and `pairwise` figures (reference code/mc3plots.py:45-82).  NO ENGINE is
+ * needed (as for bartrt_mcmc_gr): the calls own their scratch on the current HIP device, so an output.npy can be
+ * post-processed without an opacity grid.
+ * bartrt_marginals_dev: histograms of selected columns of a row-major matrix in device memory.
+ *   d_x[nrows][ld]   doubles, parameters fastest, as a chain lies (and as bartrt_colselect_dev reads it)
+ *   d_ok[nrows]      or NULL: rows with 0 do not exist
+ *   cols[nsel]       HOST array, 1 <= nsel <= 64 selected columns in [0, ld), any order, not necessarily adjacent
+ *   edges[nsel][nbins + 1]  HOST array: per selected column nbins + 1 finite, strictly increasing edges,
+ *                    uniform or not.  x is in bin i iff edges[i] <= x < edges[i + 1]; x == edges[nbins] is in
+ *                    bin nbins - 1.  The decision is the comparison with the edges themselves, so the counts
+ *                    are np.histogram(col, bins=edges)'s and np.histogram2d(a, b, bins=[ea, eb])'s, integer
+ *                    for integer -- also for edges = np.linspace(lo, hi, nbins + 1) against numpy's
+ *                    bins=nbins, range=(lo, hi).  -0.0 and +0.0 fall in the same bin.
+ *   d_h1[nsel][nbins]       the 1-D counts
+ *   d_out[nsel][3]   what is in no bin: below edges[0] (-inf included), above edges[nbins] (+inf included), NaN.
+ *                    sum(h1[s]) + sum(out[s]) is the number of rows that count, for every s.
+ *   d_h2[npairs][nbins][nbins]  or NULL (no pairs wanted).  npairs = nsel (nsel - 1) / 2 pairs of SELECTION
+ *                    indices a < b, a-major: (0,1), (0,2), ..., (1,2), ...; the first bin index is a's, so
+ *                    h2[p] is np.histogram2d(x[:, cols[a]], x[:, cols[b]], bins=[edges[a], edges[b]])[0].  A row
+ *                    counts in a pair iff both values are in range.  nsel == 1: npairs = 0, d_h2 is not touched.
+ * All counts are unsigned 64-bit, zeroed by the call and added with integer atomics: they depend on no launch
+ * shape, slab or chunk.  Asynchronous on `stream` (NULL: the null stream).  One call at a time uses the
+ * scratch: a call first waits, on the host, for the device work of the previous one.
+ *   BARTRT_EINVAL    (the message names the argument; the outputs are not touched) nsel outside 1..64; a column
+ *                    outside [0, ld), which is also how an ld below the largest selected column + 1 shows;
+ *                    nbins outside 1..1024, or above 128 with d_h2 not NULL; an edge that is not finite or not
+ *                    above the one before it; nrows < 1 or above 2^31 - 1; a NULL buffer other than d_ok, d_h2.
+ * bartrt_marginals: the same from and to host memory.  The matrix goes up in row chunks of bounded size (64 MiB,
+ * or bartrt_marginals_set_chunk rows; the whole matrix is never needed in HBM) and the counts add up on the
+ * device.  The last row need only reach its last selected column.  Waits.
+ * bartrt_marginals_range_dev / bartrt_marginals_range: lohi[nsel][2] the smallest and largest FINITE value of
+ * every selected column among the rows that count, nfinite[nsel] their number, bit for bit np.nanmin / np.nanmax
+ * over the finite values (minimum and maximum of order-preserving keys: exact in any order; -0.0 orders before
+ * +0.0).  No finite value: NaN, NaN, 0.  The same selection arguments and refusals.
+ * bartrt_marginals_slab / _set_slab: the rows one workgroup owns (0 restores the default; at most 2^24);
+ * bartrt_marginals_chunk / _set_chunk: the rows per upload of the host forms (0: the default, by bytes).  For
+ * tests: no result depends on either.
+ * bartrt_hpd (host, no device): the highest-density region of a histogram at fraction 0 < p <= 1.  The bins are
+ * ordered by descending count, ties by ascending index; the region is the shortest prefix whose cumulative count
+ * c has (double)c >= p * (double)N, N = sum(counts).  mask[nbins] (1: included), *threshold the smallest count
+ * included, *included the region's total, *nruns its number of maximal runs of bins (2: bimodal).  N == 0: an
+ * empty mask and zeros.  This is MC3's credible region taken on the histogram instead of on a kernel density
+ * estimate; no KDE is built.  BARTRT_EINVAL: nbins < 1, p outside (0, 1], a NULL buffer. */
+int bartrt_marginals_dev(const double *d_x, long nrows, long ld, const unsigned char *d_ok, int nsel,
+                         const int *cols, int nbins, const double *edges, unsigned long long *d_h1,
+                         unsigned long long *d_out, unsigned long long *d_h2, void *stream);
+int bartrt_marginals(const double *x, long nrows, long ld, const unsigned char *ok, int nsel, const int *cols,
+                     int nbins, const double *edges, unsigned long long *h1, unsigned long long *out,
+                     unsigned long long *h2);
+int bartrt_marginals_range_dev(const double *d_x, long nrows, long ld, const unsigned char *d_ok, int nsel,
+                               const int *cols, double *d_lohi, unsigned long long *d_nfinite, void *stream);
+int bartrt_marginals_range(const double *x, long nrows, long ld, const unsigned char *ok, int nsel,
+                           const int *cols, double *lohi, unsigned long long *nfinite);
+int bartrt_marginals_slab(long *rows);
+int bartrt_marginals_set_slab(long rows);
+int bartrt_marginals_chunk(long *rows);
+int bartrt_marginals_set_chunk(long rows);
+int bartrt_hpd(const unsigned long long *counts, int nbins, double p, unsigned char *mask,
+               unsigned long long *threshold, unsigned long long *included, int *nruns);
+
 /* Line-by-line engines only (cfg has `linedb`, no `opacityfile`): the Voigt
  * extinction of one profile, ext[nlayers][nwave_local] in cm-1, atm layer order. */
 int bartrt_get_lbl_extinction(const double *prof, int nprof, double *ext,
