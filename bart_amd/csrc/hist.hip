@@ -20,8 +20,8 @@
 #include "hist.hpp"
 
 #include <cstring>
-#include <stdexcept>
-#include <string>
+
+#include "scratch.hpp"
 
 namespace bartrt {
 
@@ -212,59 +212,25 @@ __global__ void hist_range_finish(const u64 *__restrict__ keys, int nsel, double
   nfinite[s] = n;
 }
 
-// The calls' scratch.  It belongs to no engine; it lives on the device that was current when it was made, and a call
-// on another device starts over.  One call at a time uses it: a call waits for the previous one's device work (`done`)
-// before it touches the staging memory or enqueues anything.
-struct HistState {
-  int device = -1;
-  long slab_rows = 0, chunk_rows = 0;
-  hipEvent_t done = nullptr;
-  bool pending = false;
+// The calls' scratch (scratch.hpp: the reuse rule).  It belongs to no engine; it lives on the device that was current
+// when it was made, and a call on another device starts over.
+struct HistState : Scratch {
   PinBuf<double> h_edges;
   PinBuf<int> h_cols;
-  DevBuf<double> edges;
+  DevBuf<double> edges, lohi;
   DevBuf<int> cols;
   DevBuf<unsigned short> idx;
-  DevBuf<u64> keys;
-  // host forms
-  DevBuf<double> x, lohi;
-  DevBuf<unsigned char> ok;
-  DevBuf<u64> h1, out, h2, nfinite;
+  DevBuf<u64> keys, h1, out, h2, nfinite;
 };
 
-HistState &state() {
-  static HistState *s = new HistState;     // (never freed: no HIP call from a static destructor)
-  return *s;
-}
+HistState *g_state = new HistState;     // (never freed at exit: no HIP call from a static destructor)
 
-// the state, ready for a new call on the current device
+// the state, ready for a new call on the current device.  The host waits for the previous call: every call rewrites
+// the pinned staging memory that call's copies read
 HistState &begin() {
-  HistState &h = state();
-  int dev = 0;
-  HIPCHK(hipGetDevice(&dev));
-  if (h.pending) {
-    HIPCHK(hipEventSynchronize(h.done));
-    h.pending = false;
-  }
-  if (dev != h.device) {
-    if (h.done) HIPCHK(hipEventDestroy(h.done));
-    h.done = nullptr;
-    for (auto *b : {&h.edges, &h.x, &h.lohi}) b->reset();
-    for (auto *b : {&h.h1, &h.out, &h.h2, &h.nfinite, &h.keys}) b->reset();
-    h.h_edges.reset();
-    h.h_cols.reset();
-    h.cols.reset();
-    h.idx.reset();
-    h.ok.reset();
-    HIPCHK(hipEventCreateWithFlags(&h.done, hipEventDisableTiming));
-    h.device = dev;
-  }
+  HistState &h = on_current_device(g_state);
+  h.wait();
   return h;
-}
-
-void end(HistState &h, hipStream_t st) {
-  HIPCHK(hipEventRecord(h.done, st));
-  h.pending = true;
 }
 
 long slab_of(const HistState &h) { return h.slab_rows > 0 ? h.slab_rows : kHistSlabRows; }
@@ -346,23 +312,14 @@ void range_finish(HistState &h, int nsel, double *d_lohi, u64 *d_nfinite, hipStr
   HIPCHK(hipGetLastError());
 }
 
-// the host forms' loop: the matrix in row chunks through h.x / h.ok, each handed to `each`
+// the host forms' loop: row chunks (marginals_set_chunk) of the matrix up to its last selected column, through `each`
 template <class F>
 void upload_chunks(HistState &h, const double *x, long nrows, long ld, const unsigned char *ok, int nsel, const int *cols,
                    hipStream_t st, F &&each) {
   long width = 0;
   for (int s = 0; s < nsel; s++) width = std::max<long>(width, cols[s] + 1);
   const long fit = std::max<long>(1, kHistChunkBytes / (long)(sizeof(double) * ld));
-  const long rows = std::min(nrows, h.chunk_rows > 0 ? h.chunk_rows : fit);
-  h.x.reserve((size_t)(rows - 1) * ld + width);
-  if (ok) h.ok.reserve((size_t)rows);
-  for (long off = 0; off < nrows; off += rows) {
-    const long n = std::min(rows, nrows - off);
-    // (the last row is read up to its last selected column: the caller's array may end there)
-    HIPCHK(hipMemcpyAsync(h.x, x + (size_t)off * ld, sizeof(double) * ((size_t)(n - 1) * ld + width), hipMemcpyHostToDevice, st));
-    if (ok) HIPCHK(hipMemcpyAsync(h.ok, ok + off, (size_t)n, hipMemcpyHostToDevice, st));
-    each(h.x.get(), n, ok ? h.ok.get() : nullptr);
-  }
+  h.upload_chunks(x, nrows, ld, width, ok, std::min(nrows, h.chunk_rows > 0 ? h.chunk_rows : fit), st, each);
 }
 
 }  // namespace
@@ -374,7 +331,7 @@ void marginals_dev(const double *d_x, long nrows, long ld, const unsigned char *
   stage_edges(h, nsel, nbins, edges, st);
   zero_counts(nsel, nbins, d_h1, d_out, d_h2, st);
   accumulate(h, d_x, nrows, ld, d_ok, nsel, nbins, d_h1, d_out, d_h2, st);
-  end(h, st);
+  h.record(st);
 }
 
 void marginals_host(const double *x, long nrows, long ld, const unsigned char *ok, int nsel, const int *cols, int nbins,
@@ -405,7 +362,7 @@ void marginals_range_dev(const double *d_x, long nrows, long ld, const unsigned 
   range_start(h, nsel, cols, st);
   range_accumulate(h, d_x, nrows, ld, d_ok, nsel, st);
   range_finish(h, nsel, d_lohi, d_nfinite, st);
-  end(h, st);
+  h.record(st);
 }
 
 void marginals_range_host(const double *x, long nrows, long ld, const unsigned char *ok, int nsel, const int *cols,
@@ -424,18 +381,10 @@ void marginals_range_host(const double *x, long nrows, long ld, const unsigned c
   HIPCHK(hipStreamSynchronize(st));
 }
 
-void marginals_set_slab(long rows) {
-  if (rows < 0 || rows > kHistMaxSlabRows)
-    throw std::invalid_argument("marginals_set_slab: rows = " + std::to_string(rows) + " is outside 0.." +
-                                std::to_string(kHistMaxSlabRows));
-  state().slab_rows = rows;
-}
-long marginals_slab() { return slab_of(state()); }
+void marginals_set_slab(long rows) { Scratch::set_rows(g_state->slab_rows, "marginals_set_slab", rows, kHistMaxSlabRows); }
+long marginals_slab() { return slab_of(*g_state); }
 
-void marginals_set_chunk(long rows) {
-  if (rows < 0) throw std::invalid_argument("marginals_set_chunk: rows = " + std::to_string(rows) + " is negative");
-  state().chunk_rows = rows;
-}
-long marginals_chunk() { return state().chunk_rows; }
+void marginals_set_chunk(long rows) { Scratch::set_rows(g_state->chunk_rows, "marginals_set_chunk", rows); }
+long marginals_chunk() { return g_state->chunk_rows; }
 
 }  // namespace bartrt

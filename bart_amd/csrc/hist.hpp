@@ -1,5 +1,6 @@
 // Marginal and pairwise histograms of selected columns of a row-major matrix in HBM, and their range (hist.hip; the
-// rule is hist_core.hpp's).  No engine: the calls own their scratch and run on the current device.
+// rule is hist_core.hpp's).  No engine: the calls own their scratch and run on the current device.  It serves one
+// call at a time: a call comes after the previous one's device work before it reuses the scratch (scratch.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,7 +20,7 @@ constexpr long kHistChunkBytes = 64l << 20;      // the host forms' upload chunk
 // d_x[nrows][ld], d_ok[nrows] or null, cols[nsel] and edges[nsel][nbins + 1] HOST arrays -> d_h1[nsel][nbins],
 // d_out[nsel][3] (below, above, NaN) and, d_h2 not null, d_h2[npairs][nbins][nbins] (pairs a < b of selection
 // indices, a-major, the first bin index a's).  Device memory, zeroed here, asynchronous on st.  The arguments are the
-// caller's to check (capi.hip).  A call waits for the previous call's device work before it reuses the scratch.
+// caller's to check (capi.hip).
 void marginals_dev(const double *d_x, long nrows, long ld, const unsigned char *d_ok, int nsel, const int *cols, int nbins,
                    const double *edges, unsigned long long *d_h1, unsigned long long *d_out, unsigned long long *d_h2,
                    hipStream_t st);

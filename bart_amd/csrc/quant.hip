@@ -22,13 +22,10 @@
 // histogram (quant::walk), appends the digit, names the next pass's leaders and zeroes the histogram again.
 #include "quant.hpp"
 
-#include <cmath>
-#include <cstdlib>
 #include <limits>
-#include <stdexcept>
-#include <string>
 #include <vector>
 
+#include "scratch.hpp"
 #include "step.hpp"
 
 namespace bartrt {
@@ -167,18 +164,14 @@ __global__ void quant_mask_of_status(const int *__restrict__ status, long n, uns
 
 }  // namespace
 
-// the engine's scratch of the selection and of the posterior envelope; grown by the call that needs more
-struct QuantState {
+// the engine's scratch of the selection and of the posterior envelope (scratch.hpp: the reuse rule, the settings)
+struct QuantState : Scratch {
   DevBuf<unsigned long long> prefix;
   DevBuf<long> krem;
   DevBuf<unsigned char> leader;
   DevBuf<unsigned> alive, active, hist;
-  long slab_rows = 0;    // bartrt_colselect_set_slab (0: kQuantSlabRows)
-  // host form of the selection
-  DevBuf<double> x, out;
-  DevBuf<unsigned char> ok;
+  DevBuf<double> out;    // host form of the selection
   // posterior_tp
-  long chunk = 0;        // bartrt_posterior_set_chunk (0: kDefaultChunk)
   DevBuf<double> params, prof, temp, order;
   DevBuf<int> status;
   DevBuf<unsigned char> good;
@@ -196,14 +189,6 @@ QuantState &state_of(Engine &e) {
   return *e.quant;
 }
 
-// room for n elements; a buffer that has to grow may still be read by a launch in flight (devbuf.hpp)
-template <class T>
-void grow(DevBuf<T> &b, size_t n) {
-  if (b && n <= b.count()) return;
-  HIPCHK(hipDeviceSynchronize());
-  b.reserve(n);
-}
-
 }  // namespace
 
 void quant_release(Engine &e) {
@@ -217,12 +202,13 @@ void colselect_dev(Engine &e, const double *d_x, long nrows, int ncols, long ld,
   QuantState &q = state_of(e);
   if (slab_rows <= 0) slab_rows = q.slab_rows > 0 ? q.slab_rows : kQuantSlabRows;
   const size_t cells = (size_t)nranks * ncols;
-  grow(q.prefix, cells);
-  grow(q.krem, cells);
-  grow(q.leader, cells);
-  grow(q.alive, (size_t)ncols);
-  grow(q.active, (size_t)ncols);
-  grow(q.hist, cells * quant::kBins);
+  q.room(q.prefix, cells);
+  q.room(q.krem, cells);
+  q.room(q.leader, cells);
+  q.room(q.alive, (size_t)ncols);
+  q.room(q.active, (size_t)ncols);
+  q.room(q.hist, cells * quant::kBins);
+  q.after_previous(st);
   SelState s{q.prefix, q.krem, q.leader, q.alive, q.active, q.hist};
   RankList rl{};
   for (int r = 0; r < nranks; r++) rl.k[r] = ranks[r];
@@ -240,27 +226,25 @@ void colselect_dev(Engine &e, const double *d_x, long nrows, int ncols, long ld,
     hipLaunchKernelGGL(quant_walk, per_col, dim3(lanes), 0, st, s, ncols, nranks, pass, d_out);
     HIPCHK(hipGetLastError());
   }
+  q.record(st);
 }
 
 void colselect_host(Engine &e, const double *x, long nrows, int ncols, long ld, const unsigned char *ok, int nranks,
                     const long *ranks, double *out) {
   QuantState &q = state_of(e);
   hipStream_t st = e.stream;
-  const size_t nx = (size_t)(nrows - 1) * ld + ncols, nout = (size_t)nranks * ncols;
-  grow(q.x, nx);
-  grow(q.out, nout);
-  if (ok) grow(q.ok, (size_t)nrows);
-  HIPCHK(hipMemcpyAsync(q.x, x, sizeof(double) * nx, hipMemcpyHostToDevice, st));
-  if (ok) HIPCHK(hipMemcpyAsync(q.ok, ok, (size_t)nrows, hipMemcpyHostToDevice, st));
-  colselect_dev(e, q.x, nrows, ncols, ld, ok ? q.ok.get() : nullptr, nranks, ranks, q.out, st);
+  const size_t nout = (size_t)nranks * ncols;
+  q.room(q.out, nout);
+  // one chunk of all rows: the selection makes 16 passes over the matrix and needs it resident.  (The staging and
+  // q.out are this function's alone, and it ends in a full wait: no earlier call can still be using them.)
+  q.upload_chunks(x, nrows, ld, ncols, ok, nrows, st, [&](const double *d_x, long, const unsigned char *d_ok) {
+    colselect_dev(e, d_x, nrows, ncols, ld, d_ok, nranks, ranks, q.out, st);
+  });
   HIPCHK(hipMemcpyAsync(out, q.out, sizeof(double) * nout, hipMemcpyDeviceToHost, st));
   e.wait(st);
 }
 
-void posterior_set_chunk(Engine &e, long rows) {
-  if (rows < 0) throw std::invalid_argument("posterior_set_chunk: rows = " + std::to_string(rows) + " is negative");
-  state_of(e).chunk = rows;
-}
+void posterior_set_chunk(Engine &e, long rows) { Scratch::set_rows(state_of(e).chunk_rows, "posterior_set_chunk", rows); }
 
 void posterior_tp(Engine &e, const double *params, long nsamples, int npars, int nq, const double *pct, double *env,
                   int *status, long *ngood) {
@@ -268,13 +252,13 @@ void posterior_tp(Engine &e, const double *params, long nsamples, int npars, int
   hipStream_t st = e.stream;
   const int L = e.L;
   const size_t nprof = (size_t)(e.S + 1) * L;
-  const long chunk = std::min(nsamples, q.chunk > 0 ? q.chunk : kDefaultChunk);
-  grow(q.params, (size_t)chunk * npars);
-  grow(q.prof, (size_t)chunk * nprof);
-  grow(q.temp, (size_t)nsamples * L);
-  grow(q.status, (size_t)nsamples);
-  grow(q.good, (size_t)nsamples);
-  grow(q.order, (size_t)2 * nq * L);
+  const long chunk = std::min(nsamples, q.chunk_rows > 0 ? q.chunk_rows : kDefaultChunk);
+  q.room(q.params, (size_t)chunk * npars);
+  q.room(q.prof, (size_t)chunk * nprof);
+  q.room(q.temp, (size_t)nsamples * L);
+  q.room(q.status, (size_t)nsamples);
+  q.room(q.good, (size_t)nsamples);
+  q.room(q.order, (size_t)2 * nq * L);
   q.last_nq = 0;
   for (long off = 0; off < nsamples; off += chunk) {
     const int n = (int)std::min(chunk, nsamples - off);
@@ -321,9 +305,6 @@ bool posterior_tp_order(const Engine &e, int nq, int nlayers, long *ranks, doubl
 
 long colselect_slab(const Engine &e) { return e.quant && e.quant->slab_rows > 0 ? e.quant->slab_rows : kQuantSlabRows; }
 
-void colselect_set_slab(Engine &e, long rows) {
-  if (rows < 0) throw std::invalid_argument("colselect_set_slab: rows = " + std::to_string(rows) + " is negative");
-  state_of(e).slab_rows = rows;
-}
+void colselect_set_slab(Engine &e, long rows) { Scratch::set_rows(state_of(e).slab_rows, "colselect_set_slab", rows); }
 
 }  // namespace bartrt

@@ -1,5 +1,6 @@
 // Column-wise order statistics of a row-major matrix in HBM, and the posterior T(p) envelope on top of them
-// (quant.hip; the arithmetic is quant_core.hpp's).
+// (quant.hip; the arithmetic is quant_core.hpp's).  The scratch is the engine's.  It serves one call at a time: a call
+// comes after the previous one's device work before it reuses the scratch (scratch.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 

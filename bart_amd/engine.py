@@ -920,13 +920,10 @@ def _row_stride(shape, strides, itemsize):
     return ld if (ld >= shape[1] or shape[0] == 1) else None
 
 
-def colselect(x, ranks, ok=None, stream=None):
-    """Order statistics of the columns of x [nrows, ncols]: -> [nranks, ncols], row r the values
-    np.sort(x[ok], axis=0)[ranks[r]] has, bit for bit.  ``x``: a float64 numpy array (host form: a rank at or above
-    the rows that count raises) or a float64 CUDA tensor (device form, asynchronous on torch's current stream: such a
-    rank gives NaN).  Rows may be padded (a view x[:, :ncols] of a wider array is read in place).  ``ok`` [nrows]:
-    rows with 0 do not exist.  At most 16 ranks, any order, duplicates allowed."""
-    r = np.ascontiguousarray(ranks, np.int64).ravel()
+def _matrix_arg(x, ok, who):
+    """The matrix of colselect, marginals and marginals_range (``who``): -> (x, nrows, ld, x pointer, ok, ok pointer,
+    is_host).  x [nrows, ncols] float64, numpy or CUDA tensor, rows contiguous (a padded view is read in place), else
+    copied; ok [nrows] or None.  Pure numpy / torch: the library is not touched."""
     if isinstance(x, np.ndarray):
         if x.dtype != np.double or x.ndim != 2:
             x = np.ascontiguousarray(x, np.double)
@@ -935,27 +932,38 @@ def colselect(x, ranks, ok=None, stream=None):
         if ld is None:
             x = np.ascontiguousarray(x)
             ld = x.shape[1]
-        ld = max(ld, x.shape[1])
         m = None if ok is None else np.ascontiguousarray(np.asarray(ok) != 0, np.uint8)
         if m is not None and m.shape != (x.shape[0],):
-            raise ValueError("colselect: ok must have one entry per row")
-        out = np.zeros((r.size, x.shape[1]))
-        _check(trm.lib().bartrt_colselect(C.c_void_p(x.ctypes.data), x.shape[0], x.shape[1], ld,
-                                          _ptr(m) if m is not None else None, r.size, _ptr(r), _ptr(out)))
-        return out
+            raise ValueError(who + ": ok must have one entry per row")
+        return x, x.shape[0], max(ld, x.shape[1]), C.c_void_p(x.ctypes.data), m, (_ptr(m) if m is not None else None), True
     import torch
     assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2
     ld = _row_stride(tuple(x.shape), tuple(s * 8 for s in x.stride()), 8)
     if ld is None:
         x = x.contiguous()
         ld = x.shape[1]
-    ld = max(ld, x.shape[1])
     if ok is not None:
         assert ok.is_cuda and ok.dtype == torch.uint8 and ok.is_contiguous() and ok.shape == (x.shape[0],)
+    return (x, x.shape[0], max(ld, x.shape[1]), C.c_void_p(x.data_ptr()), ok,
+            (C.c_void_p(ok.data_ptr()) if ok is not None else None), False)
+
+
+def colselect(x, ranks, ok=None, stream=None):
+    """Order statistics of the columns of x [nrows, ncols]: -> [nranks, ncols], row r the values
+    np.sort(x[ok], axis=0)[ranks[r]] has, bit for bit.  ``x``: a float64 numpy array (host form: a rank at or above
+    the rows that count raises) or a float64 CUDA tensor (device form, asynchronous on torch's current stream: such a
+    rank gives NaN).  Rows may be padded (a view x[:, :ncols] of a wider array is read in place).  ``ok`` [nrows]:
+    rows with 0 do not exist.  At most 16 ranks, any order, duplicates allowed."""
+    r = np.ascontiguousarray(ranks, np.int64).ravel()
+    x, nrows, ld, xp, ok, okp, host = _matrix_arg(x, ok, "colselect")
+    if host:
+        out = np.zeros((r.size, x.shape[1]))
+        _check(trm.lib().bartrt_colselect(xp, nrows, x.shape[1], ld, okp, r.size, _ptr(r), _ptr(out)))
+        return out
+    import torch
     out = torch.empty((r.size, x.shape[1]), dtype=torch.float64, device=x.device)
-    _check(trm.lib().bartrt_colselect_dev(C.c_void_p(x.data_ptr()), x.shape[0], x.shape[1], ld,
-                                          C.c_void_p(ok.data_ptr()) if ok is not None else None, r.size, _ptr(r),
-                                          C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
+    _check(trm.lib().bartrt_colselect_dev(xp, nrows, x.shape[1], ld, okp, r.size, _ptr(r), C.c_void_p(out.data_ptr()),
+                                          _stream_ptr(stream)))
     return out
 
 
@@ -1045,33 +1053,6 @@ def marginals_set_chunk(rows: int) -> None:
     _check(trm.lib().bartrt_marginals_set_chunk(int(rows)))
 
 
-def _marginals_matrix(x, ok, who):
-    """(x, nrows, ld, x pointer, ok, ok pointer, is_host): x [nrows, ncols] float64, numpy or CUDA tensor, rows
-    contiguous (a padded view is read in place); ok [nrows] or None."""
-    if isinstance(x, np.ndarray):
-        if x.dtype != np.double or x.ndim != 2:
-            x = np.ascontiguousarray(x, np.double)
-            x = x.reshape(-1, x.shape[-1]) if x.ndim != 2 else x
-        ld = _row_stride(x.shape, x.strides, 8)
-        if ld is None:
-            x = np.ascontiguousarray(x)
-            ld = x.shape[1]
-        m = None if ok is None else np.ascontiguousarray(np.asarray(ok) != 0, np.uint8)
-        if m is not None and m.shape != (x.shape[0],):
-            raise ValueError(who + ": ok must have one entry per row")
-        return x, x.shape[0], max(ld, x.shape[1]), C.c_void_p(x.ctypes.data), m, (_ptr(m) if m is not None else None), True
-    import torch
-    assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2
-    ld = _row_stride(tuple(x.shape), tuple(s * 8 for s in x.stride()), 8)
-    if ld is None:
-        x = x.contiguous()
-        ld = x.shape[1]
-    if ok is not None:
-        assert ok.is_cuda and ok.dtype == torch.uint8 and ok.is_contiguous() and ok.shape == (x.shape[0],)
-    return (x, x.shape[0], max(ld, x.shape[1]), C.c_void_p(x.data_ptr()), ok,
-            (C.c_void_p(ok.data_ptr()) if ok is not None else None), False)
-
-
 def _marginals_cols(x, cols, who):
     c = np.ascontiguousarray(cols, np.int32).ravel()
     if c.size and (c.min() < 0 or c.max() >= x.shape[1]):
@@ -1085,7 +1066,7 @@ def marginals_range(x, cols, ok=None, stream=None):
     for bit; NaN, NaN, 0 for a column without one.  ``x``: a float64 numpy array (host form, uploaded in chunks) or a
     float64 CUDA tensor (device form, asynchronous on torch's current stream; the results are CUDA tensors, nfinite
     as int64).  Needs no engine."""
-    x, nrows, ld, xp, ok, okp, host = _marginals_matrix(x, ok, "marginals_range")
+    x, nrows, ld, xp, ok, okp, host = _matrix_arg(x, ok, "marginals_range")
     c = _marginals_cols(x, cols, "marginals_range")
     if host:
         lohi, nfin = np.zeros((c.size, 2)), np.zeros(c.size, np.uint64)
@@ -1107,7 +1088,7 @@ def marginals(x, cols, edges, pairs=True, ok=None, stream=None):
     (a, b) of selection indices, a < b, a-major, with bins=[edges[a], edges[b]] -- equal integers.  At most 64 columns,
     1024 bins, 128 bins with pairs.  ``x``: a float64 numpy array (host form: uploaded in chunks, uint64 results) or
     a float64 CUDA tensor (device form, asynchronous on torch's current stream, int64 CUDA tensors).  Needs no engine."""
-    x, nrows, ld, xp, ok, okp, host = _marginals_matrix(x, ok, "marginals")
+    x, nrows, ld, xp, ok, okp, host = _matrix_arg(x, ok, "marginals")
     c = _marginals_cols(x, cols, "marginals")
     e = np.ascontiguousarray(edges, np.double)
     if e.ndim != 2 or e.shape[0] != c.size or e.shape[1] < 2:

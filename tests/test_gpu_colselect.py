@@ -136,6 +136,58 @@ def test_same_bytes_twice_and_at_another_slab(eng):
     assert qr.same_bits(a, qr.sorted_ranks(x, ranks, ok))
 
 
+# ---- the engine's scratch serves one call at a time (csrc/scratch.hpp) -------------------------------------------
+def test_two_streams_share_the_scratch(eng):
+    """Two selections back to back on two streams, nothing waited for in between: two slabs and two column tiles each,
+    so that the slab merge and the global histogram both go through the scratch the calls share."""
+    import torch
+    n = eng.colselect_slab() + 1
+    xs = [_matrix(n, 65, seed=21), _matrix(n, 65, seed=22)]
+    ranks = [[0, n - 1, n // 2, n // 2, 7], [n // 3, 1, n - 2]]
+    want = [qr.sorted_ranks(x, r) for x, r in zip(xs, ranks)]
+    d_xs = [torch.from_numpy(x).cuda() for x in xs]
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    torch.cuda.synchronize()
+    got = []
+    for rep in range(8):
+        for i in ((0, 1) if rep % 2 == 0 else (1, 0)):
+            got.append((rep, i, eng.colselect(d_xs[i], ranks[i], stream=streams[i])))
+    torch.cuda.synchronize()
+    for rep, i, g in got:
+        assert qr.same_bits(g.cpu().numpy(), want[i]), (rep, i)
+
+
+def test_scratch_regrows_between_calls(eng, small_case):
+    """A new engine's scratch grows with the first call, grows again with a larger one while the first may still run,
+    and serves the first matrix again on another stream while the second may still run."""
+    import torch
+    from bart_amd import transit_module as trm
+    trm.free_memory()
+    eng.init(small_case.tcfg)                       # (the scratch is the engine's: empty again)
+    small, large = _matrix(65, 1, seed=31), _matrix(eng.colselect_slab() + 1, 100, seed=32)
+    r_small, r_large = [64, 0, 32], list(np.random.default_rng(33).integers(0, large.shape[0], 16))
+    d_small, d_large = torch.from_numpy(small).cuda(), torch.from_numpy(large).cuda()
+    side = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    first = eng.colselect(d_small, r_small)
+    second = eng.colselect(d_large, r_large)
+    third = eng.colselect(d_small, r_small, stream=side)
+    torch.cuda.synchronize()
+    first, second, third = (t.cpu().numpy() for t in (first, second, third))
+    assert qr.same_bits(first, qr.sorted_ranks(small, r_small)) and qr.same_bits(second, qr.sorted_ranks(large, r_large))
+    assert third.tobytes() == first.tobytes()
+
+
+def test_host_form_reads_no_further_than_the_last_column(eng):
+    """A padded matrix whose memory ends with the last column of its last row."""
+    nrows, ncols = 257, 7
+    ld = ncols + 5
+    flat = np.random.default_rng(41).normal(size=(nrows - 1) * ld + ncols)
+    x = np.lib.stride_tricks.as_strided(flat, (nrows, ncols), (8 * ld, 8))
+    ranks = [0, 256, 128, 1]
+    assert qr.same_bits(eng.colselect(x, ranks), qr.sorted_ranks(x, ranks))
+
+
 # ---- refusals: one test each ------------------------------------------------------------------------------------
 def _call(x, nrows, ncols, ld, ranks, dev=False):
     from bart_amd import transit_module as trm

@@ -185,6 +185,49 @@ def test_upload_chunks_of_100_rows_equal_the_device_form(eng):
     _assert_numpy(host, x, cols, edges, ok=ok)
 
 
+@pytest.mark.parametrize("chunk", [0, 100])
+def test_host_forms_read_no_further_than_the_last_selected_column(eng, chunk):
+    """A padded matrix whose memory ends with the last selected column of its last row; uploaded whole and in chunks of
+    100 rows, where only the last chunk ends early."""
+    nrows, cols = 257, [4, 1, 6]
+    ncols = max(cols) + 1
+    ld = ncols + 5
+    edges = _edges(3, 20)
+    flat = np.full((nrows - 1) * ld + ncols, np.nan)
+    x = np.lib.stride_tricks.as_strided(flat, (nrows, ncols), (8 * ld, 8))
+    for s, c in enumerate(cols):
+        x[:, c] = hr.column_for(edges[s], nrows, 4100 + s)
+    try:
+        eng.marginals_set_chunk(chunk)
+        got = eng.marginals(x, cols, edges)
+        lohi, nfin = eng.marginals_range(x, cols)
+    finally:
+        eng.marginals_set_chunk(0)
+    _assert_numpy(got, x, cols, edges)
+    want, wn = hr.numpy_range(x, cols)
+    assert np.array_equal(lohi.view(np.uint64), want.view(np.uint64)) and np.array_equal(nfin, wn)
+
+
+def test_device_and_host_calls_alternate_on_the_scratch(eng):
+    """marginals on a CUDA tensor and a side stream, marginals_range on the host array, three times over: both entry
+    points and both kinds of staging go through the one scratch (csrc/scratch.hpp)."""
+    import torch
+    cols = [2, 0, 1]
+    edges = _edges(3, 20)
+    x = hr.matrix_for(edges, 2 * SLAB + 1, 3, cols, seed=55)
+    d_x = torch.from_numpy(x).cuda()
+    side = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    want, wn = hr.numpy_range(x, cols)
+    for _ in range(3):
+        with torch.cuda.stream(side):              # (the results are made and zeroed on the stream the call runs on)
+            dev = eng.marginals(d_x, cols, edges)
+        lohi, nfin = eng.marginals_range(x, cols)
+        assert np.array_equal(lohi.view(np.uint64), want.view(np.uint64)) and np.array_equal(nfin, wn)
+        side.synchronize()
+        _assert_numpy([t.cpu().numpy().astype(np.uint64) for t in dev], x, cols, edges)
+
+
 def test_range_special_columns(eng):
     rng = np.random.default_rng(12)
     n = SLAB + 9
