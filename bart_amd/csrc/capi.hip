@@ -8,6 +8,7 @@
 #include "contrib.hpp"
 #include "engine.hpp"
 #include "hist.hpp"
+#include "kde.hpp"
 #include "lbl.hpp"
 #include "quant.hpp"
 #include "share.hpp"
@@ -1282,6 +1283,74 @@ int bartrt_hpd(const unsigned long long *counts, int nbins, double p, unsigned c
     hist::hpd(reinterpret_cast<const uint64_t *>(counts), nbins, p, mask, &thr, &inc, nruns);
     *threshold = thr;
     *included = inc;
+    return BARTRT_OK;
+  });
+}
+
+// ---- posterior kernel density estimates (kde.hip, kde_core.hpp): no engine ----
+static int kde_check(const char *who, const void *x, long nrows, long ld, int nsel, const int *cols, int ngrid,
+                     const double *grid, int rule, double factor, const void *pdf, const void *stat, const void *nonfinite) {
+  const std::string pre = std::string(who) + ": ";
+  if (!grid || !pdf || !stat || !nonfinite) return fail(BARTRT_EINVAL, pre + "null buffer (grid, pdf, stat, nonfinite)");
+  if (int rc = marginals_check_sel(pre, x, nrows, ld, nsel, cols)) return rc;
+  if (ngrid < 1 || ngrid > kde::kMaxGrid)
+    return fail(BARTRT_EINVAL, pre + "ngrid = " + std::to_string(ngrid) + " is outside 1.." + std::to_string(kde::kMaxGrid));
+  for (int s = 0; s < nsel; s++)
+    for (int j = 0; j < ngrid; j++)
+      if (!hist::is_finite(grid[(size_t)s * ngrid + j]))
+        return fail(BARTRT_EINVAL, pre + "grid[" + std::to_string(s) + "][" + std::to_string(j) + "] is not finite");
+  if (rule != kde::kScott && rule != kde::kSilverman && rule != kde::kFactor)
+    return fail(BARTRT_EINVAL, pre + "bw_rule = " + std::to_string(rule) + " is none of 0 (Scott), 1 (Silverman), 2 (bw_factor)");
+  if (rule == kde::kFactor && !(factor > 0.0 && hist::is_finite(factor)))
+    return fail(BARTRT_EINVAL, pre + "bw_factor = " + std::to_string(factor) + " is not a finite number above 0");
+  return BARTRT_OK;
+}
+
+int bartrt_kde_dev(const double *d_x, long nrows, long ld, const unsigned char *d_ok, int nsel, const int *cols, int ngrid,
+                   const double *grid, int bw_rule, double bw_factor, double *d_pdf, double *d_stat,
+                   unsigned long long *d_nonfinite, void *stream) {
+  if (int rc = kde_check("kde_dev", d_x, nrows, ld, nsel, cols, ngrid, grid, bw_rule, bw_factor, d_pdf, d_stat, d_nonfinite))
+    return rc;
+  return guarded([&] {
+    kde_dev(d_x, nrows, ld, d_ok, nsel, cols, ngrid, grid, bw_rule, bw_factor, d_pdf, d_stat, d_nonfinite, (hipStream_t)stream);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_kde(const double *x, long nrows, long ld, const unsigned char *ok, int nsel, const int *cols, int ngrid,
+               const double *grid, int bw_rule, double bw_factor, double *pdf, double *stat, unsigned long long *nonfinite) {
+  if (int rc = kde_check("kde", x, nrows, ld, nsel, cols, ngrid, grid, bw_rule, bw_factor, pdf, stat, nonfinite)) return rc;
+  return guarded([&] {
+    kde_host(x, nrows, ld, ok, nsel, cols, ngrid, grid, bw_rule, bw_factor, pdf, stat, nonfinite);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_kde_chunk(long *rows) {
+  if (!rows) return fail(BARTRT_EINVAL, "kde_chunk: null buffer");
+  *rows = kde_chunk();
+  return BARTRT_OK;
+}
+
+int bartrt_kde_set_chunk(long rows) {
+  return guarded([&] {
+    kde_set_chunk(rows);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_kde_tile(long *rows) {
+  if (!rows) return fail(BARTRT_EINVAL, "kde_tile: null buffer");
+  *rows = kde::kKdeTileRows;
+  return BARTRT_OK;
+}
+
+int bartrt_hpd_pdf(const double *pdf, int n, double p, unsigned char *mask, double *threshold, double *included, int *nruns) {
+  if (!pdf || !mask || !threshold || !included || !nruns) return fail(BARTRT_EINVAL, "hpd_pdf: null buffer");
+  if (n < 1) return fail(BARTRT_EINVAL, "hpd_pdf: n = " + std::to_string(n) + " is below 1");
+  if (!(p > 0.0 && p <= 1.0)) return fail(BARTRT_EINVAL, "hpd_pdf: p = " + std::to_string(p) + " is outside (0, 1]");
+  return guarded([&] {
+    kde::hpd_pdf(pdf, n, p, mask, threshold, included, nruns);
     return BARTRT_OK;
   });
 }

@@ -28,7 +28,7 @@
 // (the smallest count included), the included total and the number of maximal runs of included bins (2 for a bimodal
 // histogram cut between its modes).  N = 0: an empty mask and zeros.  This is MC3's credible region taken on the
 // HISTOGRAM instead of on a kernel density estimate: MC3 smooths the samples with a Gaussian KDE and thresholds the
-// density; here the density is the bin count.  No KDE is built.
+// density; here the density is the bin count (kde_core.hpp builds the KDE and takes the region on it with hpd_of).
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -132,20 +132,22 @@ inline void marginals_range(const double *x, long nrows, long ld, const unsigned
   }
 }
 
-// HPD above.  nbins >= 1, 0 < p <= 1 are the caller's to check.
-inline void hpd(const uint64_t *counts, int nbins, double p, unsigned char *mask, uint64_t *threshold, uint64_t *included,
-                int *nruns) {
+// HPD above, for counts (T = uint64_t) and for a density on a grid (T = double; kde_core.hpp states that rule).  The
+// total is the last cumulative sum IN THE DESCENDING ORDER: for integers any order gives the same number, for doubles
+// this one is the rule.  nbins >= 1, 0 < p <= 1 and values that are neither negative nor NaN are the caller's to check.
+template <class T>
+inline void hpd_of(const T *counts, int nbins, double p, unsigned char *mask, T *threshold, T *included, int *nruns) {
   std::fill(mask, mask + nbins, (unsigned char)0);
   *threshold = *included = 0;
   *nruns = 0;
-  uint64_t N = 0;
-  for (int i = 0; i < nbins; i++) N += counts[i];
-  if (N == 0) return;
   std::vector<int> order((size_t)nbins);
   for (int i = 0; i < nbins; i++) order[i] = i;
   std::sort(order.begin(), order.end(), [&](int a, int b) { return counts[a] != counts[b] ? counts[a] > counts[b] : a < b; });
+  T N = 0;
+  for (int k = 0; k < nbins; k++) N += counts[order[k]];
+  if (N == 0) return;
   const double want = p * (double)N;
-  uint64_t c = 0;
+  T c = 0;
   for (int k = 0; k < nbins; k++) {
     const int i = order[k];
     mask[i] = 1;
@@ -155,6 +157,11 @@ inline void hpd(const uint64_t *counts, int nbins, double p, unsigned char *mask
   }
   *included = c;
   for (int i = 0; i < nbins; i++) *nruns += mask[i] && (i == 0 || !mask[i - 1]);
+}
+
+inline void hpd(const uint64_t *counts, int nbins, double p, unsigned char *mask, uint64_t *threshold, uint64_t *included,
+                int *nruns) {
+  hpd_of(counts, nbins, p, mask, threshold, included, nruns);
 }
 
 }  // namespace hist

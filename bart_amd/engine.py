@@ -1118,3 +1118,82 @@ def hpd(counts, p: float):
     thr, inc, runs = C.c_ulonglong(), C.c_ulonglong(), C.c_int()
     _check(trm.lib().bartrt_hpd(_ptr(c), c.size, float(p), _ptr(mask), C.byref(thr), C.byref(inc), C.byref(runs)))
     return mask.astype(bool), thr.value, inc.value, runs.value
+
+
+# ---- posterior kernel density estimates (include/bartrt.h, bartrt_kde) ------------------------------------------
+KDE_RULES = {"scott": 0, "silverman": 1}
+
+
+def kde_tile() -> int:
+    """The rows of a tile of the density's sums, a constant of the rule (tests place their shapes around it)."""
+    rows = C.c_long()
+    _check(trm.lib().bartrt_kde_tile(C.byref(rows)))
+    return rows.value
+
+
+def kde_chunk() -> int:
+    rows = C.c_long()
+    _check(trm.lib().bartrt_kde_chunk(C.byref(rows)))
+    return rows.value
+
+
+def kde_set_chunk(rows: int) -> None:
+    """Rows per upload of the host form and per round of launches of either form (0: the default, 64 MiB).  For tests:
+    no result depends on it."""
+    _check(trm.lib().bartrt_kde_set_chunk(int(rows)))
+
+
+def _kde_rule(bw):
+    if isinstance(bw, str):
+        if bw not in KDE_RULES:
+            raise ValueError("kde: bw is 'scott', 'silverman' or a positive number")
+        return KDE_RULES[bw], 0.0
+    return 2, float(bw)
+
+
+def kde(x, cols, grid, bw="scott", ok=None, stream=None):
+    """Gaussian kernel density estimates of the columns ``cols`` of x [nrows, ncols], column cols[s] on grid[s]
+    (include/bartrt.h, bartrt_kde; the rule is csrc/kde_core.hpp's): -> (pdf [nsel, ngrid], stat [nsel, 4] = n, mean,
+    std (ddof 1), h, nonfinite [nsel]).  ``grid`` [nsel, ngrid] (host): finite values in any order, at most 1024 per
+    column.  ``bw``: 'scott', 'silverman' or a positive factor, as scipy.stats.gaussian_kde's bw_method; pdf[s] is
+    gaussian_kde(x[ok, cols[s]], bw)(grid[s]) over the finite values, to about 1e-13 relative (the RT kernels' exponential
+    is that far from exp).  A column with fewer than two finite values or
+    without spread has a NaN row and h = NaN.  ``x``: a float64 numpy array (host form: uploaded in chunks, twice) or a
+    float64 CUDA tensor (device form, asynchronous on torch's current stream; CUDA tensors come back, nonfinite as
+    int64).  kde_dev is the device form by name.  Needs no engine."""
+    x, nrows, ld, xp, ok, okp, host = _matrix_arg(x, ok, "kde")
+    c = _marginals_cols(x, cols, "kde")
+    g = np.ascontiguousarray(grid, np.double)
+    if g.ndim != 2 or g.shape[0] != c.size or g.shape[1] < 1:
+        raise ValueError("kde: grid must be [nsel, ngrid]")
+    rule, factor = _kde_rule(bw)
+    lib = trm.lib()
+    if host:
+        pdf, stat, bad = np.zeros(g.shape), np.zeros((c.size, 4)), np.zeros(c.size, np.uint64)
+        _check(lib.bartrt_kde(xp, nrows, ld, okp, c.size, _ptr(c), g.shape[1], _ptr(g), rule, factor, _ptr(pdf),
+                              _ptr(stat), _ptr(bad)))
+        return pdf, stat, bad
+    import torch
+    pdf = torch.zeros(g.shape, dtype=torch.float64, device=x.device)
+    stat = torch.zeros((c.size, 4), dtype=torch.float64, device=x.device)
+    bad = torch.zeros(c.size, dtype=torch.int64, device=x.device)
+    _check(lib.bartrt_kde_dev(xp, nrows, ld, okp, c.size, _ptr(c), g.shape[1], _ptr(g), rule, factor,
+                              C.c_void_p(pdf.data_ptr()), C.c_void_p(stat.data_ptr()), C.c_void_p(bad.data_ptr()),
+                              _stream_ptr(stream)))
+    return pdf, stat, bad
+
+
+def kde_dev(d_x, cols, grid, bw="scott", d_ok=None, stream=None):
+    """kde on a float64 CUDA tensor: asynchronous on ``stream`` (None: torch's current stream), CUDA tensors back."""
+    assert not isinstance(d_x, np.ndarray)
+    return kde(d_x, cols, grid, bw, d_ok, stream)
+
+
+def hpd_pdf(pdf, p: float):
+    """The credible region of a density on a grid at fraction 0 < p <= 1 (include/bartrt.h, bartrt_hpd_pdf; the rule is
+    csrc/kde_core.hpp's): -> (mask [n] bool, threshold, included, nruns).  On the host; needs no device."""
+    v = np.ascontiguousarray(pdf, np.double).ravel()
+    mask = np.zeros(v.size, np.uint8)
+    thr, inc, runs = C.c_double(), C.c_double(), C.c_int()
+    _check(trm.lib().bartrt_hpd_pdf(_ptr(v), v.size, float(p), _ptr(mask), C.byref(thr), C.byref(inc), C.byref(runs)))
+    return mask.astype(bool), thr.value, inc.value, runs.value

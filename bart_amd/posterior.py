@@ -15,6 +15,8 @@ over the stacked samples and equal to np.histogram / np.histogram2d (include/bar
 csrc/hist_core.hpp).  No engine is needed for these.
 
     marginals(output_npy, cfg_or_stepsize, burnin)   index, edges, hist, outside, pairs, hist2d, hpd_*, nsamples
+    marginals(..., kde=True)                         and kde_x, kde_pdf, kde_bw, mean, std, cr_*: the Gaussian kernel
+                                                     density of every parameter and its credible regions (bartrt_kde)
 
 Plots stay out of scope.
 """
@@ -76,7 +78,8 @@ def save(path, env):
 HPD_LEVELS = (0.6827, 0.9545)
 
 
-def marginals_of_samples(samples, index, nbins=20, ranges=None, levels=HPD_LEVELS):
+def marginals_of_samples(samples, index, nbins=20, ranges=None, levels=HPD_LEVELS, kde=False, kde_points=128,
+                         kde_bw="scott"):
     """The marginals of the columns ``index`` of full parameter vectors [n, npars] (numpy: uploaded in chunks; or a
     float64 CUDA tensor): see marginals for what comes back.  Needs no engine."""
     from . import engine
@@ -118,10 +121,36 @@ def marginals_of_samples(samples, index, nbins=20, ranges=None, levels=HPD_LEVEL
             if mask.any():
                 inc = np.nonzero(mask)[0]
                 out["hpd_lo"][l, s], out["hpd_hi"][l, s] = edges[s, inc[0]], edges[s, inc[-1] + 1]
+    if kde:
+        out.update(_kde_fields(samples, index, lohi, levels, int(kde_points), kde_bw))
     return out
 
 
-def marginals(output_npy, cfg_or_stepsize, burnin, thinning=1, nbins=20, ranges=None, levels=HPD_LEVELS, layout=None):
+def _kde_fields(samples, index, lohi, levels, npoints, bw):
+    """marginals' kde_* and cr_* fields: the density of every parameter on np.linspace over the histogram's range
+    (include/bartrt.h, bartrt_kde) and the credible regions of it (bartrt_hpd_pdf)."""
+    from . import engine
+    if not 1 <= npoints <= 1024:
+        raise ValueError("marginals: kde_points is a number of grid points: 1 .. 1024")
+    grid = np.stack([np.linspace(lo, hi, npoints) for lo, hi in lohi])
+    pdf, stat, _ = engine.kde(samples, index, grid, bw)
+    if not isinstance(samples, np.ndarray):
+        pdf, stat = pdf.cpu().numpy(), stat.cpu().numpy()
+    nfree, nlev = index.size, len(levels)
+    out = dict(kde_x=grid, kde_pdf=pdf, kde_bw=stat[:, 3].copy(), mean=stat[:, 1].copy(), std=stat[:, 2].copy(),
+               cr_mask=np.zeros((nlev, nfree, npoints), bool), cr_lo=np.full((nlev, nfree), np.nan),
+               cr_hi=np.full((nlev, nfree), np.nan), cr_runs=np.zeros((nlev, nfree), np.int64))
+    for l, p in enumerate(levels):
+        for s in range(nfree):
+            mask, _, _, runs = engine.hpd_pdf(pdf[s], p)
+            out["cr_mask"][l, s], out["cr_runs"][l, s] = mask, runs
+            if mask.any():
+                out["cr_lo"][l, s], out["cr_hi"][l, s] = grid[s, mask].min(), grid[s, mask].max()
+    return out
+
+
+def marginals(output_npy, cfg_or_stepsize, burnin, thinning=1, nbins=20, ranges=None, levels=HPD_LEVELS, layout=None,
+              kde=False, kde_points=128, kde_bw="scott"):
     """The numbers behind MC3's ``histogram`` and ``pairwise`` figures (reference code/mc3plots.py:45-82) from a
     finished chain: one 1-D histogram per free parameter, one 2-D histogram per pair of them, and the highest-density
     credible region of every parameter at each of ``levels`` -- counted on the GPU (include/bartrt.h, bartrt_marginals),
@@ -137,7 +166,15 @@ def marginals(output_npy, cfg_or_stepsize, burnin, thinning=1, nbins=20, ranges=
     a-major), ``hist2d`` [npairs, nbins, nbins] (first bin index: the first parameter of the pair), ``levels``, and per
     level ``hpd_mask`` [nlevels, nfree, nbins], ``hpd_lo`` / ``hpd_hi`` [nlevels, nfree] (the outer edges of the lowest
     and highest bin of the region, which ``hpd_runs`` [nlevels, nfree] says is one interval or several), ``nsamples``.
-    The region is taken on the histogram (csrc/hist_core.hpp), not on a kernel density estimate as MC3 does."""
+    The hpd_* region is taken on the histogram (csrc/hist_core.hpp).  ``kde`` = True adds the region MC3 reports, taken
+    on a Gaussian kernel density estimate of the samples (include/bartrt.h, bartrt_kde; csrc/kde_core.hpp): ``kde_x``
+    [nfree, kde_points] (np.linspace over the histogram's range of each parameter; at most 1024 points), ``kde_pdf``
+    (scipy.stats.gaussian_kde(samples, kde_bw)(kde_x) over the finite samples; ``kde_bw``: 'scott', 'silverman' or a
+    factor; NaN for a parameter that never moved), ``kde_bw`` [nfree] (the bandwidth h), ``mean``, ``std`` (ddof 1), and
+    per level ``cr_mask`` [nlevels, nfree, kde_points], ``cr_lo`` / ``cr_hi`` (the smallest and largest grid value in
+    the region) and ``cr_runs``.  The region's rule (bartrt_hpd_pdf) is this project's, stated against SciPy's density:
+    MC3's own could not be read.  Every other key is what it is without ``kde``.  Pairwise panels stay histograms (MC3
+    draws them from histogram2d); weighted samples are not served."""
     if isinstance(cfg_or_stepsize, (str, bytes, os.PathLike)):
         params, stepsize = cf._mcmc_vectors(cfg_or_stepsize)
     else:
@@ -145,4 +182,4 @@ def marginals(output_npy, cfg_or_stepsize, burnin, thinning=1, nbins=20, ranges=
         params = np.zeros_like(stepsize)         # (fixed parameters are not histogrammed: any value serves)
     data = np.load(output_npy) if isinstance(output_npy, (str, bytes, os.PathLike)) else output_npy
     samples = cf.posterior_samples(data, params, stepsize, burnin, thinning, layout)
-    return marginals_of_samples(samples, np.nonzero(stepsize > 0)[0], nbins, ranges, levels)
+    return marginals_of_samples(samples, np.nonzero(stepsize > 0)[0], nbins, ranges, levels, kde, kde_points, kde_bw)

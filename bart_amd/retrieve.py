@@ -250,7 +250,16 @@ def main(argv=None):
                          "unif or --datasets)")
     ap.add_argument("--marginals-bins", type=int, default=20, metavar="N",
                     help="with --marginals: bins per parameter (default 20, MC3's own)")
+    ap.add_argument("--marginals-kde", action="store_true",
+                    help="with --marginals: add every free parameter's Gaussian kernel density estimate and the credible "
+                         "regions taken on it (kde_x, kde_pdf, kde_bw, mean, std, cr_*; bart_amd.posterior.marginals)")
+    ap.add_argument("--marginals-kde-points", type=int, default=128, metavar="N",
+                    help="with --marginals-kde: grid points per parameter (default 128; 1 .. 1024)")
     a = ap.parse_args(argv)
+    if a.marginals_kde and not a.marginals:
+        ap.error("--marginals-kde adds to the file --marginals writes: name it with --marginals FILE.npz")
+    if a.marginals_kde and not 1 <= a.marginals_kde_points <= 1024:
+        ap.error("--marginals-kde-points is a number of grid points: 1 .. 1024")
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -428,7 +437,8 @@ def main(argv=None):
         rows = min(int(scfg.burnin) // thin, res["chain"].shape[1] - 1)
         samples = cf.posterior_samples(res["chain"], scfg.params, scfg.stepsize, rows, layout="retrieve")
         free = np.nonzero(np.asarray(scfg.stepsize) > 0)[0]
-        marg = dict(posterior.marginals_of_samples(samples, free, a.marginals_bins), burnin=rows)
+        marg = dict(posterior.marginals_of_samples(samples, free, a.marginals_bins, kde=a.marginals_kde,
+                                                   kde_points=a.marginals_kde_points), burnin=rows)
         if rank == 0:
             posterior.save(os.path.join(out, a.marginals), marg)
         res["marginals"] = marg

@@ -171,6 +171,13 @@ def lib():
             L.bartrt_marginals_chunk.argtypes = [C.POINTER(C.c_long)]
             L.bartrt_marginals_set_chunk.argtypes = [C.c_long]
             L.bartrt_hpd.argtypes = [p, i, d, p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(i)]
+        if hasattr(L, "bartrt_kde"):
+            L.bartrt_kde_dev.argtypes = [p, C.c_long, C.c_long, p, i, p, i, p, i, d, p, p, p, p]
+            L.bartrt_kde.argtypes = [p, C.c_long, C.c_long, p, i, p, i, p, i, d, p, p, p]
+            L.bartrt_kde_chunk.argtypes = [C.POINTER(C.c_long)]
+            L.bartrt_kde_set_chunk.argtypes = [C.c_long]
+            L.bartrt_kde_tile.argtypes = [C.POINTER(C.c_long)]
+            L.bartrt_hpd_pdf.argtypes = [p, i, d, p, C.POINTER(d), C.POINTER(d), C.POINTER(i)]
         L.bartrt_algorithmic_bytes.argtypes = [i]
         L.bartrt_algorithmic_bytes.restype = d
         _lib = L

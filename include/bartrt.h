@@ -924,7 +924,8 @@ int bartrt_percentile_lerp(const double *a, const double *b, double w, double *o
  * c has (double)c >= p * (double)N, N = sum(counts).  mask[nbins] (1: included), *threshold the smallest count
  * included, *included the region's total, *nruns its number of maximal runs of bins (2: bimodal).  N == 0: an
  * empty mask and zeros.  This is MC3's credible region taken on the histogram instead of on a kernel density
- * estimate; no KDE is built.  BARTRT_EINVAL: nbins < 1, p outside (0, 1], a NULL buffer. */
+ * estimate; the estimate itself is bartrt_kde below, and bartrt_hpd_pdf takes the region on it.  BARTRT_EINVAL:
+ * nbins < 1, p outside (0, 1], a NULL buffer. */
 int bartrt_marginals_dev(const double *d_x, long nrows, long ld, const unsigned char *d_ok, int nsel,
                          const int *cols, int nbins, const double *edges, unsigned long long *d_h1,
                          unsigned long long *d_out, unsigned long long *d_h2, void *stream);
@@ -941,6 +942,66 @@ int bartrt_marginals_chunk(long *rows);
 int bartrt_marginals_set_chunk(long rows);
 int bartrt_hpd(const unsigned long long *counts, int nbins, double p, unsigned char *mask,
                unsigned long long *threshold, unsigned long long *included, int *nruns);
+
+/* ---- posterior kernel density estimates (csrc/kde.hip; the rule is csrc/kde_core.hpp's) ---------------------
+ * The density MC3 thresholds for a parameter's credible region: a Gaussian KDE of the samples of one column,
+ * scipy.stats.gaussian_kde(col, bw_method)(grid) for one dimension.  NO ENGINE is needed; the calls own their
+ * scratch on the current HIP device.
+ * bartrt_kde_dev: densities of selected columns of a row-major matrix in device memory, each on its own grid.
+ *   d_x[nrows][ld], d_ok[nrows] or NULL, cols[nsel]   as bartrt_marginals_dev takes them (cols a HOST array,
+ *                    1 <= nsel <= 64).  A row counts for a column iff d_ok lets it AND the value is finite.
+ *   grid[nsel][ngrid]  HOST array, 1 <= ngrid <= 1024 finite values per selected column, in any order, uniform or
+ *                    not.
+ *   bw_rule, bw_factor   the bandwidth h = factor * std: 0 Scott's factor n^(-1/5), 1 Silverman's (3 n / 4)^(-1/5),
+ *                    2 bw_factor itself (> 0) -- scipy's bw_method = 'scott' | 'silverman' | scalar.
+ *   d_pdf[nsel][ngrid]   pdf(g) = sum_i exp(-((g - x_i) / h)^2 / 2) / (n h sqrt(2 pi)) over the rows that count.
+ *                    The exponential is the RT kernels' exp_rt, whose formula is within 7e-14 relative of exp
+ *                    (its interpolant) plus 2.3e-17 per unit of |argument| / ln 2 (its rounded ln 2), and whose
+ *                    fp64 evaluation is within 4e-16 of that formula: a density is within about 1e-13 relative of
+ *                    the one taken with exp, not within rounding.  A term whose argument is below -708 is zero.
+ *   d_stat[nsel][4]  n (as a double), mean, std (ddof 1), h.  The moments come from tiled (n, mean, M2) triples of
+ *                    the values less the column's value in row 0, merged in ascending order: no sum of squares.
+ *                    Row 0's value is taken whatever d_ok says of it (0.0 if it is not finite): mean and std are
+ *                    as accurate as max |x - x[0]| / std allows, so a first row that holds a wild finite value (a
+ *                    sentinel like 1e300), masked or not, takes digits from the std of an otherwise good column.
+ *   d_nonfinite[nsel]  unsigned 64-bit: rows d_ok lets through whose value is an infinity or a NaN.  They are
+ *                    counted here and otherwise do not exist (scipy would return NaN everywhere).
+ * A column with n < 2, or whose std or h is zero or not finite, has h = NaN and a pdf row of NaN; the call
+ * succeeds and the other columns are not affected.  The order of every floating-point sum is fixed by the rule
+ * (tiles of bartrt_kde_tile consecutive rows of the matrix, rows ascending in a tile, tiles ascending) and there
+ * are no floating-point atomics: the bits depend on no launch shape, chunk or schedule.  Asynchronous on
+ * `stream` (NULL: the null stream).  One call at a time uses the scratch: a call first waits, on the host, for
+ * the device work of the previous one.
+ *   BARTRT_EINVAL    (the message names the argument; the outputs are not touched) nsel outside 1..64; a column
+ *                    outside [0, ld); ngrid outside 1..1024; a grid value that is not finite; nrows < 1 or above
+ *                    2^31 - 1; a NULL buffer other than d_ok; a bw_rule outside 0..2; bw_rule 2 with a bw_factor
+ *                    that is not a finite number above 0.
+ * bartrt_kde: the same from and to host memory.  The matrix goes up twice in row chunks of whole tiles (64 MiB or
+ * one tile of rows, whichever is larger -- one tile is 16 kB times ld, above 64 MiB for ld > 4096 -- or
+ * bartrt_kde_set_chunk rows rounded up to a tile), first for the moments, then for the sums; the whole matrix
+ * is never needed in HBM.  The last row need only reach its last selected column.  Waits.
+ * bartrt_kde_chunk / _set_chunk: the rows per upload of the host form, which also bound the rows one round of
+ * launches of either form covers (0: the default, by bytes).  For tests: no result depends on it.
+ * bartrt_kde_tile: the rows of a tile, a constant of the rule (tests place their shapes around it).
+ * bartrt_hpd_pdf (host, no device): the credible region of a density pdf[n] on a grid at fraction 0 < p <= 1,
+ * bartrt_hpd's sibling on doubles.  The points are ordered by descending pdf, ties by ascending index; cumulative
+ * sums are formed in that order by plain additions and the total is the last of them; the region is the shortest
+ * prefix whose sum c has c >= p * total.  mask[n], *threshold the smallest pdf included, *included the region's
+ * sum, *nruns its number of maximal runs.  A NaN or a negative value, or total == 0: an empty mask and zeros.
+ * The rule is this project's: MC3's credregion could not be read (the reference's MC3 submodule is empty), so
+ * it is stated against SciPy's density and not checked against MC3's source.  BARTRT_EINVAL: n < 1, p outside
+ * (0, 1], a NULL buffer. */
+int bartrt_kde_dev(const double *d_x, long nrows, long ld, const unsigned char *d_ok, int nsel, const int *cols,
+                   int ngrid, const double *grid, int bw_rule, double bw_factor, double *d_pdf, double *d_stat,
+                   unsigned long long *d_nonfinite, void *stream);
+int bartrt_kde(const double *x, long nrows, long ld, const unsigned char *ok, int nsel, const int *cols, int ngrid,
+               const double *grid, int bw_rule, double bw_factor, double *pdf, double *stat,
+               unsigned long long *nonfinite);
+int bartrt_kde_chunk(long *rows);
+int bartrt_kde_set_chunk(long rows);
+int bartrt_kde_tile(long *rows);
+int bartrt_hpd_pdf(const double *pdf, int n, double p, unsigned char *mask, double *threshold, double *included,
+                   int *nruns);
 
 /* Line-by-line engines only (cfg has `linedb`, no `opacityfile`): the Voigt
  * extinction of one profile, ext[nlayers][nwave_local] in cm-1, atm layer order. */
