@@ -12,8 +12,8 @@ LIB = os.path.join(HERE, "libbartrt.so")
 CLI = os.path.join(HERE, "transit")
 SOURCES = ["rt_eclipse_angles.hip", "rt_eclipse_slant_ilp.hip", "rt_eclipse_qadj.hip", "rt_eclipse_i0.hip", "rt_eclipse_i1.hip", "rt_eclipse_i2.hip", "rt_eclipse_i0_ilp.hip", "rt_eclipse_i1_ilp.hip", "lbl.hip",
            "transit_geom.hip", "contrib.hip",
-           "kernels.hip", "capi.hip", "engine.hip", "step.hip", "comm.hip", "mcmc.hip", "grid.hip", "fit.hip", "quant.hip", "hist.hip", "kde.hip", "share.hip", "svc.hip", "rtc.hip", "io.cpp"]   # longest first
-HEADERS = ["engine.hpp", "kernels.hpp", "rt_eclipse.hpp", "rt_launch.hpp", "rt_eclipse_unit.inc", "rt_eclipse_s1.hpp", "rt_eclipse_s1s.hpp", "rt_eclipse_qadj.hpp", "kernel_table.inc", "imw_tab.hpp", "integ.hpp", "step.hpp", "retrieval.hpp", "retrieval_host.hpp", "mcmc_core.hpp", "grid_core.hpp", "gr_core.hpp", "ess_core.hpp", "quant_core.hpp", "quant.hpp", "hist_core.hpp", "hist.hpp", "kde_core.hpp", "kde.hpp", "fit_core.hpp", "lbl.hpp", "voigt_coef.hpp", "expint_coef.hpp", "prep.hpp", "io.hpp", "share.hpp", "svc.hpp", "svc_core.hpp", "rtc.hpp", "contrib.hpp", "comm.hpp", "devbuf.hpp", "scratch.hpp", "lds.hpp",
+           "kernels.hip", "capi.hip", "engine.hip", "step.hip", "comm.hip", "mcmc.hip", "grid.hip", "fit.hip", "quant.hip", "specenv.hip", "hist.hip", "kde.hip", "share.hip", "svc.hip", "rtc.hip", "io.cpp"]   # longest first
+HEADERS = ["engine.hpp", "kernels.hpp", "rt_eclipse.hpp", "rt_launch.hpp", "rt_eclipse_unit.inc", "rt_eclipse_s1.hpp", "rt_eclipse_s1s.hpp", "rt_eclipse_qadj.hpp", "kernel_table.inc", "imw_tab.hpp", "integ.hpp", "step.hpp", "retrieval.hpp", "retrieval_host.hpp", "mcmc_core.hpp", "grid_core.hpp", "gr_core.hpp", "ess_core.hpp", "quant_core.hpp", "quant.hpp", "hist_core.hpp", "hist.hpp", "kde_core.hpp", "kde.hpp", "specenv_core.hpp", "specenv.hpp", "fit_core.hpp", "lbl.hpp", "voigt_coef.hpp", "expint_coef.hpp", "prep.hpp", "io.hpp", "share.hpp", "svc.hpp", "svc_core.hpp", "rtc.hpp", "contrib.hpp", "comm.hpp", "devbuf.hpp", "scratch.hpp", "lds.hpp",
            "transit_main.cpp", "../../include/bartrt.h"]
 
 

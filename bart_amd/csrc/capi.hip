@@ -12,6 +12,7 @@
 #include "lbl.hpp"
 #include "quant.hpp"
 #include "share.hpp"
+#include "specenv.hpp"
 #include "step.hpp"
 #include "rt_launch.hpp"
 #include "rtc.hpp"
@@ -1171,6 +1172,105 @@ int bartrt_percentile_lerp(const double *a, const double *b, double w, double *o
   if (!a || !b || !out) return fail(BARTRT_EINVAL, "percentile_lerp: null buffer");
   for (long i = 0; i < n; i++) out[i] = quant::interpolate(a[i], b[i], w);
   return BARTRT_OK;
+}
+
+// ---- posterior spectra (specenv.hip, specenv_core.hpp) -------------------
+// the display rule's arguments, each refusal named
+static int display_check(const std::string &pre, int r, long stride) {
+  if (r < 0 || r > specenv::kMaxRadius)
+    return fail(BARTRT_EINVAL, pre + "r = " + std::to_string(r) + " is outside 0.." + std::to_string(specenv::kMaxRadius));
+  if (stride < 1) return fail(BARTRT_EINVAL, pre + "stride = " + std::to_string(stride) + " is below 1");
+  return BARTRT_OK;
+}
+
+// what the posterior spectrum calls need of the engine: the whole grid on this GPU, and the step
+static int spectrum_needs(const Engine *e, const std::string &pre) {
+  if (e->lo != 0 || e->hi != e->Wfull)
+    return fail(BARTRT_ENOTSUP, pre + "wavenumber-sharded engines are not supported: the spectra are not whole on this GPU "
+                                      "(an engine on the whole grid serves the call)");
+  if (!e->step) return fail(BARTRT_EINVAL, pre + "call bartrt_step_setup first");
+  return BARTRT_OK;
+}
+
+int bartrt_spectrum_display_dev(const double *d_spec, long nrows, int nwave, long ld, const double *d_sflux, double rprs,
+                                int r, const double *half, long stride, double *d_out, long ldo, void *stream) {
+  NEED_ENGINE();
+  const std::string pre = "spectrum_display_dev: ";
+  if (int rc = display_check(pre, r, stride)) return rc;
+  if (!d_spec || !d_out || !half) return fail(BARTRT_EINVAL, pre + "null buffer (d_spec, half, d_out)");
+  if (nrows < 1) return fail(BARTRT_EINVAL, pre + "nrows = " + std::to_string(nrows) + " is below 1");
+  if (nwave < 1) return fail(BARTRT_EINVAL, pre + "nwave = " + std::to_string(nwave) + " is below 1");
+  if (ld < nwave) return fail(BARTRT_EINVAL, pre + "ld = " + std::to_string(ld) + " is below nwave = " + std::to_string(nwave));
+  const long Wk = specenv::kept_columns(nwave, stride);
+  if (ldo < Wk) return fail(BARTRT_EINVAL, pre + "ldo = " + std::to_string(ldo) + " is below Wk = " + std::to_string(Wk));
+  return guarded([&] {
+    spectrum_display_dev(d_spec, nrows, nwave, ld, d_sflux, rprs, r, half, stride, d_out, ldo, stream_of(stream));
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_spectrum_display_tile(int r, long stride, long *cols) {
+  if (!cols) return fail(BARTRT_EINVAL, "spectrum_display_tile: null buffer");
+  if (int rc = display_check("spectrum_display_tile: ", r, stride)) return rc;
+  *cols = spec_tile_out(r, stride);
+  return BARTRT_OK;
+}
+
+int bartrt_posterior_spectrum(const double *params, long nsamples, int npars, int nq, const double *q, const double *sflux,
+                              int r, const double *half, long stride, double *env_spec, double *env_band, int *status,
+                              long *ngood) {
+  NEED_ENGINE();
+  Engine *e = g_eng;
+  const std::string pre = "posterior_spectrum: ";
+  if (int rc = spectrum_needs(e, pre)) return rc;
+  if (int rc = display_check(pre, r, stride)) return rc;
+  if (!params || !q || !half || !env_spec || !env_band || !status || !ngood) return fail(BARTRT_EINVAL, pre + "null buffer");
+  if (nsamples < 1 || nsamples > kQuantMaxRows)
+    return fail(BARTRT_EINVAL, pre + "nsamples = " + std::to_string(nsamples) + " is outside 1.." + std::to_string(kQuantMaxRows));
+  if (nq < 1 || nq > quant::kMaxPercents)
+    return fail(BARTRT_EINVAL, pre + "nq = " + std::to_string(nq) + " is outside 1.." + std::to_string(quant::kMaxPercents));
+  for (int i = 0; i < nq; i++)
+    if (!(q[i] >= 0.0 && q[i] <= 100.0))
+      return fail(BARTRT_EINVAL, pre + "q[" + std::to_string(i) + "] = " + std::to_string(q[i]) + " is outside 0..100");
+  if (npars != step_npars(*e))
+    return fail(BARTRT_EINVAL, pre + "npars must be nPT + (radius, cloud top, scattering parameters declared with "
+                                     "step_set_extras) + nmolfit");
+  if (specenv::kept_columns(e->Wfull, stride) > kQuantMaxCols)
+    return fail(BARTRT_EINVAL, pre + "more than " + std::to_string(kQuantMaxCols) + " kept columns: raise stride");
+  return guarded([&] {
+    posterior_spectrum(*e, params, nsamples, npars, nq, q, sflux, r, half, stride, env_spec, env_band, status, ngood);
+    return BARTRT_OK;
+  });
+}
+
+int bartrt_posterior_spectrum_shape(long stride, long *Wk, int *F) {
+  NEED_ENGINE();
+  if (int rc = spectrum_needs(g_eng, "posterior_spectrum_shape: ")) return rc;
+  if (int rc = display_check("posterior_spectrum_shape: ", 0, stride)) return rc;
+  if (!Wk || !F) return fail(BARTRT_EINVAL, "posterior_spectrum_shape: null buffer");
+  *Wk = specenv::kept_columns(g_eng->Wfull, stride);
+  *F = g_eng->step->nfilters;
+  return BARTRT_OK;
+}
+
+int bartrt_posterior_spectrum_order(int nq, long Wk, int F, long *ranks, double *order_spec, double *order_band) {
+  NEED_ENGINE();
+  if (!ranks || !order_spec || !order_band) return fail(BARTRT_EINVAL, "posterior_spectrum_order: null buffer");
+  if (!posterior_spectrum_order(*g_eng, nq, Wk, F, ranks, order_spec, order_band))
+    return fail(BARTRT_EINVAL, "posterior_spectrum_order: no envelope of that shape (no bartrt_posterior_spectrum yet, no "
+                               "accepted sample, or another nq / Wk / F)");
+  return BARTRT_OK;
+}
+
+int bartrt_posterior_spectrum_rows(long row0, long nrows, double *out) {
+  NEED_ENGINE();
+  if (!out) return fail(BARTRT_EINVAL, "posterior_spectrum_rows: null buffer");
+  return guarded([&] {
+    if (!posterior_spectrum_rows(*g_eng, row0, nrows, out))
+      return fail(BARTRT_EINVAL, "posterior_spectrum_rows: rows " + std::to_string(row0) + " .. " + std::to_string(row0 + nrows) +
+                                     " are outside the latest sample matrix (no bartrt_posterior_spectrum yet, or another range)");
+    return BARTRT_OK;
+  });
 }
 
 // ---- posterior marginals (hist.hip, hist_core.hpp): no engine ------------

@@ -7,6 +7,7 @@
 #include "contrib.hpp"
 #include "quant.hpp"
 #include "share.hpp"
+#include "specenv.hpp"
 #include "step.hpp"
 #include "svc.hpp"
 
@@ -33,6 +34,7 @@ Engine::~Engine() {
   delete lbl;
   cf_release(*this);
   quant_release(*this);
+  specenv_release(*this);
   if (kappa_share) { kappa_share->release(); kappa_share = nullptr; }
 }
 

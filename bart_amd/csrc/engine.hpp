@@ -30,6 +30,7 @@ struct Lbl;       // line-by-line extinction (lbl.hip)
 struct Comm;      // the ranks' communicator (comm.hpp)
 struct CfState;   // contribution-function tables and workspaces (contrib.hip)
 struct QuantState;  // scratch of the order statistics and the posterior envelope (quant.hip)
+struct SpecEnvState;  // the display matrix and the scratch of the posterior spectrum envelope (specenv.hip)
 
 // The stream and the timing events, as a base of Engine: a base outlives the members, so every buffer the engine
 // owns (DevBuf / PinBuf members, freed by their own destructors) goes before the events, and the stream goes last.
@@ -234,6 +235,7 @@ struct Engine : EngineStream {
   unsigned long long ncollectives = 0;  // collectives this engine has issued (kept across bartrt_comm_free)
 
   QuantState *quant = nullptr;  // owned, null until a selection call (quant_release)
+  SpecEnvState *specenv = nullptr;  // owned, null until a posterior_spectrum call (specenv_release)
 };
 
 }  // namespace bartrt

@@ -246,13 +246,15 @@ void colselect_host(Engine &e, const double *x, long nrows, int ncols, long ld, 
 
 void posterior_set_chunk(Engine &e, long rows) { Scratch::set_rows(state_of(e).chunk_rows, "posterior_set_chunk", rows); }
 
+long posterior_chunk(const Engine &e) { return e.quant && e.quant->chunk_rows > 0 ? e.quant->chunk_rows : kDefaultChunk; }
+
 void posterior_tp(Engine &e, const double *params, long nsamples, int npars, int nq, const double *pct, double *env,
                   int *status, long *ngood) {
   QuantState &q = state_of(e);
   hipStream_t st = e.stream;
   const int L = e.L;
   const size_t nprof = (size_t)(e.S + 1) * L;
-  const long chunk = std::min(nsamples, q.chunk_rows > 0 ? q.chunk_rows : kDefaultChunk);
+  const long chunk = std::min(nsamples, posterior_chunk(e));
   q.room(q.params, (size_t)chunk * npars);
   q.room(q.prof, (size_t)chunk * nprof);
   q.room(q.temp, (size_t)nsamples * L);

@@ -34,6 +34,7 @@ void posterior_tp(Engine &e, const double *params, long nsamples, int npars, int
 bool posterior_tp_order(const Engine &e, int nq, int nlayers, long *ranks, double *order);
 // rows per chunk of posterior_tp (0: the default); the envelope does not depend on it
 void posterior_set_chunk(Engine &e, long rows);
+long posterior_chunk(const Engine &e);   // the rows per chunk in force (the default where none is set)
 // rows per workgroup of the selection (0: kQuantSlabRows), for tests: the result does not depend on it
 void colselect_set_slab(Engine &e, long rows);
 long colselect_slab(const Engine &e);

@@ -76,8 +76,10 @@ void step_bandflux_blocks_dev(Engine &e, const double *d_blocks, int nranks, int
                               double *d_bandflux, hipStream_t st, int *status_out = nullptr);
 // with a communicator attached (e.comm), the RT block, one all-gather and the block integration; without one the
 // engine must hold the whole grid
+// sel_walkers > n: the walker count the RT kernel variant is chosen for instead of n (RunRequest::sel_walkers), so that
+// a caller that cuts one set of rows into launches of any size gets the same bits from each
 void step_run_dev(Engine &e, const double *d_params, int n, int npars, double *d_bandflux,
-                  int *d_status, double *d_spec, hipStream_t st, int *status_out = nullptr);
+                  int *d_status, double *d_spec, hipStream_t st, int *status_out = nullptr, int sel_walkers = 0);
 void step_run_host(Engine &e, const double *params, int n, int npars, double *bandflux,
                    int *status);
 // diagnostics (bartrt_expint_e2): the T(p) kernels' exponential integral E_2 on n host values; needs no engine

@@ -1035,6 +1035,96 @@ def posterior_tp(params, q, chunk=None, want_order=False):
     return env, status, ngood.value, ranks, order
 
 
+# ---- posterior spectra: the display quantity and its envelopes (include/bartrt.h, bartrt_posterior_spectrum) ----
+def _display_args(half, stride):
+    half = np.ascontiguousarray(half, np.double).ravel()
+    if half.size < 1:
+        raise ValueError("the half kernel holds at least its centre weight")
+    return half, half.size - 1, int(stride)
+
+
+def spectrum_display_tile(r: int, stride: int = 1) -> int:
+    """The kept output columns one workgroup of the display kernel owns (tests place their shapes around it)."""
+    cols = C.c_long()
+    _check(trm.lib().bartrt_spectrum_display_tile(int(r), int(stride), C.byref(cols)))
+    return cols.value
+
+
+def spectrum_display_dev(d_spec, half, d_sflux=None, rprs=1.0, stride=1, nwave=None, stream=None):
+    """The display quantity of the spectra d_spec [nrows, >= nwave] (float64 CUDA tensor, rows contiguous; a padded view
+    is read in place): -> [nrows, ceil(nwave / stride)] CUDA tensor, asynchronous on torch's current stream.  With
+    ``d_sflux`` [nwave] the rows are x / sflux * rprs * rprs before the smoothing; ``half`` [r + 1]: the symmetric
+    kernel's half, centre first (posterior.gauss_half); csrc/specenv_core.hpp has the rule."""
+    import torch
+    half, r, stride = _display_args(half, stride)
+    assert d_spec.is_cuda and d_spec.dtype == torch.float64 and d_spec.dim() == 2
+    ld = _row_stride(tuple(d_spec.shape), tuple(s * 8 for s in d_spec.stride()), 8)
+    if ld is None:
+        d_spec = d_spec.contiguous()
+        ld = d_spec.shape[1]
+    nwave = d_spec.shape[1] if nwave is None else int(nwave)
+    if d_sflux is not None:
+        assert d_sflux.is_cuda and d_sflux.dtype == torch.float64 and d_sflux.is_contiguous() and d_sflux.numel() >= nwave
+    wk = -(-nwave // stride) if stride >= 1 and nwave >= 1 else 1
+    out = torch.empty((d_spec.shape[0], wk), dtype=torch.float64, device=d_spec.device)
+    _check(trm.lib().bartrt_spectrum_display_dev(
+        C.c_void_p(d_spec.data_ptr()), d_spec.shape[0], nwave, max(ld, d_spec.shape[1]),
+        C.c_void_p(d_sflux.data_ptr()) if d_sflux is not None else None, float(rprs), r, _ptr(half), stride,
+        C.c_void_p(out.data_ptr()), wk, _stream_ptr(stream)))
+    return out
+
+
+def posterior_spectrum(params, q, sflux, half, stride=1, chunk=None, want_order=False):
+    """The percentile envelopes of the display quantity and of the band fluxes of parameter vectors [nsamples, npars]
+    as step_batch takes them (after step_setup, whose rprs and filters are used; include/bartrt.h,
+    bartrt_posterior_spectrum): -> (env_spec [nq, Wk], env_band [nq, F], status [nsamples], ngood); with ``want_order``
+    also (ranks [2 nq], order_spec [2 nq, Wk], order_band [2 nq, F]), the order statistics behind the envelopes (None
+    each when no sample was accepted).  ``sflux`` [nwave]: the stellar flux on the engine's grid (eclipse) or None;
+    ``half``: the smoothing kernel's half; ``stride``: every stride-th grid sample is kept, Wk = ceil(nwave / stride),
+    and the sample matrix takes nsamples * Wk * 8 bytes of device memory.  ``chunk``: rows per launch, at most 4096 (a
+    larger value is cut to that); the result does not depend on it, because every launch's RT kernel variant is chosen
+    as for 4096 rows -- which is also why a sample's spectrum here can differ in the last bits from step_batch_dev's
+    on a small batch."""
+    p = np.ascontiguousarray(params, np.double)
+    p = p.reshape(-1, p.shape[-1])
+    qs = np.ascontiguousarray(np.atleast_1d(q), np.double)
+    half, r, stride = _display_args(half, stride)
+    wk, nf = C.c_long(), C.c_int()
+    _check(trm.lib().bartrt_posterior_spectrum_shape(stride, C.byref(wk), C.byref(nf)))
+    wk, nf = wk.value, nf.value
+    if sflux is not None:
+        sflux = np.ascontiguousarray(sflux, np.double).ravel()
+        if sflux.size != trm.get_no_samples():
+            raise ValueError("posterior_spectrum: sflux has one value per sample of the engine's grid")
+    env_spec, env_band = np.zeros((qs.size, wk)), np.zeros((qs.size, nf))
+    status = np.zeros(p.shape[0], np.int32)
+    ngood = C.c_long()
+    if chunk is not None:
+        posterior_set_chunk(chunk)
+    try:
+        _check(trm.lib().bartrt_posterior_spectrum(
+            _ptr(p), p.shape[0], p.shape[1], qs.size, _ptr(qs), _ptr(sflux) if sflux is not None else None, r,
+            _ptr(half), stride, _ptr(env_spec), _ptr(env_band), _ptr(status), C.byref(ngood)))
+    finally:
+        if chunk is not None:
+            posterior_set_chunk(0)
+    if not want_order:
+        return env_spec, env_band, status, ngood.value
+    if ngood.value == 0:
+        return env_spec, env_band, status, 0, None, None, None
+    ranks, ospec, oband = np.zeros(2 * qs.size, np.int64), np.zeros((2 * qs.size, wk)), np.zeros((2 * qs.size, nf))
+    _check(trm.lib().bartrt_posterior_spectrum_order(qs.size, wk, nf, _ptr(ranks), _ptr(ospec), _ptr(oband)))
+    return env_spec, env_band, status, ngood.value, ranks, ospec, oband
+
+
+def posterior_spectrum_rows(row0: int, nrows: int, wk: int) -> np.ndarray:
+    """Rows row0 .. row0 + nrows - 1 of the latest posterior_spectrum's sample matrix -> [nrows, wk] (``wk``: the
+    call's kept columns, env_spec.shape[1]): every sample's display curve, rejected samples' rows as they lie."""
+    out = np.zeros((int(nrows), int(wk)))
+    _check(trm.lib().bartrt_posterior_spectrum_rows(int(row0), int(nrows), _ptr(out)))
+    return out
+
+
 # ---- posterior marginals: histograms, ranges, HPD regions (include/bartrt.h, bartrt_marginals) ------------------
 def marginals_slab() -> int:
     """The rows one workgroup of the histogram kernels owns (tests place their shapes around it)."""

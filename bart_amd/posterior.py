@@ -18,6 +18,17 @@ csrc/hist_core.hpp).  No engine is needed for these.
     marginals(..., kde=True)                         and kde_x, kde_pdf, kde_bw, mean, std, cr_*: the Gaussian kernel
                                                      density of every parameter and its credible regions (bartrt_kde)
 
+And the curves of the best-fit spectrum figure (reference code/bestFit.py:528-688) as envelopes over the posterior: what
+the figure plots is the DISPLAY quantity, gaussian_filter1d(spectrum / sflux * rprs * rprs, 2) for an eclipse (:645-648)
+and gaussian_filter1d(spectrum, 2) otherwise (:655, :662), beside the band-integrated points.  Every sample goes through
+the step's whole run in chunks, one kernel turns a chunk's spectra into rows of the display quantity in HBM
+(include/bartrt.h, bartrt_posterior_spectrum; csrc/specenv_core.hpp has the rule), and the percentiles of every grid
+sample and of every band flux come from the same selection as T(p)'s.  The sample matrix takes nsamples * Wk * 8 bytes
+of device memory, Wk = ceil(nwave / stride).
+
+    spectrum_envelopes(output_npy, cfg, burnin)   wn, wl, median .. hi2 [Wk], band_median .. band_hi2 [F], meanwn, meanwl,
+                                                  data, uncert, status, ngood (best=...: best_spectrum, best_band)
+
 Plots stay out of scope.
 """
 from __future__ import annotations
@@ -69,9 +80,112 @@ def tp_envelopes(output_npy, cfg, burnin, thinning=1, layout=None, chunk=4096, s
 
 
 def save(path, env):
-    """tp_envelopes' curves, or marginals' arrays, as an .npz (retrieve --tp-envelopes, --marginals): every key but
-    ``samples``."""
+    """tp_envelopes' or spectrum_envelopes' curves, or marginals' arrays, as an .npz (retrieve --tp-envelopes,
+    --spectrum-envelopes, --marginals): every key but ``samples``."""
     np.savez(path, **{k: v for k, v in env.items() if k != "samples"})
+
+
+def gauss_half(sigma, truncate=4.0):
+    """The half k = 0 .. radius of the weights scipy.ndimage.gaussian_filter1d(x, sigma, truncate=truncate) smooths
+    with, made as SciPy makes them (_gaussian_kernel1d): radius = int(truncate * sigma + 0.5), exp(-0.5 / sigma**2 *
+    k**2) over k = -radius .. radius, divided by their sum.  sigma 2 gives radius 8.  The library takes radii 0 .. 64."""
+    sigma = float(sigma)
+    if not sigma > 0:
+        raise ValueError("gauss_half: sigma must be positive")
+    radius = int(float(truncate) * sigma + 0.5)
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    phi = phi / phi.sum()
+    return np.ascontiguousarray(phi[radius:])
+
+
+def display_of_samples(samples, sigma=2.0, stride=1, chunk=4096, sflux=None, want_order=False):
+    """The envelopes of the display quantity and of the band fluxes of full parameter vectors [n, npars] on an engine
+    whose step is set up (BARTfunc.Worker) and holds the whole grid.  ``sflux`` [nwave]: the stellar flux on the
+    engine's wavenumbers for an eclipse (stellar_flux), None for transit and direct geometry; ``sigma``: the smoothing
+    (None or 0: none); ``stride``: every stride-th grid sample is kept.
+    -> dict of ``median``, ``lo1``, ``hi1``, ``lo2``, ``hi2`` [Wk], ``band_median`` ... ``band_hi2`` [F] (NaN when no
+    sample was accepted), ``status`` [n] (0, 1 temperature, 2 abundance, 3 energy balance), ``ngood``, ``wn`` [Wk];
+    with ``want_order`` also ``ranks``, ``order``, ``band_order`` (None when no sample was accepted)."""
+    from . import engine, transit_module as trm
+    half = gauss_half(sigma) if sigma else np.ones(1)
+    stride = int(stride)
+    res = engine.posterior_spectrum(samples, list(LEVELS.values()), sflux, half, stride, chunk=max(1, int(chunk)),
+                                    want_order=want_order)
+    out = {k: res[0][i] for i, k in enumerate(LEVELS)}
+    out.update({"band_" + k: res[1][i] for i, k in enumerate(LEVELS)})
+    out.update(status=res[2], ngood=int(res[3]), wn=trm.get_waveno_arr(trm.get_no_samples())[::stride].copy())
+    if want_order:
+        out.update(ranks=res[4], order=res[5], band_order=res[6])
+    return out
+
+
+def stellar_flux(worker):
+    """The stellar flux on the worker's wavenumber grid for an eclipse -- bestFit.py:645-646's
+    si.interp1d(starwn, starfl)(specwn) of the Kurucz model the worker reads -- and None for the other geometries."""
+    from . import hostio
+    if worker.cfg.solution != "eclipse":
+        return None
+    starfl, starwn, _, _ = hostio.readkurucz(worker.cfg.kurucz, worker.tstar, worker.gstar)
+    return np.interp(worker.specwn, starwn, starfl)
+
+
+def read_best(best):
+    """A full parameter vector from ``best``: the vector itself, or the path of a bestFit.txt as bart_amd.retrieve
+    writes it (comment lines, then the parameters on one line)."""
+    if isinstance(best, (str, bytes, os.PathLike)):
+        best = np.loadtxt(best, comments="#")
+    return np.ascontiguousarray(best, np.double).ravel()
+
+
+def spectrum_envelopes_of_worker(worker, samples, sigma=2.0, stride=1, chunk=4096, best=None, data=None, uncert=None):
+    """spectrum_envelopes on a live BARTfunc.Worker (retrieve --spectrum-envelopes): every key but ``samples``."""
+    from . import hostio
+    sflux = stellar_flux(worker)
+    out = {}
+    if best is not None:
+        # the figure's blue curve and black points: one row through the same kernels (every percentile of one row is it)
+        one = display_of_samples(read_best(best)[None], sigma, stride, 1, sflux)
+        out.update(best_spectrum=one["median"], best_band=one["band_median"], best_status=int(one["status"][0]))
+    out.update(display_of_samples(samples, sigma, stride, chunk, sflux))
+    meanwn = []
+    for f in worker.cfg.filters:
+        fwn, ftr = hostio.readfilter(f)
+        meanwn.append(np.sum(fwn * ftr) / sum(ftr))             # (bestFit.py:604)
+    out.update(wl=1e4 / out["wn"], meanwn=np.array(meanwn), meanwl=1e4 / np.array(meanwn),
+               data=np.asarray(data if data is not None else [], np.double),
+               uncert=np.asarray(uncert if uncert is not None else [], np.double))
+    return out
+
+
+def spectrum_envelopes(output_npy, cfg, burnin, thinning=1, layout=None, sigma=2.0, stride=1, chunk=4096, best=None):
+    """The envelopes of the best-fit spectrum figure's curves (bestFit.py:528-688) over an MCMC posterior.
+    ``output_npy``, ``cfg``, ``burnin``, ``thinning``, ``layout``: as tp_envelopes takes them; the engine is initialised
+    on the cfg's ``tconfig`` (the whole grid on one GPU: a wavenumber-sharded engine is refused) and freed afterwards.
+    Every sample's spectrum becomes the display quantity -- for an eclipse gaussian_filter1d(spectrum / sflux * rprs *
+    rprs, sigma) with sflux the Kurucz model interpolated onto the engine's wavenumbers, otherwise
+    gaussian_filter1d(spectrum, sigma) -- on the GPU; ``stride`` keeps every stride-th grid sample (the smoothing runs
+    on the full grid), and the sample matrix takes nsamples * ceil(nwave / stride) * 8 bytes of device memory.
+    -> dict: ``wn``, ``wl`` (1e4 / wn) [Wk]; ``median``, ``lo1``, ``hi1``, ``lo2``, ``hi2`` [Wk] and ``band_median`` ...
+    ``band_hi2`` [F] (the percentiles of LEVELS over the accepted samples; NaN when none was accepted); ``meanwn``,
+    ``meanwl`` [F] (the filter-weighted mean wavenumber of bestFit.py:604, :618); ``data``, ``uncert`` from the cfg (read
+    as bart_amd.retrieve reads it: the run's whole [MCMC] section is expected);
+    ``status`` [n], ``ngood``, ``samples`` [n, npars].  ``best``: a full parameter vector or the path of a bestFit.txt
+    adds ``best_spectrum`` [Wk] and ``best_band`` [F] (the figure's blue curve and black points; ``best_status`` says
+    whether the vector was accepted), computed by the same kernels with one row."""
+    from . import BARTfunc, sampler
+    params, stepsize = cf._mcmc_vectors(cfg)
+    data = np.load(output_npy) if isinstance(output_npy, (str, bytes, os.PathLike)) else output_npy
+    samples = cf.posterior_samples(data, params, stepsize, burnin, thinning, layout)
+    scfg = sampler.SamplerConfig.from_cfg(cfg)      # (the reader retrieve uses: `data` and `uncert` as the run had them)
+    obs = (scfg.data, scfg.uncert)
+    w = BARTfunc.Worker(BARTfunc.WorkerConfig.from_cfg(cfg), carry=False)
+    try:
+        out = spectrum_envelopes_of_worker(w, samples, sigma, stride, chunk, best, *obs)
+    finally:
+        w.close()
+    out["samples"] = samples
+    return out
 
 
 # MC3's 1- and 2-sigma credible fractions

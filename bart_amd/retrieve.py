@@ -243,6 +243,12 @@ def main(argv=None):
                     help="after the run (after --resume: on the whole chain) write tp_envelopes.npz beside output.npy: "
                          "the median and the 1- and 2-sigma percentiles of T(p) over the rows past the burn-in "
                          "(bart_amd.posterior; not with walk = unif or --datasets)")
+    ap.add_argument("--spectrum-envelopes", action="store_true",
+                    help="after the run (after --resume: on the whole chain) write spectrum_envelopes.npz beside "
+                         "output.npy: the median and the 1- and 2-sigma percentiles of the smoothed model spectrum (flux "
+                         "ratio for an eclipse) and of the band fluxes over the rows past the burn-in, and the best fit's "
+                         "curve and points (bart_amd.posterior.spectrum_envelopes; on one GPU; not with walk = unif or "
+                         "--datasets)")
     ap.add_argument("--marginals", default=None, metavar="FILE.npz",
                     help="after the run (after --resume: on the whole chain) write the free parameters' 1-D and "
                          "pairwise histograms and their highest-density regions over the rows past the burn-in to "
@@ -299,6 +305,11 @@ def main(argv=None):
         ap.error("--grid-bands and --grid-f32 go with walk = unif")
     if a.tp_envelopes and (unif or a.datasets):
         ap.error("--tp-envelopes is the envelope of one retrieval's chain: not with walk = unif or --datasets")
+    if a.spectrum_envelopes and (unif or a.datasets):
+        ap.error("--spectrum-envelopes is the envelope of one retrieval's chain: not with walk = unif or --datasets")
+    if a.spectrum_envelopes and world > 1:
+        ap.error("--spectrum-envelopes needs whole spectra on one GPU: not on several ranks (run "
+                 "bart_amd.posterior.spectrum_envelopes on the written output.npy)")
     if a.marginals and (unif or a.datasets):
         ap.error("--marginals is the histograms of one retrieval's chain: not with walk = unif or --datasets")
     if a.marginals and not 1 <= a.marginals_bins <= 1024:
@@ -430,6 +441,18 @@ def main(argv=None):
         if rank == 0:
             posterior.save(os.path.join(out, "tp_envelopes.npz"), env)
         res["tp_envelopes"] = env
+    if a.spectrum_envelopes:
+        # the same rows on the engine the run used, and the run's best fit as the figure's curve and points
+        from . import cf, posterior
+        thin = max(1, int(scfg.thinning)) if a.resident else 1
+        rows = min(int(scfg.burnin) // thin, res["chain"].shape[1] - 1)
+        samples = cf.posterior_samples(res["chain"], scfg.params, scfg.stepsize, rows, layout="retrieve")
+        top = fitted if fitted is not None else res
+        senv = dict(posterior.spectrum_envelopes_of_worker(w, samples, best=top["bestp"], data=scfg.data,
+                                                           uncert=scfg.uncert), burnin=rows)
+        if rank == 0:
+            posterior.save(os.path.join(out, "spectrum_envelopes.npz"), senv)
+        res["spectrum_envelopes"] = senv
     if a.marginals:
         # the same rows; counted on this rank's GPU (no engine call: every rank gets the same integers, rank 0 writes)
         from . import cf, posterior

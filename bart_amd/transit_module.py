@@ -159,6 +159,13 @@ def lib():
         L.bartrt_posterior_tp.argtypes = [p, C.c_long, i, i, p, p, p, C.POINTER(C.c_long)]
         L.bartrt_posterior_set_chunk.argtypes = [C.c_long]
         L.bartrt_posterior_tp_order.argtypes = [i, i, p, p]
+        if hasattr(L, "bartrt_posterior_spectrum"):
+            L.bartrt_spectrum_display_dev.argtypes = [p, C.c_long, i, C.c_long, p, d, i, p, C.c_long, p, C.c_long, p]
+            L.bartrt_spectrum_display_tile.argtypes = [i, C.c_long, C.POINTER(C.c_long)]
+            L.bartrt_posterior_spectrum.argtypes = [p, C.c_long, i, i, p, p, i, p, C.c_long, p, p, p, C.POINTER(C.c_long)]
+            L.bartrt_posterior_spectrum_shape.argtypes = [C.c_long, C.POINTER(C.c_long), C.POINTER(i)]
+            L.bartrt_posterior_spectrum_order.argtypes = [i, C.c_long, i, p, p, p]
+            L.bartrt_posterior_spectrum_rows.argtypes = [C.c_long, C.c_long, p]
         L.bartrt_percentile_rule.argtypes = [C.c_long, d, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(d)]
         L.bartrt_percentile_lerp.argtypes = [p, p, d, p, C.c_long]
         if hasattr(L, "bartrt_marginals"):

@@ -880,6 +880,66 @@ int bartrt_posterior_tp_order(int nq, int nlayers, long *ranks, double *order);
 int bartrt_percentile_rule(long n, double q, long *lo, long *hi, double *w);
 int bartrt_percentile_lerp(const double *a, const double *b, double w, double *out, long n);
 
+/* ---- posterior spectra: the display quantity, spectrum and band-flux envelopes (csrc/specenv.hip,
+ * csrc/specenv_core.hpp) ----
+ * What the reference's best-fit spectrum figure plots (reference code/bestFit.py:528-688) is the DISPLAY QUANTITY of a
+ * model spectrum: for an eclipse gaussian_filter1d(spectrum / sflux * rprs * rprs, 2) (:645-648), for transit and direct
+ * geometry gaussian_filter1d(spectrum, 2) (:655, :662).  The rule, stated once for host and device:
+ *   value      with a stellar flux y[i] = x[i] / sflux[i] * rprs * rprs, left to right (numpy's bits); without, x[i]
+ *   smoothing  scipy.ndimage.correlate1d with the symmetric kernel half[0..r] (half[0] the centre, 0 <= r <= 64) in
+ *              mode `reflect` (d c b a | a b c d | d c b a, repeated as often as needed: any row length from 1);
+ *              the centre term first, then the pairs (y[l-j] + y[l+j]) half[j] from j = r inwards, no contraction.
+ *              r = 0 is the identity.  The library does not compute weights: the caller passes them
+ *              (bart_amd.posterior.gauss_half makes SciPy's for a sigma)
+ *   stride     >= 1: output column c is grid sample c * stride, Wk = ceil(nwave / stride) columns; the smoothing
+ *              always runs on the full grid
+ * bartrt_spectrum_display_dev: the kernel alone on device buffers, asynchronous on `stream` (NULL: the engine's own).
+ *   d_spec[nrows][ld]  spectra, the first nwave <= ld samples of every row read
+ *   d_sflux[nwave]     or NULL
+ *   half[r + 1]        HOST
+ *   d_out[nrows][ldo]  the first Wk <= ldo columns of every row written, every value by exactly one lane: the result
+ *                      depends on no launch shape
+ *   BARTRT_EINVAL      r outside 0..64, stride < 1, ld < nwave, ldo < Wk, nrows < 1, nwave < 1, a NULL buffer; the
+ *                      message names the argument.  It needs an initialised engine for the stream only.
+ * bartrt_spectrum_display_tile: *cols = the kept output columns one workgroup owns for (r, stride) (tests place
+ * their shapes around it).
+ *
+ * bartrt_posterior_spectrum: the percentile envelopes of the display quantity and of the band fluxes of a posterior,
+ * after bartrt_step_setup (whose rprs is the one used).
+ *   params[nsamples][npars]  HOST, rows as bartrt_step_batch takes them; they go through bartrt_step_batch_dev in
+ *                    chunks (bartrt_posterior_set_chunk rows, at most 4096: a larger setting is cut to that, and
+ *                    every launch's RT kernel variant is chosen as for 4096 walkers, so the result does not depend
+ *                    on the chunk; a one-row call therefore runs the large-batch variant, not the small-batch
+ *                    forms bartrt_step_batch_dev would pick), every chunk's spectra through the display kernel
+ *                    into one [nsamples][Wk] matrix on the device -- nsamples * Wk * 8 bytes; where that does not
+ *                    fit, BARTRT_EINVAL names the bytes: raise stride, or thin the samples -- and its band fluxes
+ *                    into one [nsamples][nfilters] matrix
+ *   q[nq]            1 <= nq <= 8 percents in [0, 100]
+ *   sflux[nwave]     HOST or NULL: the stellar flux on the engine's wavenumber grid (eclipse)
+ *   env_spec[nq][Wk], env_band[nq][nfilters]   HOST: percentile q[i] of every column over the accepted samples, by
+ *                    np.percentile's default rule from two order statistics selected on the device (bartrt_colselect_dev)
+ *   status[nsamples] 0, 1 (temperature), 2 (abundance), 3 (energy balance): every status but 0 drops the sample;
+ *                    bartrt_step_set_carry has no effect
+ *   *ngood           the accepted samples.  None accepted: both envelopes are NaN, *ngood = 0, the call succeeds.
+ *   BARTRT_ENOTSUP   a wavenumber-sharded engine (the spectra are not whole on this GPU).  Line-by-line engines
+ *                    are served.
+ * bartrt_posterior_spectrum_shape: *Wk = ceil(nwave / stride) and *F = the filters of bartrt_step_setup: the widths
+ * of the envelopes a call with that stride writes.
+ * bartrt_posterior_spectrum_order: the order statistics behind the latest envelope: ranks[2 nq] (lo, hi of each
+ * percent), order_spec[2 nq][Wk], order_band[2 nq][F]; BARTRT_EINVAL when there is none of that shape.
+ * bartrt_posterior_spectrum_rows: rows row0 .. row0 + nrows - 1 of the latest sample matrix -> out[nrows][Wk] (HOST),
+ * rejected samples' rows included as they lie; BARTRT_EINVAL when there is no matrix or the range is outside it. */
+int bartrt_spectrum_display_dev(const double *d_spec, long nrows, int nwave, long ld, const double *d_sflux,
+                                double rprs, int r, const double *half, long stride, double *d_out, long ldo,
+                                void *stream);
+int bartrt_spectrum_display_tile(int r, long stride, long *cols);
+int bartrt_posterior_spectrum(const double *params, long nsamples, int npars, int nq, const double *q,
+                              const double *sflux, int r, const double *half, long stride, double *env_spec,
+                              double *env_band, int *status, long *ngood);
+int bartrt_posterior_spectrum_shape(long stride, long *Wk, int *F);
+int bartrt_posterior_spectrum_order(int nq, long Wk, int F, long *ranks, double *order_spec, double *order_band);
+int bartrt_posterior_spectrum_rows(long row0, long nrows, double *out);
+
 /* ---- posterior marginals: 1-D and pairwise histograms, their range, HPD regions (csrc/hist.hip,
  * csrc/hist_core.hpp) ----
  * The numbers behind MC3's `histogram` and `pairwise` figures (reference code/mc3plots.py:45-82).  NO ENGINE is
